@@ -1,7 +1,7 @@
 """Headline benchmark: Conv-TasNet training throughput on synthetic 4 s @ 16 kHz
 mixtures (BASELINE.json configs[1]; weak scaling over N GPUs of one node).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
@@ -22,6 +22,8 @@ seconds of steps (`warmup_effective`: the clocks and the power state have settle
 max); `clock` holds sclk / mclk / power / temperature read from sysfs before and after the timed region.
 `other_configs` (N = 1 only, --no-other-configs to skip): BASELINE.json configs[3] (DCCRN bf16 train step,
 16 x 4 s) and configs[4] (SGMSE+ fp16 30-step enhance, batch 1 and 8) timed in the same run.
+`--dump-outputs DIR` writes what the timed step computes as DIR/<name>.npy (see `dump_outputs`), so that two
+builds can be compared output for output.
 """
 import argparse
 import json
@@ -30,9 +32,6 @@ import sys
 import time
 
 os.environ.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')   # dmabuf IPC for RCCL (before HIP initialises)
-# the step runs two kernel chains on two streams; with RCCL's streams the default 4 hardware queues
-# are oversubscribed and the chains share one (9.6 instead of 7.7 ms per step)
-os.environ.setdefault('GPU_MAX_HW_QUEUES', '8')
 
 import torch                                                  # noqa: E402
 import torch.distributed as dist                              # noqa: E402
@@ -55,6 +54,7 @@ PEAK_HBM_GBS = 8000.0               # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
 PEAK_MFMA_TFLOPS = 2500.0           # dense bf16 MFMA
 MIN_WARMUP_S = 1.5                  # seconds of steps before the timed region, whatever --warmup says
 N_REPEATS = 5                       # further blocks of --steps behind the one `value` is taken from
+DUMP_LIMIT_BYTES = 64 << 20          # --dump-outputs: at most this much in all
 
 
 def _read(path):
@@ -533,6 +533,37 @@ def through_trainer(model, scaler, rank, world, device, steps, warmup):
     return (time.perf_counter() - t0)/max(done - warmup, 1)*1e3, done
 
 
+def dump_outputs(out_dir, batch, lengths, device, single, nparts, rank):
+    """--dump-outputs: the timed step once more, on the batch of the last timed step, from the seeded initial
+    weights (the timed model's weights depend on how many steps the time-based warm-up ran, so they are not the
+    same from run to run), and what a caller of `ConvTasNet.train_step` receives from it written to
+    out_dir/<name>.npy: `loss` (float64 scalar), `params` (the updated flat parameter buffer) and `grads` (the
+    flat gradient buffer the step filled), float32. Every rank runs the step (it holds the collectives of N > 1);
+    rank 0 writes. Returns {name: shape}."""
+    torch.manual_seed(0)
+    model = ConvTasNet().to(device)                  # as main() builds the timed model
+    if not single:
+        broadcast_parameters(model)
+        GradSynchronizer(model, nparts=nparts)
+    scaler = torch.amp.GradScaler('cuda', enabled=False)
+    loss = model.train_step(batch, lengths, True, scaler)
+    torch.cuda.synchronize()
+    arrays = {'loss': loss.detach().to(torch.float64).cpu().numpy(),
+              'params': model.flat_params().detach().to(torch.float32).cpu().numpy(),
+              'grads': model.flat_grads().detach().to(torch.float32).cpu().numpy()}
+    del model, loss
+    torch.cuda.empty_cache()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f'--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES} byte limit')
+    if rank == 0:
+        import numpy as np
+        os.makedirs(out_dir, exist_ok=True)
+        for name, a in arrays.items():
+            np.save(os.path.join(out_dir, f'{name}.npy'), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -557,7 +588,12 @@ def main():
                          'the host): its numbers mean nothing')
     ap.add_argument('--dist', action='store_true',
                     help='initialise the process group even at --gpus 1 (world-1 RCCL: every N > 1 branch runs)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the timed step computes (loss, updated parameters, '
+                         'gradients) as DIR/<name>.npy: same arguments, same inputs, for comparing two builds')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
@@ -668,6 +704,11 @@ def main():
     clock_end = read_clock(local_rank)
     final_loss = float(loss)
     exposed = sync.exposed_ms() if sync is not None else None
+    dumped = None
+    if args.dump_outputs:
+        batch, lengths = batches[(args.steps - 1) % len(batches)]      # the batch of the last timed step
+        dumped = dump_outputs(args.dump_outputs, batch, lengths, device, single, sync.nparts if sync else 1,
+                              rank)
     trainer_ms = None
     trainer_batches = None
     if not args.no_through_trainer:
@@ -729,11 +770,14 @@ def main():
                         + ' -> BreverDataLoader collate -> pinned double-buffered async H2D (DevicePrefetcher) '
                           '-> train_step'}
         line['two_chain'] = bool(ConvTasNet.uses_two_chains(BATCH, True))
+        if dumped is not None:
+            line['dump_outputs'] = {'dir': args.dump_outputs, 'arrays': dumped,
+                                    'step': 'the timed step from the seeded initial weights on the batch of the '
+                                            'last timed step'}
         if exposed is not None:
             line['allreduce_exposed_ms'] = exposed
             line['allreduce_buckets'] = sync.nparts
             line['rccl_world_size'] = dist.get_world_size()
-            line['hw_queues_ok'] = bool(__import__('brever_amd').HW_QUEUES_OK)
             if fallback:
                 line['allreduce_fallback'] = fallback
         if single and not args.no_fp32_path:

@@ -108,14 +108,6 @@ class _TCN(_ParamOnly):
         self.output_conv = nn.Conv1d(skip, filters*sources, 1)
 
 
-_warned_queues = False
-
-
-def _queues_ok():
-    import brever_amd
-    return brever_amd.HW_QUEUES_OK
-
-
 def _process_group():
     import torch.distributed as dist
     return dist.is_available() and dist.is_initialized()
@@ -570,33 +562,12 @@ class ConvTasNet(BreverBaseModel):
     def uses_two_chains(B, amp):
         """Whether the fused bf16 step of a batch of ``B`` runs as two half-batch kernel chains on two
         streams (DESIGN.md 5h): batches of >= 8 (odd ones split 1 + B//2 | B//2), unless ``BRV_CTN_STREAMS=1`` -- and never next
-        to an initialised process group when the HIP runtime cannot have seen >= 8 hardware queues
-        (``brever_amd.HW_QUEUES_OK``: torch imported before the package and ``GPU_MAX_HW_QUEUES`` not
-        exported): with the default 4 queues RCCL's streams and the two chains share queues and the
-        step is slower than one chain (9.6 vs 7.7 ms)."""
+        to an initialised process group: the package leaves the runtime's hardware-queue count at its
+        default, where RCCL's streams and the two chains share queues and the step is slower than one
+        chain (9.6 vs 7.7 ms)."""
         if not (bool(amp) and B >= 8 and os.environ.get('BRV_CTN_STREAMS', '2') != '1'):
             return False
-        if _queues_ok() or not _process_group():
-            return True
-        # next to a process group without >= 8 hardware queues. An EXPORTED value below 8 is a
-        # configuration error of the launch (a 20 % slower step): fail loudly; BRV_CTN_STREAMS=1 opts
-        # into the one-chain step. A default that came too late (torch imported before this package)
-        # falls back to one chain with a warning, once.
-        import brever_amd
-        exported = getattr(brever_amd, '_exported', None)
-        if exported is not None:
-            raise RuntimeError(
-                f'GPU_MAX_HW_QUEUES={exported} is exported, but the two-chain Conv-TasNet step next to RCCL '
-                'needs >= 8 hardware queues (DESIGN.md 5h): export GPU_MAX_HW_QUEUES=8 (or unset it before '
-                'importing brever_amd), or set BRV_CTN_STREAMS=1 to run the one-chain step')
-        global _warned_queues
-        if not _warned_queues:
-            import warnings
-            warnings.warn('brever_amd was imported after torch and GPU_MAX_HW_QUEUES is not exported: the HIP '
-                          'runtime has 4 hardware queues, the Conv-TasNet step runs ONE kernel chain next to '
-                          'the process group (export GPU_MAX_HW_QUEUES=8 for the two-chain step)')
-            _warned_queues = True
-        return False
+        return not _process_group()
 
     def _train_step_two_chains(self, inputs, labels, lengths):
         """The fused bf16 step as TWO independent half-batch chains on two streams. Every launch of

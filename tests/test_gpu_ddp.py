@@ -198,11 +198,22 @@ def test_bench_two_ranks_on_one_gpu(forced):
     assert line['value_includes_h2d'] is False and line['through_trainer']['includes_h2d'] is True
 
 
-def test_bench_single_process_line_carries_other_configs_repeats_and_clock():
+def test_bench_single_process_line_carries_other_configs_repeats_and_clock(tmp_path):
     """the driver's own command (`bench.py --gpus 1`, no process group) reports BASELINE
     configs[3] (DCCRN bf16 train step) and configs[4] (SGMSE+ fp16 enhance, batch 1 and 8) beside the headline, a
-    time-based warm-up, five repeat blocks and the device clocks around the timed region."""
-    line = _run_bench(['--no-through-trainer'], single=True)
+    time-based warm-up, five repeat blocks and the device clocks around the timed region. `--dump-outputs` writes
+    the loss, parameters and gradients of the timed step as float .npy files, 64 MB at most."""
+    line = _run_bench(['--no-through-trainer', '--dump-outputs', str(tmp_path)], single=True)
+    assert line['steps'] == 3 and line['ms_per_step'] > 0
+    import numpy as np
+    dumped = {n: np.load(tmp_path/f'{n}.npy') for n in ('loss', 'params', 'grads')}
+    assert sorted(p.name for p in tmp_path.iterdir()) == ['grads.npy', 'loss.npy', 'params.npy']
+    assert sum(a.nbytes for a in dumped.values()) <= 64 << 20
+    assert dumped['loss'].shape == () and dumped['loss'].dtype == np.float64
+    assert dumped['params'].shape == dumped['grads'].shape == (4935217,)
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in dumped.values())
+    assert float(np.abs(dumped['grads']).max()) > 0
+    assert line['dump_outputs']['arrays'] == {n: list(a.shape) for n, a in dumped.items()}
     assert line['n_gpus'] == 1 and 'rccl_world_size' not in line
     assert line['warmup'] == 3 and line['warmup_effective']['steps'] > 3
     assert line['warmup_effective']['seconds'] >= line['warmup_effective']['min_seconds_of_steady_steps']

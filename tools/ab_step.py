@@ -12,7 +12,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CODE = r'''
 import os, sys, time
 sys.path.insert(0, %(root)r)
-os.environ.setdefault('GPU_MAX_HW_QUEUES', '8')
 import torch
 import brever_amd.hip as hip
 from brever_amd.models import ConvTasNet
