@@ -99,6 +99,12 @@ SIGNATURES = {
                                            _c_i64, _c_i64, _c_ptr]),
     'brv_ctn_f32_backward': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr,
                                             _c_ptr, _c_i64, _c_i64, _c_ptr]),
+    'brv_ctn_stream_state_bytes': (_c_i64, [_c_ptr]),
+    'brv_ctn_stream_workspace_bytes': (_c_i64, [_c_ptr, _c_i64, _c_i64, ctypes.c_int32]),
+    'brv_ctn_stream_reset': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_i64, _c_ptr]),
+    'brv_ctn_stream_step': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_ptr,
+                                           ctypes.c_int32, _c_ptr, _c_i64, _c_ptr, _c_ptr]),
+    'brv_ctn_stream_tail': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_i64, _c_ptr, _c_ptr]),
     'brv_resample_poly': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_ptr] + [_c_i64]*7 + [_c_ptr]),
     'brv_stoi_frames': (_c_i64, [_c_i64]),
     'brv_stoi_compact': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64, _c_ptr, _c_ptr,

@@ -163,6 +163,31 @@ int brv_ctn_f32_backward_part(const brv_ctn_config* cfg, const float* params,
                               float* grads, int64_t batch, int64_t length,
                               int32_t part, int32_t nparts, brv_stream_t stream);
 
+/* ---- streaming inference of the causal Conv-TasNet (csrc/ctn_stream.hip) ----------------------
+ * A caller-owned state buffer holds `slots` streams, brv_ctn_stream_state_bytes each (slot i at byte
+ * i * state_bytes). One step advances the n streams whose slot ids are listed (distinct, any order,
+ * int32 on the device) by `hops` hops of filter_length/2 samples: x (n, hops*hop) fp32 new mono input ->
+ * y (n, sources, hops*hop) fp32, the output one hop behind the input (zeros for the first hop of a
+ * stream). Concatenated over the steps of a stream and followed by the flush (one more step on the
+ * zero-padded last partial hop, if any, then brv_ctn_stream_tail), the output minus its first hop is
+ * ConvTasNet.forward of the whole signal, up to the summation order of the statistics. amp = 0: fp32
+ * products (v_mfma_f32_16x16x4_f32); amp = 1: bf16 operands, fp32 accumulation and state. The flat
+ * fp32 parameters are read as they are at each step; a stream's output does not depend on which other
+ * streams share the step. Causal models only (-3 otherwise), filter_length even, kernel_size <= 8,
+ * channel counts <= 992 (-2 otherwise). `opts` may be NULL (no option of these calls yet). */
+int64_t brv_ctn_stream_state_bytes(const brv_ctn_config* cfg);
+int64_t brv_ctn_stream_workspace_bytes(const brv_ctn_config* cfg, int64_t n, int64_t hops, int32_t amp);
+/* put the listed slots back to the start of a stream */
+int brv_ctn_stream_reset(const brv_ctn_config* cfg, void* state, const int32_t* ids, int64_t n,
+                         brv_stream_t stream);
+int brv_ctn_stream_step(const brv_ctn_config* cfg, const float* params, void* state, const int32_t* ids,
+                        int64_t n, const float* x, int64_t hops, float* y, int32_t amp, void* workspace,
+                        int64_t workspace_bytes, const brv_launch_opts* opts, brv_stream_t stream);
+/* overlap-add tail of the listed slots -> y (n, sources, hop): the samples still owed at the end of
+ * the input */
+int brv_ctn_stream_tail(const brv_ctn_config* cfg, const void* state, const int32_t* ids, int64_t n,
+                        float* y, brv_stream_t stream);
+
 /* ---- criteria (brever/criterion.py) ---------------------------------------
  * x, y: (batch, sources, length) fp32 contiguous rows with `stride` floats
  * between rows; lengths: (batch,) int64 on the device; scratch: at least

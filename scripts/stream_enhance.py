@@ -1,0 +1,71 @@
+"""Enhance a WAV or FLAC file chunk by chunk through a trained causal Conv-TasNet, as a live stream
+would arrive (brever_amd.streaming): the output is written as 16-bit FLAC through the native encoder
+and the real-time factor (compute time / audio time) is printed.
+
+    python scripts/stream_enhance.py -i models/<id> input.flac output.flac [--chunk-ms 16] [--use-amp]
+"""
+import argparse
+import os
+import time
+
+import _common  # noqa: F401  (puts the repository root on sys.path)
+import torch
+
+from brever_amd.config import get_config
+from brever_amd.data import audio_read, write_flac
+from brever_amd.models import ModelRegistry
+
+
+def main():
+    p = argparse.ArgumentParser(description='stream a file through a causal Conv-TasNet')
+    p.add_argument('-i', '--input', required=True, help='model directory (or a .ckpt file in it)')
+    p.add_argument('audio', help='input WAV or FLAC file (channels are averaged, as enhance does)')
+    p.add_argument('output', help='output FLAC file (the first source)')
+    p.add_argument('--chunk-ms', type=float, default=16.0, help='chunk length, rounded down to whole hops')
+    p.add_argument('--use-amp', action='store_true', help='bf16 operands (fp32 accumulation and state)')
+    args = p.parse_args()
+
+    from brever_amd.streaming import ConvTasNetStreamer
+    if args.input.endswith('.ckpt'):
+        model_dir, ckpt = os.path.dirname(os.path.dirname(args.input)), args.input
+    else:
+        model_dir, ckpt = args.input, os.path.join(args.input, 'checkpoints', 'last.ckpt')
+    cfg = get_config(os.path.join(model_dir, 'config.yaml'))
+    if cfg.arch != 'convtasnet':
+        raise SystemExit(f'{model_dir}: streaming needs a convtasnet model, got {cfg.arch}')
+    model = ModelRegistry.get(cfg.arch)(**cfg.model.to_dict()).cuda()
+    state = torch.load(ckpt, map_location='cuda', weights_only=False)
+    model.load_state_dict(state['model'])
+    if 'ema' in state:
+        from brever_amd.training import ExponentialMovingAverage
+        ema = ExponentialMovingAverage(model.parameters(), decay=cfg.trainer.ema_decay)
+        ema.load_state_dict(state['ema'])
+        ema.copy_to()
+        model.mark_params_changed()
+
+    with open(args.audio, 'rb') as f:
+        x, fs = audio_read(f, args.audio)
+    x = torch.as_tensor(x, dtype=torch.float32)
+    x = (x.mean(dim=1) if x.dim() == 2 else x).cuda()
+    s = ConvTasNetStreamer(model, max_streams=1, use_amp=args.use_amp)
+    hop = s.hop
+    chunk = max(1, int(args.chunk_ms*fs/1000)//hop)*hop
+    ids = s.open(1)
+    L = x.numel()
+    whole = L//hop*hop
+    outs = []
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for i in range(0, whole, chunk):
+        outs.append(s.process(x[None, i:min(i + chunk, whole)], ids))
+    outs.append(s.flush(ids, x[None, whole:] if L > whole else None))
+    torch.cuda.synchronize()
+    elapsed = time.perf_counter() - t0
+    y = torch.cat(outs, dim=-1)[0, 0, hop:].cpu().numpy()
+    write_flac(args.output, y, fs)
+    print(f'{args.audio}: {L/fs:.2f} s in chunks of {1e3*chunk/fs:.1f} ms, {elapsed:.3f} s, '
+          f'real-time factor {elapsed/(L/fs):.4f}')
+
+
+if __name__ == '__main__':
+    main()
