@@ -32,6 +32,20 @@ class LaunchOpts(ctypes.Structure):
                 ('wg_target', ctypes.c_int32), ('prof', ctypes.c_void_p)]
 
 
+DCCRN_STREAM_MAX_LEVELS = 8
+
+
+class DccrnStreamConfig(ctypes.Structure):
+    """``brv_dccrn_stream_config`` -- geometry, flat-parameter offsets and running-buffer addresses of a
+    DCCRN for the streaming entry points."""
+    _M = DCCRN_STREAM_MAX_LEVELS
+    _fields_ = [(name, ctypes.c_int32) for name in (
+        'n_fft', 'hop', 'levels', 'kf', 'kt', 'sf', 'pf', 'opf', 'st', 'pt', 'opt', 'complex_bn')] + [
+        ('channels', ctypes.c_int32*_M), ('lstm_hidden', ctypes.c_int32), ('lstm_layers', ctypes.c_int32),
+        ('eps', ctypes.c_float*(2*_M)), ('off_block', (_c_i64*7)*(2*_M)), ('off_lstm', ((_c_i64*4)*2)*4),
+        ('off_linear', _c_i64*4), ('run_mean', _c_ptr*(2*_M)), ('run_var', _c_ptr*(2*_M))]
+
+
 OPT_NO_FWD_FUSE, OPT_NO_BWD_FUSE, OPT_NO_WS, OPT_DWPW2_WS = 0x001, 0x002, 0x004, 0x008
 OPT_NO_DZ_FUSE, OPT_NO_DZ1_FUSE, OPT_NO_WGRAD_FULL, OPT_NO_WGRAD_SPLIT = 0x010, 0x020, 0x040, 0x080
 OPT_NO_PW1_RC, OPT_PW1_RC_WGRAD, OPT_PW1_RC_TILES, OPT_DWPW2_V2, OPT_NO_WGRAD_128, OPT_BWD_PERSIST = 0x100, 0x200, 0x400, 0x800, 0x1000, 0x2000
@@ -105,6 +119,13 @@ SIGNATURES = {
     'brv_ctn_stream_step': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_ptr,
                                            ctypes.c_int32, _c_ptr, _c_i64, _c_ptr, _c_ptr]),
     'brv_ctn_stream_tail': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_i64, _c_ptr, _c_ptr]),
+    'brv_dccrn_stream_state_bytes': (_c_i64, [_c_ptr]),
+    'brv_dccrn_stream_workspace_bytes': (_c_i64, [_c_ptr, _c_i64, _c_i64, ctypes.c_int32]),
+    'brv_dccrn_stream_reset': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_i64, _c_ptr]),
+    'brv_dccrn_stream_step': (ctypes.c_int, [_c_ptr]*7 + [_c_i64, _c_ptr, _c_i64, _c_ptr, ctypes.c_int32, _c_ptr,
+                                                         _c_i64, _c_ptr, _c_ptr]),
+    'brv_dccrn_stream_tail': (ctypes.c_int, [_c_ptr]*7 + [_c_i64, _c_ptr, _c_i64, _c_ptr, ctypes.c_int32, _c_ptr,
+                                                         _c_i64, _c_ptr, _c_ptr]),
     'brv_resample_poly': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_ptr] + [_c_i64]*7 + [_c_ptr]),
     'brv_stoi_frames': (_c_i64, [_c_i64]),
     'brv_stoi_compact': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64, _c_ptr, _c_ptr,

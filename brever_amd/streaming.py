@@ -11,6 +11,11 @@ the summation order of the layer-norm statistics).
 The kernels read the model's flat fp32 parameters at every step, as the offline fp32 path does, so an
 optimizer step, ``load_state_dict`` or ``mark_params_changed`` takes effect at the next ``process``.
 Streams that are already open keep the state they computed with the old parameters.
+
+A :class:`DCCRNStreamer` does the same for :class:`~brever_amd.models.DCCRN` (C ABI ``brv_dccrn_stream_*``,
+``csrc/dccrn_stream.hip``) at the model's own latency: its output lags the input by
+``lag = model.latency - hop`` samples, and the concatenated output minus the first ``lag`` samples is
+``enhance`` of the model in eval mode.
 """
 import ctypes
 
@@ -19,38 +24,8 @@ import torch
 from . import hip
 
 
-class ConvTasNetStreamer:
-    """Many concurrent streams of one causal :class:`~brever_amd.models.ConvTasNet` on its device.
-
-    ``use_amp=False``: fp32 products (the precision of ``enhance(x, use_amp=False)``);
-    ``use_amp=True``: bf16 operands with fp32 accumulation and state."""
-
-    def __init__(self, model, max_streams=64, use_amp=False):
-        from .models.convtasnet import ConvTasNet
-        if not isinstance(model, ConvTasNet):
-            raise ValueError(f'streaming needs a ConvTasNet, got {type(model).__name__}')
-        if not model.cfg.causal:
-            raise ValueError('streaming needs a causal ConvTasNet: the global layer norm of the '
-                             'non-causal model needs the whole signal')
-        if model.cfg.filter_length % 2:
-            raise ValueError('streaming needs an even filter_length (hop = filter_length // 2)')
-        if int(max_streams) < 1:
-            raise ValueError(f'max_streams must be >= 1, got {max_streams}')
-        hip.require_device(model.flat_params())
-        self.model = model
-        self.use_amp = bool(use_amp)
-        self.max_streams = int(max_streams)
-        self.hop = model.cfg.filter_length//2
-        self.sources = model.output_sources
-        nbytes = hip.lib().brv_ctn_stream_state_bytes(model._cfg_ptr())
-        if nbytes < 0:
-            hip.check(int(nbytes), 'brv_ctn_stream_state_bytes')
-        self.state_bytes = int(nbytes)
-        self._state = torch.zeros(self.max_streams*self.state_bytes, dtype=torch.uint8,
-                                  device=model.flat_params().device)
-        self._open = [False]*self.max_streams
-        self._ws = None
-        self._ids_cache = None
+class _StreamSlots:
+    """Slot bookkeeping shared by the streamers: ``max_streams`` slots of ``state_bytes`` in one HBM buffer."""
 
     @property
     def device(self):
@@ -99,11 +74,6 @@ class ConvTasNetStreamer:
             self._ids_cache = (key, torch.tensor(ids, dtype=torch.int32).to(self.device))
         return self._ids_cache[1]
 
-    def _reset(self, ids):
-        t = self._ids_tensor(ids)
-        hip.check(hip.lib().brv_ctn_stream_reset(self.model._cfg_ptr(), hip.ptr(self._state), hip.ptr(t),
-                                                 len(ids), hip.stream()), 'brv_ctn_stream_reset')
-
     def _mono(self, x, n):
         hip.require_device(x)
         if x.dim() == 3:
@@ -112,6 +82,46 @@ class ConvTasNetStreamer:
             raise ValueError(f'input must be (n, samples) or (n, channels, samples) with n = {n} streams, '
                              f'got {tuple(x.shape)}')
         return x.float().contiguous()
+
+
+class ConvTasNetStreamer(_StreamSlots):
+    """Many concurrent streams of one causal :class:`~brever_amd.models.ConvTasNet` on its device.
+
+    ``use_amp=False``: fp32 products (the precision of ``enhance(x, use_amp=False)``);
+    ``use_amp=True``: bf16 operands with fp32 accumulation and state."""
+
+    def __init__(self, model, max_streams=64, use_amp=False):
+        from .models.convtasnet import ConvTasNet
+        if not isinstance(model, ConvTasNet):
+            raise ValueError(f'streaming needs a ConvTasNet, got {type(model).__name__}')
+        if not model.cfg.causal:
+            raise ValueError('streaming needs a causal ConvTasNet: the global layer norm of the '
+                             'non-causal model needs the whole signal')
+        if model.cfg.filter_length % 2:
+            raise ValueError('streaming needs an even filter_length (hop = filter_length // 2)')
+        if int(max_streams) < 1:
+            raise ValueError(f'max_streams must be >= 1, got {max_streams}')
+        hip.require_device(model.flat_params())
+        self.model = model
+        self.use_amp = bool(use_amp)
+        self.max_streams = int(max_streams)
+        self.hop = model.cfg.filter_length//2
+        self.lag = self.hop               # the output lags the input by one hop
+        self.sources = model.output_sources
+        nbytes = hip.lib().brv_ctn_stream_state_bytes(model._cfg_ptr())
+        if nbytes < 0:
+            hip.check(int(nbytes), 'brv_ctn_stream_state_bytes')
+        self.state_bytes = int(nbytes)
+        self._state = torch.zeros(self.max_streams*self.state_bytes, dtype=torch.uint8,
+                                  device=model.flat_params().device)
+        self._open = [False]*self.max_streams
+        self._ws = None
+        self._ids_cache = None
+
+    def _reset(self, ids):
+        t = self._ids_tensor(ids)
+        hip.check(hip.lib().brv_ctn_stream_reset(self.model._cfg_ptr(), hip.ptr(self._state), hip.ptr(t),
+                                                 len(ids), hip.stream()), 'brv_ctn_stream_reset')
 
     # ---- compute --------------------------------------------------------------------------------
     def process(self, x, ids):
@@ -171,16 +181,227 @@ class ConvTasNetStreamer:
         return torch.cat(out, dim=-1)
 
 
+class DCCRNStreamer(_StreamSlots):
+    """Many concurrent streams of one :class:`~brever_amd.models.DCCRN` on its device, at the model's own
+    latency: the output lags the input by ``lag = model.latency - hop`` samples (the first ``lag`` are
+    zeros). Batch norms always use their running statistics (the model in eval mode, whatever
+    ``model.training`` says); the flat parameters and the running buffers are read where they live at
+    every call.
+
+    ``use_amp=False``: fp32 products (the precision of ``enhance(x, use_amp=False)``);
+    ``use_amp=True``: bf16 operands with fp32 accumulation, activations and state."""
+
+    def __init__(self, model, max_streams=64, use_amp=False):
+        self.lag = self.lag_for(model)           # (validates the model)
+        if int(max_streams) < 1:
+            raise ValueError(f'max_streams must be >= 1, got {max_streams}')
+        nbytes = hip.lib().brv_dccrn_stream_state_bytes(ctypes.byref(self._geometry(model)))
+        if nbytes < 0:
+            raise ValueError(f'this DCCRN cannot stream: {hip.lib().brv_last_error().decode()}')
+        hip.require_device(model.flat_params())
+        self.model = model
+        self.use_amp = bool(use_amp)
+        self.max_streams = int(max_streams)
+        self.hop = model.stft.hop_length
+        self.state_bytes = int(nbytes)
+        self._state = torch.zeros(self.max_streams*self.state_bytes, dtype=torch.uint8,
+                                  device=model.flat_params().device)
+        self._open = [False]*self.max_streams
+        self._hops = [0]*self.max_streams          # hops received per slot
+        self._ended = [False]*self.max_streams     # flushed: reset or close before the next process
+        self._ws = None
+        self._ids_cache = None
+        self._offsets = None
+
+    # ---- configuration --------------------------------------------------------------------------
+    @staticmethod
+    def lag_for(model):
+        """Output lag of a DCCRN stream in samples (``model.latency - hop``); ``ValueError`` for a model
+        the streaming kernels do not take."""
+        from .models.dccrn import DCCRN
+        if not isinstance(model, DCCRN):
+            raise ValueError(f'streaming needs a DCCRN, got {type(model).__name__}')
+        (kf, kt), (sf, st), (pf, pt), (opf, opt) = model.mask_net.geom
+        if st != 1 or pt != 0 or opt != 0:
+            raise ValueError('DCCRN streaming needs time stride 1, time padding 0 and time output padding 0 '
+                             f'(got stride {st}, padding {pt}, output padding {opt})')
+        stft = model.stft
+        if stft.n_fft != stft.frame_length:
+            raise ValueError(f'DCCRN streaming needs n_fft == frame_length, got {stft.n_fft} and {stft.frame_length}')
+        if stft.frame_length % (2*stft.hop_length):
+            raise ValueError('DCCRN streaming needs frame_length to be a multiple of 2 hop (the centre padding '
+                             f'in whole hops), got {stft.frame_length} and hop {stft.hop_length}')
+        if not (stft.center and stft.pad_mode == 'constant' and stft.normalized and stft.onesided
+                and stft.compression_factor == 1 and stft.scale_factor == 1):
+            raise ValueError('DCCRN streaming needs the STFT settings DCCRN builds')
+        net = model.mask_net
+        for blk in list(net.encoder) + list(net.decoder):
+            if blk.norm is not None and (not getattr(blk.norm, 'track_running_stats', True)
+                                         or getattr(blk.norm, 'running_mean', None) is None):
+                raise ValueError('DCCRN streaming needs batch norms that track running statistics')
+        if model.flat_params() is None:
+            raise ValueError('DCCRN streaming reads the flat parameter buffer; this model keeps separate '
+                             'parameters (optimizer other than Adam)')
+        return model.latency - stft.hop_length
+
+    @staticmethod
+    def _geometry(model):
+        """``brv_dccrn_stream_config`` with the geometry only (offsets and buffer addresses unset)."""
+        from .models.dccrn import ComplexBatchNorm2d
+        net = model.mask_net
+        (kf, kt), (sf, st), (pf, pt), (opf, opt) = net.geom
+        cfg = hip.DccrnStreamConfig()
+        cfg.n_fft, cfg.hop, cfg.levels = model.stft.n_fft, model.stft.hop_length, len(net.encoder)
+        cfg.kf, cfg.kt, cfg.sf, cfg.pf, cfg.opf, cfg.st, cfg.pt, cfg.opt = kf, kt, sf, pf, opf, st, pt, opt
+        cfg.complex_bn = int(isinstance(net.encoder[0].norm, ComplexBatchNorm2d))
+        if len(net.encoder) > hip.DCCRN_STREAM_MAX_LEVELS:
+            cfg.levels = hip.DCCRN_STREAM_MAX_LEVELS + 1       # (refused by the library, with its message)
+        for i, blk in enumerate(list(net.encoder)[:hip.DCCRN_STREAM_MAX_LEVELS]):
+            cfg.channels[i] = blk.conv.module_real.out_channels
+        lstm = net.lstm.lstm.layers
+        cfg.lstm_hidden, cfg.lstm_layers = lstm[0].module_real.hidden_size, len(lstm)
+        return cfg
+
+    def _config(self):
+        """The full config of one call: geometry, flat offsets, eps and the running buffers' current addresses."""
+        model = self.model
+        net = model.mask_net
+        flat = model.flat_params()
+        key = (flat.data_ptr(), flat.numel())
+        if self._offsets is None or self._offsets[0] != key:
+            self._offsets = (key, {id(p): off for p, off in model.param_offsets()})
+        offs = self._offsets[1]
+        cfg = self._geometry(model)
+
+        def off(p):
+            return offs[id(p)] if p is not None else -1
+        blocks = list(net.encoder) + list(net.decoder)
+        for b, blk in enumerate(blocks):
+            mr, mi = blk.conv.module_real, blk.conv.module_imag
+            norm, act = blk.norm, blk.activation
+            cfg.off_block[b][:] = [off(mr.weight), off(mr.bias), off(mi.weight), off(mi.bias),
+                                   off(norm.weight) if norm is not None else -1,
+                                   off(norm.bias) if norm is not None else -1,
+                                   off(act.weight) if act is not None else -1]
+            if norm is not None:
+                hip.require_device(norm.running_mean, norm.running_var)
+                cfg.eps[b] = float(norm.eps)
+                cfg.run_mean[b] = norm.running_mean.data_ptr()
+                cfg.run_var[b] = norm.running_var.data_ptr()
+        for li, layer in enumerate(net.lstm.lstm.layers):
+            for m, mod in enumerate((layer.module_real, layer.module_imag)):
+                cfg.off_lstm[li][m][:] = [off(mod.weight_ih_l0), off(mod.weight_hh_l0), off(mod.bias_ih_l0),
+                                          off(mod.bias_hh_l0)]
+        lr, li_ = net.lstm.linear_r, net.lstm.linear_i
+        cfg.off_linear[:] = [off(lr.weight), off(lr.bias), off(li_.weight), off(li_.bias)]
+        for b, blk in enumerate(blocks):
+            norm = blk.norm
+            if norm is not None and (not norm.running_mean.is_contiguous() or not norm.running_var.is_contiguous()
+                                     or norm.running_mean.dtype != torch.float32):
+                raise RuntimeError('the running buffers must be contiguous fp32 tensors')
+        return cfg
+
+    def _reset(self, ids):
+        t = self._ids_tensor(ids)
+        cfg = self._geometry(self.model)
+        hip.check(hip.lib().brv_dccrn_stream_reset(ctypes.byref(cfg), hip.ptr(self._state), hip.ptr(t), len(ids),
+                                                   hip.stream()), 'brv_dccrn_stream_reset')
+        for i in ids:
+            self._hops[i] = 0
+            self._ended[i] = False
+
+    def _call(self, ids, n, hops):
+        """What every launch of a call needs: params, tables, config, workspace."""
+        model = self.model
+        flat = model.flat_params()
+        hip.require_device(flat)
+        if flat.device != self.device:
+            raise RuntimeError(f'the model moved to {flat.device}; the streams live on {self.device}')
+        cfg = self._config()
+        lib = hip.lib()
+        nbytes = lib.brv_dccrn_stream_workspace_bytes(ctypes.byref(cfg), n, hops, int(self.use_amp))
+        if nbytes < 0:
+            hip.check(int(nbytes), 'brv_dccrn_stream_workspace_bytes')
+        if self._ws is None or self._ws.numel() < nbytes:
+            self._ws = None
+            self._ws = torch.empty(int(nbytes), dtype=torch.uint8, device=self.device)
+        tb = model.stft._tables(self.device)
+        return cfg, flat, tb
+
+    # ---- compute --------------------------------------------------------------------------------
+    def process(self, x, ids):
+        """Advance the streams ``ids`` by the chunk ``x`` (``(n, k hop)`` or ``(n, channels, k hop)``):
+        returns ``(n, k hop)``, ``lag`` samples behind the input."""
+        ids = self._check_ids(ids)
+        n = len(ids)
+        x = self._mono(x, n)
+        L = x.shape[1]
+        if L == 0 or L % self.hop:
+            raise ValueError(f'a chunk must be a positive multiple of hop = {self.hop} samples, got {L}')
+        for i in ids:
+            if self._ended[i]:
+                raise ValueError(f'stream {i} was flushed; reset or close it first')
+        hops = L//self.hop
+        cfg, flat, tb = self._call(ids, n, hops)
+        y = torch.empty(n, L, dtype=torch.float32, device=self.device)
+        t = self._ids_tensor(ids)
+        hip.check(hip.lib().brv_dccrn_stream_step(
+            ctypes.byref(cfg), hip.ptr(flat), hip.ptr(tb['window']), hip.ptr(tb['basis']), hip.ptr(tb['synthesis']),
+            hip.ptr(self._state), hip.ptr(t), n, hip.ptr(x), hops, hip.ptr(y), int(self.use_amp), hip.ptr(self._ws),
+            self._ws.numel(), None, hip.stream()), 'brv_dccrn_stream_step')
+        for i in ids:
+            self._hops[i] += hops
+        return y
+
+    def flush(self, ids, rest=None):
+        """End the streams ``ids``: ``rest`` is their last ``r < hop`` input samples (``(n, r)`` or
+        ``(n, channels, r)``, or None). Runs the frames of the zero-padded end and returns the ``(n, lag + r)``
+        output samples still owed. Reset or close the streams afterwards."""
+        ids = self._check_ids(ids)
+        n = len(ids)
+        r = 0
+        if rest is not None:
+            rest = self._mono(rest, n)
+            r = rest.shape[1]
+            if r >= self.hop:
+                raise ValueError(f'rest must be shorter than hop = {self.hop} samples, got {r}; '
+                                 'process the whole hops first')
+        stft = self.model.stft
+        (_, kt), _, _, _ = self.model.mask_net.geom
+        need = 1 + len(self.model.mask_net.encoder)*(kt - 1)     # STFT frames the offline model needs
+        for i in ids:
+            if self._ended[i]:
+                raise ValueError(f'stream {i} was flushed already; reset or close it first')
+            length = self._hops[i]*self.hop + r
+            frames = stft.frame_count(length) + stft.n_fft//self.hop
+            if frames < need:
+                raise ValueError(f'stream {i} has {length} samples: DCCRN needs at least {need} STFT frames '
+                                 f'({frames} here)')
+        hops = self.lag//self.hop + (1 if r else 0)
+        cfg, flat, tb = self._call(ids, n, hops)
+        y = torch.empty(n, self.lag + r, dtype=torch.float32, device=self.device)
+        t = self._ids_tensor(ids)
+        hip.check(hip.lib().brv_dccrn_stream_tail(
+            ctypes.byref(cfg), hip.ptr(flat), hip.ptr(tb['window']), hip.ptr(tb['basis']), hip.ptr(tb['synthesis']),
+            hip.ptr(self._state), hip.ptr(t), n, hip.ptr(rest) if r else None, r, hip.ptr(y), int(self.use_amp),
+            hip.ptr(self._ws), self._ws.numel(), None, hip.stream()), 'brv_dccrn_stream_tail')
+        for i in ids:
+            self._ended[i] = True
+        return y
+
+
 def enhance_streaming(model, x, chunk_samples, use_amp=False):
-    """``model.enhance(x, use_amp)`` computed chunk by chunk through a :class:`ConvTasNetStreamer`
-    (same shapes: ``(channels, L)`` -> ``(S, L)``, ``(B, channels, L)`` -> ``(B, S, L)``).
-    ``chunk_samples`` is rounded down to whole hops (at least one)."""
+    """``model.enhance(x, use_amp)`` computed chunk by chunk through a :class:`ConvTasNetStreamer` or, for a
+    DCCRN, a :class:`DCCRNStreamer` (same shapes as ``model.enhance``). ``chunk_samples`` is rounded down to
+    whole hops (at least one)."""
     if x.ndim == 2:
         return enhance_streaming(model, x.unsqueeze(0), chunk_samples, use_amp).squeeze(0)
     if x.ndim != 3:
         raise ValueError(f'input must be 2 or 3 dimensional, got {x.ndim}')
     B, L = x.shape[0], x.shape[-1]
-    s = ConvTasNetStreamer(model, max_streams=B, use_amp=use_amp)
+    from .models.dccrn import DCCRN
+    cls = DCCRNStreamer if isinstance(model, DCCRN) else ConvTasNetStreamer
+    s = cls(model, max_streams=B, use_amp=use_amp)
     hip.require_device(x)
     hop = s.hop
     chunk = max(1, int(chunk_samples)//hop)*hop
@@ -190,4 +411,4 @@ def enhance_streaming(model, x, chunk_samples, use_amp=False):
     outs = [s.process(mono[:, i:i + chunk], ids) if i + chunk <= whole else
             s.process(mono[:, i:whole], ids) for i in range(0, whole, chunk)]
     outs.append(s.flush(ids, mono[:, whole:] if L > whole else None))
-    return torch.cat(outs, dim=-1)[..., hop:]
+    return torch.cat(outs, dim=-1)[..., s.lag:]

@@ -188,6 +188,63 @@ int brv_ctn_stream_step(const brv_ctn_config* cfg, const float* params, void* st
 int brv_ctn_stream_tail(const brv_ctn_config* cfg, const void* state, const int32_t* ids, int64_t n,
                         float* y, brv_stream_t stream);
 
+/* ---- streaming inference of DCCRN (csrc/dccrn_stream.hip) -------------------------------------
+ * Geometry, flat-parameter offsets (in floats, into the `params` of the step) and the addresses of
+ * the batch-norm running buffers of a DCCRN in eval mode. Block b = 0 .. levels-1 is encoder level
+ * b + 1, block levels + k - 1 is decoder k (k = 1 the deepest; the last one has no norm and no PReLU:
+ * its norm / prelu offsets are -1). Per block: off_block = {conv real weight, real bias, imaginary
+ * weight, imaginary bias, norm weight, norm bias, PReLU slope}. off_lstm[layer][module][4] =
+ * {weight_ih, weight_hh, bias_ih, bias_hh} of module_real (0) / module_imag (1); off_linear =
+ * {linear_r weight, linear_r bias, linear_i weight, linear_i bias}. run_mean / run_var point at the
+ * running_mean / running_var buffers as they live in the model (nn.BatchNorm2d: (2C), (2C);
+ * complex_bn: (2, C), (2, 2, C)): the kernels read them at every step. The time axis must have
+ * stride 1, padding 0, output padding 0, n_fft == frame length, n_fft % (2 hop) == 0 (-2 otherwise).
+ * Limits (-2 beyond them): levels <= 8, channels <= 1024, lstm_hidden <= 512, lstm_layers <= 4,
+ * kf * kt <= 64, n_fft <= 4096. */
+#define BRV_DCCRN_STREAM_MAX_LEVELS 8
+typedef struct brv_dccrn_stream_config {
+  int32_t n_fft, hop, levels, kf, kt, sf, pf, opf;   /* kernel (freq, time), freq stride / padding / output padding */
+  int32_t st, pt, opt, complex_bn;                   /* time stride, padding, output padding (1, 0, 0); norm kind */
+  int32_t channels[BRV_DCCRN_STREAM_MAX_LEVELS];
+  int32_t lstm_hidden, lstm_layers;
+  float eps[2*BRV_DCCRN_STREAM_MAX_LEVELS];
+  int64_t off_block[2*BRV_DCCRN_STREAM_MAX_LEVELS][7];
+  int64_t off_lstm[4][2][4];
+  int64_t off_linear[4];
+  const float* run_mean[2*BRV_DCCRN_STREAM_MAX_LEVELS];
+  const float* run_var[2*BRV_DCCRN_STREAM_MAX_LEVELS];
+} brv_dccrn_stream_config;
+
+/* State of `slots` streams in one caller-owned buffer, brv_dccrn_stream_state_bytes each (slot i at
+ * byte i * state_bytes; layout in DESIGN.md 5e). One step advances the n streams listed in `ids`
+ * (distinct int32 slot ids on the device) by `hops` hops: x (n, hops*hop) fp32 new mono input ->
+ * y (n, hops*hop) fp32, lagging the input by n_fft - hop + levels (kt - 1) hop samples (zeros first).
+ * `window` is the analysis window (n_fft floats), `basis` / `synthesis` the fp64 DFT tables of the
+ * offline STFT ((2 bins, n_fft) each: rows 2k / 2k + 1 = real / imaginary part of bin k). amp = 0:
+ * fp32 products; amp = 1: bf16 operands, fp32 accumulation; transforms in fp64, the rest fp32. A
+ * stream's output does not depend on which other streams share the step. `opts` may be NULL. */
+int64_t brv_dccrn_stream_state_bytes(const brv_dccrn_stream_config* cfg);
+/* workspace of a step of n streams x hops hops; a tail needs the one of hops = lag/hop + 1 */
+int64_t brv_dccrn_stream_workspace_bytes(const brv_dccrn_stream_config* cfg, int64_t n, int64_t hops,
+                                         int32_t amp);
+/* put the listed slots back to the start of a stream */
+int brv_dccrn_stream_reset(const brv_dccrn_stream_config* cfg, void* state, const int32_t* ids, int64_t n,
+                           brv_stream_t stream);
+int brv_dccrn_stream_step(const brv_dccrn_stream_config* cfg, const float* params, const float* window,
+                          const double* basis, const double* synthesis, void* state, const int32_t* ids,
+                          int64_t n, const float* x, int64_t hops, float* y, int32_t amp, void* workspace,
+                          int64_t workspace_bytes, const brv_launch_opts* opts, brv_stream_t stream);
+/* End the listed streams: rest (n, r) fp32 holds their last r < hop input samples (NULL if r = 0).
+ * Runs the remaining frames of the zero-padded end (STFT.pad + centre padding) and the decoders'
+ * trailing frames, and writes the lag + r output samples still owed -> y (n, lag + r). Concatenated
+ * with every step's output and stripped of its first lag samples, that is DCCRN.forward (eval) of the
+ * whole signal. The caller checks the stream length first (>= 1 + levels (kt - 1) STFT frames); the
+ * slots must be reset before they are stepped again. */
+int brv_dccrn_stream_tail(const brv_dccrn_stream_config* cfg, const float* params, const float* window,
+                          const double* basis, const double* synthesis, void* state, const int32_t* ids,
+                          int64_t n, const float* rest, int64_t r, float* y, int32_t amp, void* workspace,
+                          int64_t workspace_bytes, const brv_launch_opts* opts, brv_stream_t stream);
+
 /* ---- criteria (brever/criterion.py) ---------------------------------------
  * x, y: (batch, sources, length) fp32 contiguous rows with `stride` floats
  * between rows; lengths: (batch,) int64 on the device; scratch: at least

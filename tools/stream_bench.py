@@ -1,9 +1,10 @@
-"""Step time of the streaming Conv-TasNet (brever_amd.streaming) on one GPU: one JSON line per
+"""Step time of the streaming Conv-TasNet or DCCRN (brever_amd.streaming) on one GPU: one JSON line per
 (precision, n streams, F hops per call) with the median and p90 of the synchronised step time, the
 real-time factor (step time / audio time of a chunk), the streams one GPU keeps in real time at that
 chunk size (n / real-time factor, rounded down) and the launches per step.
 
-    python tools/stream_bench.py [--n 1 16 64 256] [--hops 1 16] [--steps 50] [--warmup 10]
+    python tools/stream_bench.py [--model {convtasnet,dccrn}] [--n 1 16 64 256] [--hops 1 16] [--steps 50]
+                                 [--warmup 10]
 """
 import argparse
 import json
@@ -18,6 +19,7 @@ if ROOT not in sys.path:
 
 def main():
     p = argparse.ArgumentParser(description=__doc__.split('\n\n')[0])
+    p.add_argument('--model', choices=['convtasnet', 'dccrn'], default='convtasnet')
     p.add_argument('--n', type=int, nargs='+', default=[1, 16, 64, 256])
     p.add_argument('--hops', type=int, nargs='+', default=[1, 16])
     p.add_argument('--amp', type=int, nargs='+', default=[0, 1])
@@ -27,17 +29,24 @@ def main():
     args = p.parse_args()
 
     import torch
-    from brever_amd.models import ConvTasNet
-    from brever_amd.streaming import ConvTasNetStreamer
+    from brever_amd.models import DCCRN, ConvTasNet
+    from brever_amd.streaming import ConvTasNetStreamer, DCCRNStreamer
 
     torch.manual_seed(0)
-    model = ConvTasNet(causal=True).cuda()          # default widths: 512/32/128/512/128, 8 x 3 blocks
-    cfg = model.cfg
-    launches = 5 + 3*cfg.layers*cfg.repeats
-    hop = cfg.filter_length//2
+    if args.model == 'dccrn':
+        model = DCCRN().cuda()                      # default widths: 16 .. 128 channels, 6 levels, LSTM 2 x 128
+        Streamer = DCCRNStreamer
+        launches = 5 + 2*len(model.mask_net.encoder) + 2*len(model.mask_net.lstm.lstm.layers)
+        hop = model.stft.hop_length
+    else:
+        model = ConvTasNet(causal=True).cuda()      # default widths: 512/32/128/512/128, 8 x 3 blocks
+        Streamer = ConvTasNetStreamer
+        cfg = model.cfg
+        launches = 5 + 3*cfg.layers*cfg.repeats
+        hop = cfg.filter_length//2
     for amp in args.amp:
         for n in args.n:
-            s = ConvTasNetStreamer(model, max_streams=n, use_amp=bool(amp))
+            s = Streamer(model, max_streams=n, use_amp=bool(amp))
             ids = s.open(n)
             for F in args.hops:
                 s.reset(ids)
