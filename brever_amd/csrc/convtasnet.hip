@@ -16,14 +16,6 @@
 #include "gemm_wgrad.cuh"
 #include "gemm_ws.cuh"
 #include "dwpw2_fused.cuh"
-// Two kernel organisations that were built, measured slower and rejected are NOT part of the
-// default library (round 6): `tools/mkvariant.sh <tag> -DBRV_WITH_VARIANTS` builds a library that holds them, the
-// default one answers BRV_OPT_DWPW2_V2 / BRV_OPT_BWD_PERSIST with an error.
-#ifdef BRV_WITH_VARIANTS
-#include "dwpw2_fused_v2.cuh"
-#else
-constexpr int D2_TT = 64;            // (tile of the whole-row form; only its launch arithmetic needs the name)
-#endif
 #include "gemm_wgrad_full.cuh"
 #include "gemm_wgrad_full128.cuh"
 
@@ -31,9 +23,6 @@ constexpr int kWgSplit = 4;          // item splits of the [res | skip] weight-g
 #include "prep.cuh"
 #include "tcn_kernels.cuh"
 #include "bwd_fused.cuh"
-#ifdef BRV_WITH_VARIANTS
-#include "bwd_fused_p.cuh"
-#endif
 #include "pw1_bwd.cuh"
 #include "cln_kernels.cuh"
 
@@ -65,6 +54,13 @@ struct OptsScope {
     t_opts = (o && o->size >= sizeof(brv_launch_opts)) ? o : &kDefaultOpts;
   }
   ~OptsScope() { t_opts = prev; }
+  // a flags word with a bit this library does not know is an error, never silently the default kernels
+  int check() const {
+    const uint32_t unknown = t_opts->flags & ~BRV_OPT_KNOWN;
+    if (!unknown) return 0;
+    char bits[16]; snprintf(bits, sizeof(bits), "0x%x", unknown);
+    return fail(-1, std::string("unknown option bits ") + bits + " in brv_launch_opts.flags");
+  }
 };
 inline bool opt(uint32_t flag) { return (t_opts->flags & flag) != 0; }
 inline bool fwd_fuse_requested() { return !opt(BRV_OPT_NO_FWD_FUSE) && !opt(BRV_OPT_NO_WS); }
@@ -532,19 +528,6 @@ template <int P> struct DwBwdFused {
                    2.0*d.B*d.T*((double)p.Kg + 3.0*d.Cp), st);
     dim3 grid(ceil_div(tiles*d.B, 8)*8*(d.Cp/HL_CG));     // whole runs of 8 tiles (XCD map of the kernel)
     if (d.C != d.Cp) return fail(-1, "fused backward: channel count must be a multiple of 64");
-#ifndef BF_NT
-#define BF_NT 2
-#endif
-    const int nt = opt(BRV_OPT_BWD_PERSIST) ? BF_NT : 1;       // (opt-in: 83 against 73 us per launch)
-    if (nt > 1 && p.Kg == 256) {
-#ifdef BRV_WITH_VARIANTS
-      // persistent form (bwd_fused_p.cuh): a workgroup walks `nt` tiles of its channel group
-      dim3 gridp(ceil_div(ceil_div(tiles*d.B, 8), nt)*8*(d.Cp/HL_CG));
-      hipLaunchKernelGGL((dwconv_bwd_fused_p_kernel<P, 256>), gridp, dim3(256), BF_LDS, st, p, nt);
-#else
-      return fail(-1, "BRV_OPT_BWD_PERSIST: the persistent fused backward is not in this build (tools/mkvariant.sh <tag> -DBRV_WITH_VARIANTS)");
-#endif
-    } else
     if (p.Kg == 256) hipLaunchKernelGGL((dwconv_bwd_fused_kernel<P, 256>), grid, dim3(256), BF_LDS, st, p);
     else if (p.Kg == 128) hipLaunchKernelGGL((dwconv_bwd_fused_kernel<P, 128>), grid, dim3(256), BF_LDS, st, p);
     else return fail(-1, "fused backward: unexpected [res | skip] width");
@@ -1170,6 +1153,7 @@ int64_t brv_ctn_workspace_offset(const brv_ctn_config* cfg, int64_t batch, int64
 int brv_ctn_prepare(const brv_ctn_config* cfg, const float* params, void* prepared,
                     const brv_launch_opts* opts, brv_stream_t stream) {
   OptsScope scope(opts);
+  if (int r = scope.check()) return r;
   Layout l; if (int r = l.init(cfg)) return r;
   hipStream_t st = (hipStream_t)stream;
   std::vector<PrepJob> jobs;
@@ -1271,6 +1255,7 @@ int brv_ctn_forward(const brv_ctn_config* cfg, const float* params, const void* 
                     void* workspace, const float* wave, int64_t wave_stride, float* out, int64_t batch,
                     int64_t length, const brv_launch_opts* opts, brv_stream_t stream) {
   OptsScope scope(opts);
+  if (int r = scope.check()) return r;
   if (wave_stride != 0 && wave_stride < length) return fail(-1, "wave_stride shorter than the rows");
   Layout l; if (int r = l.init(cfg)) return r;
   hipStream_t st = (hipStream_t)stream;
@@ -1378,29 +1363,12 @@ int brv_ctn_forward(const brv_ctn_config* cfg, const float* params, const void* 
           dp.taps = params + b.dconv_w; dp.dbias = params + b.dconv_b;
           dp.B = B; dp.T = (int)T; dp.dil = dil; dp.left = ((l.P - 1)*dil)/2; dp.C = l.H;
           dp.inv_n = 1.0/((double)T*l.H); dp.eps = 1e-8f;
-          const bool v2 = opt(BRV_OPT_DWPW2_V2);
-          const int n_tiles = B*(int)((T + (v2 ? D2_TT : DP_TT) - 1)/(v2 ? D2_TT : DP_TT));
+          const int n_tiles = B*(int)((T + DP_TT - 1)/DP_TT);
           // (a multiple of 8 workgroups: the kernel deals the tiles to the 8 XCDs in equal runs of slots)
           const int cap = num_cus() >= 8 ? num_cus()/8*8 : 8;
           // (one workgroup per tile for the half-batch launches of the two-chain step -- 256 tiles on 256 instead of 224
           // workgroups, so that none walks two tiles -- measured no change: 6.49 ms either way, profiles/r05_dwpw2_ablation.txt)
-#ifndef D2V_SEQ
-#define D2V_SEQ 0
-#endif
-          const int cap2 = (v2 && D2V_SEQ) ? 2*cap : cap;
-          const int n_wg = n_tiles < cap2 ? (n_tiles + 7)/8*8 : cap2;
-#ifndef D2V_NW
-#define D2V_NW 4
-#endif
-#ifndef D2V_AHEAD
-#define D2V_AHEAD 8
-#endif
-#ifdef BRV_WITH_VARIANTS
-          if (v2) hipLaunchKernelGGL((dwpw2_v2_kernel<D2V_NW, D2V_AHEAD, (bool)D2V_SEQ>), dim3(n_wg), dim3(64*D2V_NW), 0, st, dp);
-          else
-#else
-          if (v2) return fail(-1, "BRV_OPT_DWPW2_V2: the whole-row fused forward is not in this build (tools/mkvariant.sh <tag> -DBRV_WITH_VARIANTS)");
-#endif
+          const int n_wg = n_tiles < cap ? (n_tiles + 7)/8*8 : cap;
           hipLaunchKernelGGL(dwpw2_fused_kernel, dim3(n_wg), dim3(512), 0, st, dp);
           HIP_OK(hipGetLastError());
         }
@@ -1672,6 +1640,7 @@ int brv_ctn_backward_part(const brv_ctn_config* cfg, const float* params, const 
                           int64_t batch, int64_t length, int32_t part, int32_t nparts,
                           const brv_launch_opts* opts, brv_stream_t stream) {
   OptsScope scope(opts);
+  if (int r = scope.check()) return r;
   Layout l; if (int r = l.init(cfg)) return r;
   hipStream_t st = (hipStream_t)stream;
   const int B = (int)batch; const long long L = length;

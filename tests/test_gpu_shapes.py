@@ -327,63 +327,46 @@ def test_sgmse_default_denoiser_full_spectrogram():
     assert err <= 5e-3, err
 
 
-def _variant_library():
-    """tools/_v/variants/libbrever_hip.so: the library with the two rejected kernel organisations compiled in
-    (`__graft_entry__.build()` makes it; built here when missing -- hipcc cross-compiles in ~30 s)."""
-    import os
-    import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    lib = os.path.join(root, 'tools', '_v', 'variants', 'libbrever_hip.so')
-    csrc = os.path.join(root, 'brever_amd', 'csrc')
-    newest = max(os.path.getmtime(os.path.join(csrc, f)) for f in os.listdir(csrc) if f.endswith(('.hip', '.cuh', '.h')))
-    newest = max(newest, os.path.getmtime(os.path.join(root, 'include', 'brever_hip.h')))
-    if not os.path.exists(lib) or os.path.getmtime(lib) < newest:      # (stale: built before the last source change)
-        subprocess.run(['bash', os.path.join(root, 'tools', 'mkvariant.sh'), 'variants', '-DBRV_WITH_VARIANTS'],
-                       check=True, capture_output=True, timeout=900)
-    return root, lib
-
-
-def _variant_check(switch, layers, repeats, B, L):
-    import json
-    import os
-    import subprocess
-    import sys
-    root, lib = _variant_library()
-    env = dict(os.environ, BRV_LIB_PATH=lib)
-    out = subprocess.run([sys.executable, os.path.join(root, 'tests', 'variant_check.py'), switch, str(layers), str(repeats),
-                          str(B), str(L)], env=env, cwd=root, capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-3000:]
-    return json.loads([ln for ln in out.stdout.splitlines() if ln.startswith('{')][-1])
-
-
-def test_default_library_refuses_the_rejected_kernel_variants(monkeypatch):
-    """Round 6: csrc/dwpw2_fused_v2.cuh and csrc/bwd_fused_p.cuh are compiled only with -DBRV_WITH_VARIANTS; the
-    default library must fail loudly (no silent fall-through to the default kernel) when their switches are set."""
+def test_retired_and_unknown_options_are_refused(monkeypatch):
+    """The switches of the two retired kernel variants and option bits the library does not know
+    (0x800 and 0x2000 were theirs, 0x4000 was never assigned) fail loudly -- no silent fall-through to the default
+    kernels -- and the refused call leaves nothing behind: the same model then runs forward and backward."""
+    from brever_amd import hip
     from brever_amd.criterion import snr
     from brever_amd.models import ConvTasNet
     gen = torch.Generator().manual_seed(3)
     batch, lengths = _ragged_batch(gen, 2, 4000)
+    net = ConvTasNet(layers=2, repeats=1).to(_cuda())
+    net._amp = True
+
+    def step():
+        net.zero_grad()
+        out = net(batch[:, 0].cuda())
+        snr(out, batch[:, 1:].cuda(), lengths.cuda()).mean().backward()
+        return out
+
+    def runs_clean():
+        out = step()
+        assert torch.isfinite(out).all()
+        assert all(torch.isfinite(p.grad).all() for p in net.parameters())
+
     for switch in ('BRV_DWPW2_V2', 'BRV_BWD_PERSIST'):
         monkeypatch.setenv(switch, '1')
-        net = ConvTasNet(layers=2, repeats=1).to(_cuda())
-        net._amp = True
-        with pytest.raises(RuntimeError, match='not in this build'):
-            out = net(batch[:, 0].cuda())
-            snr(out, batch[:, 1:].cuda(), lengths.cuda()).mean().backward()
+        with pytest.raises(RuntimeError, match='retired'):
+            net(batch[:, 0].cuda())
         monkeypatch.delenv(switch)
-
-
-@pytest.mark.parametrize('layers,repeats,B,L', [(8, 1, 2, 16000), (4, 2, 1, 700), (8, 1, 11, 10500)])
-def test_whole_row_fused_forward_variant_against_the_oracle(layers, repeats, B, L):
-    """The whole-row organisation of the fused forward stage (csrc/dwpw2_fused_v2.cuh; variant library only, DESIGN
-    5m: 64 against 50 us per launch) against the bf16-emulating ORACLE -- output, loss and every gradient of the
-    step that follows, with the bounds of the default kernels -- and against the slab form of the same library.
-    Items shorter than a tile / than the dilation, ragged lengths, tile counts that do not divide over the XCDs."""
-    r = _variant_check('BRV_DWPW2_V2', layers, repeats, B, L)
-    print(f'layers {layers} x {repeats}, B {B}, L {L}: whole-row forward', r)
-    assert r['finite']
-    assert r['out_vs_oracle'] <= 1e-2 and r['loss_vs_oracle'] <= 2e-3 and r['grad_vs_oracle'] <= 6e-2, r
-    assert r['out_vs_default'] <= 5e-3 and r['grad_vs_default'] <= 4e-2, r
+        runs_clean()
+    real = hip.launch_opts
+    for bit in (0x800, 0x2000, 0x4000):
+        def with_bit(*args, **kwargs):
+            opts = real(*args, **kwargs)
+            opts.flags |= bit
+            return opts
+        monkeypatch.setattr(hip, 'launch_opts', with_bit)
+        with pytest.raises(RuntimeError, match='unknown option'):
+            step()
+        monkeypatch.setattr(hip, 'launch_opts', real)
+        runs_clean()
 
 
 @pytest.mark.parametrize('layers,repeats,B,L', [(8, 1, 2, 16000), (8, 2, 3, 5000), (4, 2, 1, 700), (8, 1, 5, 2100),
@@ -419,20 +402,6 @@ def test_fused_backward_equals_three_launch_backward(monkeypatch, layers, repeat
             assert e <= 1.5e-2, e
             worst = _per_tensor(net, grads['1'], grads['0'], 5e-2, min_numel=128, min_norm=1e-5)
             print('   worst tensor', worst)
-
-
-@pytest.mark.parametrize('layers,repeats,B,L', [(8, 1, 2, 16000), (8, 1, 9, 2100), (8, 1, 2, 300)])
-def test_persistent_fused_backward_variant_against_the_oracle(layers, repeats, B, L):
-    """csrc/bwd_fused_p.cuh (variant library only, DESIGN 5n: 83 against 73 us per launch; a workgroup walks two
-    tiles, per-channel partial sums kept in LDS over the range, atomics once per workgroup) against the
-    bf16-emulating ORACLE with the default kernel's bounds, and against the one-tile-per-workgroup kernel of the same
-    library (same arithmetic per element, per-channel sums in another order). Odd tile counts, items shorter than
-    a tile, tile ranges that cross items."""
-    r = _variant_check('BRV_BWD_PERSIST', layers, repeats, B, L)
-    print(f'layers {layers} x {repeats}, B {B}, L {L}: persistent backward', r)
-    assert r['finite']
-    assert r['loss_vs_oracle'] <= 2e-3 and r['grad_vs_oracle'] <= 6e-2, r
-    assert r['grad_vs_default'] <= 2e-3, r
 
 
 @pytest.mark.parametrize('layers,repeats,B,L', [(8, 1, 2, 16000), (8, 2, 3, 5000), (4, 2, 1, 700), (8, 1, 5, 2100),

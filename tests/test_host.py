@@ -589,7 +589,7 @@ def test_launch_opts_come_from_the_environment_on_the_host(monkeypatch):
     DESIGN 5c into `brv_launch_opts` flags at call time."""
     import ctypes
     for name in ('BRV_FWD_FUSE', 'BRV_BWD_FUSE', 'BRV_NO_WS', 'BRV_DWPW2_WS', 'BRV_NO_DZ_FUSE', 'BRV_NO_DZ1_FUSE',
-                 'BRV_NO_WGRAD_FULL', 'BRV_NO_WGRAD_SPLIT', 'BRV_WG_TARGET', 'BRV_PW1_RC', 'BRV_DWPW2_V2', 'BRV_WGRAD_128', 'BRV_BWD_PERSIST'):
+                 'BRV_NO_WGRAD_FULL', 'BRV_NO_WGRAD_SPLIT', 'BRV_WG_TARGET', 'BRV_PW1_RC', 'BRV_WGRAD_128'):
         monkeypatch.delenv(name, raising=False)
     o = hip.launch_opts()
     assert o.size == ctypes.sizeof(hip.LaunchOpts) == 24 and o.flags == 0 and o.cu_eighths == 8
@@ -602,15 +602,21 @@ def test_launch_opts_come_from_the_environment_on_the_host(monkeypatch):
     monkeypatch.setenv('BRV_FWD_FUSE', '1')                  # '1' = default: only '0' switches the fusion off
     monkeypatch.setenv('BRV_BWD_FUSE', '0')
     assert hip.launch_opts().flags == hip.OPT_NO_BWD_FUSE | hip.OPT_NO_DZ1_FUSE
-    # round 5: the 128-wide [res | skip] weight gradient is the default ('0' selects the 64-wide kernel), the whole-row
-    # fused forward is opt-in
+    # round 5: the 128-wide [res | skip] weight gradient is the default ('0' selects the 64-wide kernel), the
+    # one-tile-per-workgroup recompute is opt-in
     monkeypatch.setenv('BRV_WGRAD_128', '1')
-    monkeypatch.setenv('BRV_DWPW2_V2', '0')
+    monkeypatch.setenv('BRV_PW1_RC_TILES', '0')
     assert hip.launch_opts().flags == hip.OPT_NO_BWD_FUSE | hip.OPT_NO_DZ1_FUSE
     monkeypatch.setenv('BRV_WGRAD_128', '0')
-    monkeypatch.setenv('BRV_DWPW2_V2', '1')
-    assert hip.launch_opts().flags == hip.OPT_NO_BWD_FUSE | hip.OPT_NO_DZ1_FUSE | hip.OPT_NO_WGRAD_128 | hip.OPT_DWPW2_V2
-    assert (hip.OPT_NO_WGRAD_128, hip.OPT_DWPW2_V2) == (0x1000, 0x800)
+    monkeypatch.setenv('BRV_PW1_RC_TILES', '1')
+    assert hip.launch_opts().flags == hip.OPT_NO_BWD_FUSE | hip.OPT_NO_DZ1_FUSE | hip.OPT_NO_WGRAD_128 | hip.OPT_PW1_RC_TILES
+    assert (hip.OPT_NO_WGRAD_128, hip.OPT_PW1_RC_TILES) == (0x1000, 0x400)
+    # the switches of the two retired kernel variants are refused, not ignored
+    for name in ('BRV_DWPW2_V2', 'BRV_BWD_PERSIST'):
+        monkeypatch.setenv(name, '1')
+        with pytest.raises(RuntimeError, match='retired'):
+            hip.launch_opts()
+        monkeypatch.delenv(name)
     # the shared library itself has no getenv among its undefined symbols' users on the product path:
     # (checked at the source level -- diagnostic builds only, behind BRV_DIAG)
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
