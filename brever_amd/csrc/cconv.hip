@@ -25,6 +25,7 @@
 #include <type_traits>
 
 #include "common.cuh"
+#include "status.h"
 #include "../../include/brever_hip.h"
 
 namespace {
@@ -899,10 +900,13 @@ template <typename TI>
 static int cconv_rows_any(const void* in, const void* in2, int64_t in_seg, const void* wp, const float* bias, void* out,
                           void* out2, int64_t out_seg, int64_t B, int64_t C, int64_t M, int64_t Hin, int64_t Win,
                           int32_t transposed, brv_stream_t stream, int out_bf16 = 0) {
-  if (!in || !wp || !out || B < 1 || C < 1 || M < 1 || Hin < 1 || Win < 1) return -1;
-  if (!transposed && ((Hin & 1) || Win < 2)) return -1;
-  if (in_seg < 0 || (in_seg > 0 && (!in2 || C != 4*in_seg || (in_seg & 7)))) return -1;
-  if (out_seg < 0 || (out_seg > 0 && (!out2 || M != 4*out_seg))) return -1;
+  BRV_REFUSE(!in || !wp || !out || B < 1 || C < 1 || M < 1 || Hin < 1 || Win < 1,
+             "requires in != NULL, wp != NULL, out != NULL, B >= 1, C >= 1, M >= 1, Hin >= 1, Win >= 1");
+  BRV_REFUSE(!transposed && ((Hin & 1) || Win < 2), "the convolution (not transposed) requires an even Hin and Win >= 2");
+  BRV_REFUSE(in_seg < 0 || (in_seg > 0 && (!in2 || C != 4*in_seg || (in_seg & 7))),
+             "requires in_seg >= 0, and with in_seg > 0: in2 != NULL, C == 4*in_seg, in_seg a multiple of 8");
+  BRV_REFUSE(out_seg < 0 || (out_seg > 0 && (!out2 || M != 4*out_seg)),
+             "requires out_seg >= 0, and with out_seg > 0: out2 != NULL, M == 4*out_seg");
   CConvParams p;
   p.in = in; p.in2 = in2; p.wp = (const uint4*)wp; p.bias = bias; p.out = out; p.out2 = out2; p.out_bf16 = out_bf16;
   p.in_seg = (int)in_seg; p.out_seg = (int)out_seg;
@@ -929,7 +933,8 @@ static int cconv_rows_any(const void* in, const void* in2, int64_t in_seg, const
   else if (M > 32) CC_LAUNCH(2, 1, 1, 8);
   else CC_LAUNCH(1, 1, 1, 8);
 #undef CC_LAUNCH
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+  BRV_HIP_OK(hipGetLastError());
+  return 0;
 }
 
 }  // namespace
@@ -942,21 +947,23 @@ int64_t brv_cconv_packed_bytes(int64_t M, int64_t C) {
 
 int brv_cconv_pack(const float* wc, void* wp, int64_t M, int64_t C, int64_t m_stride, int64_t c_stride,
                    brv_stream_t stream) {
-  if (!wc || !wp || M < 1 || C < 1) return -1;
+  BRV_REFUSE(!wc || !wp || M < 1 || C < 1, "requires wc != NULL, wp != NULL, M >= 1, C >= 1");
   const int ncc = (int)((C + 7)/8);
   const long long total = ((M + 31)/32)*(long long)ncc*CC_KH*64;
   hipLaunchKernelGGL(cconv_pack_kernel, dim3((unsigned)((total + 255)/256)), dim3(256), 0, (hipStream_t)stream,
                      wc, (uint4*)wp, (int)M, (int)C, (long long)m_stride, (long long)c_stride, ncc, total);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+  BRV_HIP_OK(hipGetLastError());
+  return 0;
 }
 
 int brv_cconv_pack_complex(const float* wr, const float* wi, const float* br, const float* bi, int64_t R, int64_t C,
                            int64_t Cb, float sign, float* wc, float* bias, void* wp1, int64_t M1, int64_t C1,
                            int64_t m_stride1, int64_t c_stride1, void* wp2, int64_t M2, int64_t C2,
                            int64_t m_stride2, int64_t c_stride2, brv_stream_t stream) {
-  if (!wr || !wi || !br || !bi || !wc || !bias || !wp1 || R < 1 || C < 1 || Cb < 1 || M1 < 1 || C1 < 1) return -1;
-  if (wp2 && (M2 < 1 || C2 < 1)) return -1;
-  if (4*R*C >= (1LL << 31)) return -1;
+  BRV_REFUSE(!wr || !wi || !br || !bi || !wc || !bias || !wp1 || R < 1 || C < 1 || Cb < 1 || M1 < 1 || C1 < 1,
+             "requires wr != NULL, wi != NULL, br != NULL, bi != NULL, wc != NULL, bias != NULL, wp1 != NULL, R >= 1, C >= 1, Cb >= 1, M1 >= 1, C1 >= 1");
+  BRV_REFUSE(wp2 && (M2 < 1 || C2 < 1), "wp2 requires M2 >= 1, C2 >= 1");
+  BRV_REFUSE(4*R*C >= (1LL << 31), "requires 4*R*C < 2^31");
   CPackAllParams p; memset(&p, 0, sizeof(p));
   p.wr = wr; p.wi = wi; p.br = br; p.bi = bi; p.wc = wc; p.bias = bias;
   p.R = (int)R; p.C = (int)C; p.Cb = (int)Cb; p.s = sign;
@@ -966,17 +973,19 @@ int brv_cconv_pack_complex(const float* wr, const float* wi, const float* br, co
   for (int q = 0; q < 2; ++q) {
     if (!wps[q]) continue;
     // every index the job forms stays inside wc
-    if ((Ms[q] - 1)*sm[q] + (Cs[q] - 1)*sk[q] + 2*(CC_KH - 1) + 1 >= 4*R*C) return -1;
+    BRV_REFUSE((Ms[q] - 1)*sm[q] + (Cs[q] - 1)*sk[q] + 2*(CC_KH - 1) + 1 >= 4*R*C,
+               "a packed view reaches past the 4*R*C elements of wc");
     CPackJob& j = p.job[q];
     j.wp = (uint4*)wps[q]; j.M = (int)Ms[q]; j.C = (int)Cs[q]; j.ncc = (int)((Cs[q] + 7)/8);
     j.sm = (unsigned int)sm[q]; j.sk = (unsigned int)sk[q];
     const long long total = ((Ms[q] + 31)/32)*(long long)j.ncc*CC_KH*64;
-    if (total >= (1LL << 31)) return -1;
+    BRV_REFUSE(total >= (1LL << 31), "requires fewer than 2^31 packed weight elements");
     j.total = (unsigned int)total;
     if (total > most) most = total;
   }
   hipLaunchKernelGGL(cconv_pack_all_kernel, dim3((unsigned)((most + 255)/256)), dim3(256), 0, (hipStream_t)stream, p);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+  BRV_HIP_OK(hipGetLastError());
+  return 0;
 }
 
 int brv_cconv_rows(const float* in, const float* in2, int64_t in_seg, const void* wp, const float* bias, float* out,
@@ -1011,7 +1020,7 @@ static void cconv_wgrad_plan(int64_t B, int64_t A, int64_t C, int64_t Hs, int& a
 }
 
 int64_t brv_cconv_wgrad_workspace_bytes(int64_t B, int64_t A, int64_t C, int64_t Hs) {
-  if (B < 1 || A < 1 || C < 1 || Hs < 1) return -1;
+  BRV_REFUSE(B < 1 || A < 1 || C < 1 || Hs < 1, "requires B >= 1, A >= 1, C >= 1, Hs >= 1");
   int atiles, ctiles, nsplit, pairs_per;
   cconv_wgrad_plan(B, A, C, Hs, atiles, ctiles, nsplit, pairs_per);
   return (int64_t)nsplit*10*A*C*4;
@@ -1022,8 +1031,10 @@ int64_t brv_cconv_wgrad_workspace_bytes(int64_t B, int64_t A, int64_t C, int64_t
 template <typename T>
 static int cconv_wgrad_any(const void* small, const void* small2, const void* big, float* out, void* workspace,
                            int64_t B, int64_t A, int64_t C, int64_t Hs, int64_t Ws, int64_t seg, brv_stream_t stream) {
-  if (!small || !big || !out || !workspace || B < 1 || A < 1 || C < 1 || Hs < 1 || Ws < 1) return -1;
-  if (seg < 0 || (seg > 0 && (!small2 || A != 4*seg))) return -1;
+  BRV_REFUSE(!small || !big || !out || !workspace || B < 1 || A < 1 || C < 1 || Hs < 1 || Ws < 1,
+             "requires small != NULL, big != NULL, out != NULL, workspace != NULL, B >= 1, A >= 1, C >= 1, Hs >= 1, Ws >= 1");
+  BRV_REFUSE(seg < 0 || (seg > 0 && (!small2 || A != 4*seg)),
+             "requires seg >= 0, and with seg > 0: small2 != NULL, A == 4*seg");
   CWgradParams p;
   p.small = small; p.small2 = small2; p.big = big; p.part = (float*)workspace;
   p.B = (int)B; p.A = (int)A; p.C = (int)C; p.Hs = (int)Hs; p.Ws = (int)Ws; p.Hb = (int)(2*Hs); p.Wb = (int)(Ws + 1);
@@ -1043,7 +1054,8 @@ static int cconv_wgrad_any(const void* small, const void* small2, const void* bi
   const long long n = 10*A*C;
   hipLaunchKernelGGL(cconv_wgrad_reduce_kernel, dim3((unsigned)((n + 63)/64)), dim3(256), 0, st,
                      (const float*)workspace, out, (int)A, (int)C, nsplit);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+  BRV_HIP_OK(hipGetLastError());
+  return 0;
 }
 
 extern "C" {

@@ -181,3 +181,7 @@ __host__ __device__ inline int round_up(int x, int m) { return (x + m - 1)/m*m; 
 __host__ __device__ inline int ceil_div(int x, int m) { return (x + m - 1)/m; }
 
 }  // namespace brv
+
+// flat loop of a 256-thread workgroup grid over n elements (the grid: flat_grid in status.h)
+#define GRID_STRIDE(i, n) \
+  for (long long i = (long long)blockIdx.x*256 + threadIdx.x; i < (n); i += (long long)gridDim.x*256)

@@ -24,12 +24,12 @@
 
 #include "../../include/brever_hip.h"
 #include "common.cuh"
+#include "status.h"
 
 using namespace brv;
 
 namespace {
 
-#define CM_OK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return (int)e_; } while (0)
 
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef float f32x8 __attribute__((ext_vector_type(8)));
@@ -326,20 +326,20 @@ __global__ __launch_bounds__(256) void conv_pack_kernel(const float* w, _Float16
 extern "C" {
 
 int64_t brv_conv2d_packed_size(int64_t Cout, int64_t Cin, int64_t ksize) {
-  if (Cout < 1 || Cin < 1 || (ksize != 1 && ksize != 3)) return -1;
+  BRV_REFUSE(Cout < 1 || Cin < 1 || (ksize != 1 && ksize != 3), "requires Cout >= 1, Cin >= 1, ksize 1 or 3");
   return ((Cout + 63)/64)*64*((Cin + CM_CK - 1)/CM_CK)*CM_CK*ksize*ksize;
 }
 
 int brv_conv2d_pack_f16(const float* w, void* wp, int64_t Cout, int64_t Cin, int64_t ksize,
                         brv_stream_t stream) {
   const int64_t total = brv_conv2d_packed_size(Cout, Cin, ksize);
-  if (total < 0) return -1;
+  BRV_REFUSE(total < 0, "the packed size overflows");
   long long g = (total + 255)/256;
   if (g > 4096) g = 4096;
   hipLaunchKernelGGL(conv_pack_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, w,
                      (_Float16*)wp, (int)Cout, (int)Cin, (int)(ksize*ksize),
                      (int)((Cin + CM_CK - 1)/CM_CK), (long long)total);
-  CM_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 
@@ -348,10 +348,13 @@ int brv_conv2d_mfma_forward(const float* x, const void* wp, const float* bias, c
                             int64_t B, int64_t Cin, int64_t H, int64_t W, int64_t Cout,
                             int64_t ksize, int64_t x_batch_stride, int64_t y_batch_stride,
                             float out_scale, brv_stream_t stream) {
-  if (B < 1 || Cin < 1 || Cout < 1 || H < 1 || W < 1 || (ksize != 1 && ksize != 3)) return -1;
+  BRV_REFUSE(B < 1 || Cin < 1 || Cout < 1 || H < 1 || W < 1 || (ksize != 1 && ksize != 3),
+             "requires B >= 1, Cin >= 1, Cout >= 1, H >= 1, W >= 1, ksize 1 or 3");
   const int64_t n_chunks = (Cin + CM_CK - 1)/CM_CK;
-  if ((n_chunks*CM_CK + 1)*H*W*4 >= (1LL << 32)) return -2;      // 32-bit buffer offsets
-  if (in_scale != nullptr && n_chunks*CM_CK > CM_MAX_FOLD) return -3;
+  // 32-bit buffer offsets
+  BRV_UNSUPPORTED((n_chunks*CM_CK + 1)*H*W*4 >= (1LL << 32),
+                  "the input planes exceed the 32-bit buffer offsets");
+  if (in_scale != nullptr && n_chunks*CM_CK > CM_MAX_FOLD) return fail(-3, "in_scale: more input channels than the fold table holds");
   ConvMfmaParams p;
   p.x = x; p.wp = (const h8*)wp; p.bias = bias; p.res = res; p.y = y;
   p.in_scale = in_scale; p.in_shift = in_shift; p.in_silu = in_silu;
@@ -382,7 +385,7 @@ int brv_conv2d_mfma_forward(const float* x, const void* wp, const float* bias, c
     hipLaunchKernelGGL(conv_mfma_kernel<3>, grid, dim3(256), 0, (hipStream_t)stream, p);
   else
     hipLaunchKernelGGL(conv_mfma_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, p);
-  CM_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 

@@ -37,12 +37,12 @@
 
 #include "../../include/brever_hip.h"
 #include "common.cuh"
+#include "status.h"
 
 using namespace brv;
 
 namespace {
 
-#define CN_OK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return (int)e_; } while (0)
 
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef _Float16 h4 __attribute__((ext_vector_type(4)));
@@ -785,20 +785,20 @@ unsigned long long* brv_conv_nhwc_dbg = nullptr;
 extern "C" {
 
 int64_t brv_conv_nhwc_packed_size(int64_t Cout, int64_t Cin, int64_t ksize) {
-  if (Cout < 1 || Cin < 1 || ksize != 3) return -1;
+  BRV_REFUSE(Cout < 1 || Cin < 1 || ksize != 3, "requires Cout >= 1, Cin >= 1, ksize == 3");
   return ((Cout + 127)/128)*128*((Cin + CN_CK - 1)/CN_CK)*CN_CK*ksize*ksize;
 }
 
 int brv_conv_nhwc_pack(const float* w, void* wp, int64_t Cout, int64_t Cin, int64_t ksize,
                        brv_stream_t stream) {
   const int64_t total = brv_conv_nhwc_packed_size(Cout, Cin, ksize);
-  if (total < 0) return -1;
+  BRV_REFUSE(total < 0, "the packed size overflows");
   long long g = (total + 255)/256;
   if (g > 4096) g = 4096;
   hipLaunchKernelGGL(conv_nhwc_pack_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, w,
                      (_Float16*)wp, (int)Cout, (int)Cin, (int)(ksize*ksize),
                      (int)((Cin + CN_CK - 1)/CN_CK), (long long)total);
-  CN_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 
@@ -820,16 +820,19 @@ int conv_nhwc_launch(const void* x1, int64_t C1, int64_t C1s, const void* x2, in
                      void* y, int64_t Cys, int64_t B, int64_t H, int64_t W, int64_t Cout, int64_t ksize,
                      float out_scale, double* stats, brv_stream_t stream,
                      float* split_ws = nullptr, long long split_floats = 0) {
-  if (B < 1 || H < 1 || W < 1 || C1 < 1 || Cout < 1 || ksize != 3) return -1;
-  if ((C1s & 7) || C1 > C1s || (Cys & 7) || (res && (Crs & 7)) || (Cout & 3)) return -2;
-  if (x2 && ((C2s & 7) || C2 > C2s || C2 < 1 || (C1 % CN_CK) != 0)) return -2;
+  BRV_REFUSE(B < 1 || H < 1 || W < 1 || C1 < 1 || Cout < 1 || ksize != 3,
+             "requires B >= 1, H >= 1, W >= 1, C1 >= 1, Cout >= 1, ksize == 3");
+  BRV_UNSUPPORTED((C1s & 7) || C1 > C1s || (Cys & 7) || (res && (Crs & 7)) || (Cout & 3),
+                  "requires C1s a multiple of 8, C1 <= C1s, Cys a multiple of 8, Crs a multiple of 8, Cout a multiple of 4");
+  BRV_UNSUPPORTED(x2 && ((C2s & 7) || C2 > C2s || C2 < 1 || (C1 % CN_CK) != 0),
+                  "x2 requires C2s a multiple of 8, 1 <= C2 <= C2s and C1 a multiple of the channel chunk");
   const int64_t Cin = C1 + (x2 ? C2 : 0);
-  if ((in_scale || gn) && (Cin % CN_CK) != 0) return -3;
-  if (gn && (gn->groups < 1 || Cin % gn->groups || !gn->fold_ws)) return -3;
+  if ((in_scale || gn) && (Cin % CN_CK) != 0) return fail(-3, "a folded input scale / group norm requires Cin a multiple of the channel chunk");
+  if (gn && (gn->groups < 1 || Cin % gn->groups || !gn->fold_ws)) return fail(-3, "gn requires groups >= 1, Cin a multiple of groups, fold_ws != NULL");
   static const unsigned char* zeros = nullptr;
   if (!zeros) {
     void* z = nullptr;
-    CN_OK(hipGetSymbolAddress(&z, HIP_SYMBOL(cn_zero_block)));
+    BRV_HIP_OK(hipGetSymbolAddress(&z, HIP_SYMBOL(cn_zero_block)));
     zeros = (const unsigned char*)z;
   }
   ConvNhwcParams p;
@@ -866,7 +869,7 @@ int conv_nhwc_launch(const void* x1, int64_t C1, int64_t C1s, const void* x2, in
       if (gn) hipLaunchKernelGGL((conv_nhwc_splitk_kernel<2>), sgrid, dim3(CN_THREADS), 0, sst, sp);
       else if (in_scale) hipLaunchKernelGGL((conv_nhwc_splitk_kernel<1>), sgrid, dim3(CN_THREADS), 0, sst, sp);
       else hipLaunchKernelGGL((conv_nhwc_splitk_kernel<0>), sgrid, dim3(CN_THREADS), 0, sst, sp);
-      CN_OK(hipGetLastError());
+      BRV_HIP_OK(hipGetLastError());
       ConvCombineParams cp;
       memset(&cp, 0, sizeof(cp));
       cp.part = split_ws; cp.n_split = n_split; cp.cq_n = p.n_cob*32; cp.npix = (long long)B*H*W; cp.hw = (long long)H*W;
@@ -874,7 +877,7 @@ int conv_nhwc_launch(const void* x1, int64_t C1, int64_t C1s, const void* x2, in
       cp.Cout = (int)Cout; cp.Crs = (int)Crs; cp.Cys = (int)Cys; cp.out_scale = out_scale;
       const dim3 cgrid((unsigned)((H*W + 255)/256), (unsigned)(B*cp.cq_n));
       hipLaunchKernelGGL(conv_nhwc_combine_kernel, cgrid, dim3(256), 0, sst, cp);
-      CN_OK(hipGetLastError());
+      BRV_HIP_OK(hipGetLastError());
       return 0;
     }
   }
@@ -895,7 +898,7 @@ int conv_nhwc_launch(const void* x1, int64_t C1, int64_t C1s, const void* x2, in
   if (force_pf == 1 || force_pf == 2 || force_pf == 4) pf = force_pf;
   p.n_ht = (int)((H + 4*pf - 1)/(4*pf));
   const long long n_tiles = (long long)B*p.n_ht*p.n_wt*p.n_cob;
-  if (n_tiles > 0x7fffffffLL) return -2;
+  BRV_UNSUPPORTED(n_tiles > 0x7fffffffLL, "requires fewer than 2^31 output tiles");
   p.n_tiles = (int)n_tiles;
   p.out_scale = out_scale; p.in_silu = in_silu;
 #ifndef BRV_CONV_STAGGER
@@ -904,7 +907,7 @@ int conv_nhwc_launch(const void* x1, int64_t C1, int64_t C1s, const void* x2, in
   p.stagger = BRV_CONV_STAGGER;
 #ifdef CN_DIAG
   static unsigned long long* dbg = nullptr;
-  if (!dbg) CN_OK(hipMalloc(&dbg, 4096));
+  if (!dbg) BRV_HIP_OK(hipMalloc(&dbg, 4096));
   p.dbg = dbg;
   brv_conv_nhwc_dbg = dbg;
 #endif
@@ -943,7 +946,7 @@ int conv_nhwc_launch(const void* x1, int64_t C1, int64_t C1s, const void* x2, in
   if (fold == 2) CN_LAUNCH_PF(2); else if (fold == 1) CN_LAUNCH_PF(1); else CN_LAUNCH_PF(0);
 #undef CN_LAUNCH_PF
 #undef CN_LAUNCH
-  CN_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 }  // namespace
@@ -986,7 +989,8 @@ int brv_conv_nhwc_forward_gn_ws(const void* x1, int64_t C1, int64_t C1s, const v
                                 float* fold_ws, int in_silu, void* y, int64_t Cys, int64_t B, int64_t H,
                                 int64_t W, int64_t Cout, int64_t ksize, float out_scale, double* stats,
                                 void* split_ws, int64_t split_ws_bytes, brv_stream_t stream) {
-  if (!sums1 || !gamma || !beta || (x2 && !sums2)) return -1;
+  BRV_REFUSE(!sums1 || !gamma || !beta || (x2 && !sums2),
+             "requires sums1 != NULL, gamma != NULL, beta != NULL, sums2 != NULL with x2");
   ConvNhwcNorm gn = {sums1, sums2, add_bc, gamma, beta, adm_scale, adm_shift, (int)groups, eps, fold_ws};
   return conv_nhwc_launch(x1, C1, C1s, x2, C2, C2s, wp, bias, res, Crs, nullptr, nullptr, &gn, in_silu,
                           y, Cys, B, H, W, Cout, ksize, out_scale, stats, stream,
@@ -1001,7 +1005,8 @@ int brv_conv_nhwc_forward_gn(const void* x1, int64_t C1, int64_t C1s, const void
                              float* fold_ws, int in_silu, void* y, int64_t Cys, int64_t B, int64_t H,
                              int64_t W, int64_t Cout, int64_t ksize, float out_scale, double* stats,
                              brv_stream_t stream) {
-  if (!sums1 || !gamma || !beta || (x2 && !sums2)) return -1;
+  BRV_REFUSE(!sums1 || !gamma || !beta || (x2 && !sums2),
+             "requires sums1 != NULL, gamma != NULL, beta != NULL, sums2 != NULL with x2");
   ConvNhwcNorm gn = {sums1, sums2, add_bc, gamma, beta, adm_scale, adm_shift, (int)groups, eps, fold_ws};
   return conv_nhwc_launch(x1, C1, C1s, x2, C2, C2s, wp, bias, res, Crs, nullptr, nullptr, &gn, in_silu,
                           y, Cys, B, H, W, Cout, ksize, out_scale, stats, stream);

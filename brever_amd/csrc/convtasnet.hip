@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/brever_hip.h"
+#include "status.h"
 #include "gemm_rows.cuh"
 #include "gemm_wgrad.cuh"
 #include "gemm_ws.cuh"
@@ -29,16 +30,6 @@ constexpr int kWgSplit = 4;          // item splits of the [res | skip] weight-g
 using namespace brv;
 
 namespace {
-
-thread_local std::string g_err;
-int fail(int code, const std::string& msg) { g_err = msg; return code; }
-
-#define HIP_OK(expr)                                                        \
-  do {                                                                      \
-    hipError_t e_ = (expr);                                                 \
-    if (e_ != hipSuccess)                                                   \
-      return fail((int)e_, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
 
 inline long long align_up(long long x, long long a) { return (x + a - 1)/a*a; }
 
@@ -262,7 +253,7 @@ int launch_gemm_rows_t(const GemmRowsParams& p0, int batch, hipStream_t st) {
   p.n_ttiles = ceil_div(p.T, GR_BM); p.n_ntiles = ceil_div(p.Np, BN); p.batch = batch;
   dim3 grid(p.n_ttiles*p.n_ntiles*batch);
   hipLaunchKernelGGL((gemm_rows_kernel<BN, AK, EM>), grid, dim3(256), 0, st, p);
-  HIP_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 
@@ -336,7 +327,8 @@ inline int launch_call_init(double* a, long long a_n, void* b, long long b_bytes
   int gx = (int)std::min<long long>(512, (units + 1023)/1024);
   if (gx < 1) gx = 1;
   hipLaunchKernelGGL(call_init_kernel, dim3(gx), dim3(256), 0, st, ip);
-  return (int)hipGetLastError();
+  BRV_HIP_OK(hipGetLastError());
+  return 0;
 }
 
 // Workgroups of a persistent launch: one per CU -- or opts.cu_eighths/8 of that while two kernel
@@ -388,7 +380,7 @@ int launch_gemm_ws(const GemmRowsParams& p0, int batch, hipStream_t st) {
 #ifdef BRV_DIAG
   if (p.dbg & 512) hipLaunchKernelGGL(diag_stamp_kernel, dim3(1), dim3(64), 0, st, debug_buffer() + 131000, 1);
 #endif
-  HIP_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 
@@ -441,7 +433,7 @@ int launch_wgrad_t(WgradGroupParams& gp, hipStream_t st, int target) {
   p.nsplit = ns;
   dim3 grid(tiles, ns, nprob);
   hipLaunchKernelGGL((gemm_wgrad_kernel<BH, HK>), grid, dim3(256), 0, st, gp);
-  HIP_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 // `gp.base` carries the shared dimensions / strides; `gp.prob[0..nprob)` the tensors
@@ -482,7 +474,7 @@ template <int P> struct DwFwd {
     ProfScope prof("dwconv_fwd", 2.0*P*p.B*p.T*(double)p.Cp, 4.0*p.B*p.T*(double)p.Cp, st);
     dim3 grid(ceil_div(p.T, DW_TT_F)*p.B);
     hipLaunchKernelGGL((dwconv_fwd_kernel<P>), grid, dim3(256), 0, st, p);
-    HIP_OK(hipGetLastError());
+    BRV_HIP_OK(hipGetLastError());
     return 0;
   }
 };
@@ -498,13 +490,13 @@ template <int P> struct DwBwd {
       dim3 grid(tiles*p.B*(p.Cp/HL_CG));
       const size_t lds = (size_t)hl_window_rows(p.dil, P)*HL_CG*2;
       hipLaunchKernelGGL((dwconv_bwd_halo_kernel<P>), grid, dim3(256), lds, st, p);
-      HIP_OK(hipGetLastError());
+      BRV_HIP_OK(hipGetLastError());
       return 0;
     }
     ProfScope prof("dwconv_bwd", 4.0*P*p.B*p.T*(double)p.Cp, 6.0*p.B*p.T*(double)p.Cp, st);
     dim3 grid(ceil_div(p.T, DW_TT_B)*p.B);
     hipLaunchKernelGGL((dwconv_bwd_kernel<P>), grid, dim3(256), 0, st, p);
-    HIP_OK(hipGetLastError());
+    BRV_HIP_OK(hipGetLastError());
     return 0;
   }
 };
@@ -531,7 +523,7 @@ template <int P> struct DwBwdFused {
     if (p.Kg == 256) hipLaunchKernelGGL((dwconv_bwd_fused_kernel<P, 256>), grid, dim3(256), BF_LDS, st, p);
     else if (p.Kg == 128) hipLaunchKernelGGL((dwconv_bwd_fused_kernel<P, 128>), grid, dim3(256), BF_LDS, st, p);
     else return fail(-1, "fused backward: unexpected [res | skip] width");
-    HIP_OK(hipGetLastError());
+    BRV_HIP_OK(hipGetLastError());
     return 0;
   }
 };
@@ -546,7 +538,7 @@ int launch_dz(const DzParams& p, hipStream_t st) {
   if (gx > cap) gx = cap;
   if (gx < 1) gx = 1;
   hipLaunchKernelGGL(dz_kernel, dim3(gx, p.B), dim3(256), 0, st, p);
-  HIP_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 
@@ -742,7 +734,7 @@ int reduce_vector_grads(const Layout& l, const Workspace& ws, const float* vg, f
     if (gx > 1024) gx = 1024;
     ProfScope prof("vgrad_reduce", 0, 4.0*total*(kReplicas + 2), st);
     hipLaunchKernelGGL(vgrad_reduce_kernel, dim3(gx), dim3(256), 0, st, vp);
-    HIP_OK(hipGetLastError());
+    BRV_HIP_OK(hipGetLastError());
   }
   return 0;
 }
@@ -781,8 +773,8 @@ int causal_ctx(const Layout& l, const Workspace& ws, char* base, int B, long lon
   const int n = (int)cmax > B ? (int)cmax : B;
   hipLaunchKernelGGL(fill_identity_kernel, dim3((n + 255)/256), dim3(256), 0, st, c.ones, c.zeros,
                      c.one, (int)cmax, c.fake, B, sumsq);
-  HIP_OK(hipGetLastError());
-  HIP_OK(hipMemsetAsync(c.scratch_stats, 0, (size_t)B*kStatStride*8, st));
+  BRV_HIP_OK(hipGetLastError());
+  BRV_HIP_OK(hipMemsetAsync(c.scratch_stats, 0, (size_t)B*kStatStride*8, st));
   return 0;
 }
 
@@ -798,7 +790,7 @@ int cln_forward(const CausalCtx& cx, const bf16_t* z, const float* slope, const 
   int gx = (int)(((long long)B*T*(Cp/8) + 255)/256);
   if (gx > 4096) gx = 4096;
   hipLaunchKernelGGL(cln_apply_kernel, dim3(gx), dim3(256), 0, st, p);
-  HIP_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 
@@ -818,7 +810,7 @@ int cln_backward(const CausalCtx& cx, const bf16_t* g, const bf16_t* z, const fl
   int gx = (int)(((long long)B*T*(Cp/8) + 255)/256);
   if (gx > 2048) gx = 2048;
   hipLaunchKernelGGL(cln_bwd_apply_kernel, dim3(gx), dim3(256), 0, st, p);
-  HIP_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 
@@ -840,7 +832,7 @@ int forward_causal(const Layout& l, const brv_ctn_config* cfg, const float* para
   bf16_t* m = (bf16_t*)(base + ws.m);
   bf16_t* y = (bf16_t*)(base + ws.y);
   CausalCtx cx; if (int r = causal_ctx(l, ws, base, B, T, st, cx)) return r;
-  HIP_OK(hipMemsetAsync(out, 0, (size_t)B*l.S*L*sizeof(float), st));
+  BRV_HIP_OK(hipMemsetAsync(out, 0, (size_t)B*l.S*L*sizeof(float), st));
 
   GemmRowsParams g;
   memset(&g, 0, sizeof(g));                                // encoder
@@ -939,7 +931,7 @@ int backward_causal(const Layout& l, const brv_ctn_config* cfg, const float* par
   float* vslope = vg + 2LL*l.N + vper*l.nb;
   float* vscratch = vslope + 1 + 2*l.nb;                   // 2*Hp floats per replica, discarded
   CausalCtx cx; if (int r = causal_ctx(l, ws, base, B, T, st, cx)) return r;
-  HIP_OK(hipMemsetAsync(vg, 0, ws.vg_bytes, st));
+  BRV_HIP_OK(hipMemsetAsync(vg, 0, ws.vg_bytes, st));
 
   GemmRowsParams g; WgradParams wg;
   memset(&g, 0, sizeof(g));                                // decoder data gradient + mask backward
@@ -1046,8 +1038,6 @@ int backward_causal(const Layout& l, const brv_ctn_config* cfg, const float* par
 
 extern "C" {
 
-int brv_version(void) { return 100; }
-
 #ifdef BRV_DIAG
 // Copies the cycle stamps of a BRV_DBG=64 run (tools/ablate.py) to the host.
 int brv_debug_read(long long* out, int64_t n) {
@@ -1100,9 +1090,6 @@ int64_t brv_prof_collect(void* prof, char* buf, int64_t buflen) {
   }
   return (int64_t)out.size() + 1;
 }
-const char* brv_last_error(void) { return g_err.c_str(); }
-// other translation units of the library report through the same thread-local message (not exported)
-__attribute__((visibility("hidden"))) void brv_internal_set_error(const char* msg) { g_err = msg ? msg : ""; }
 
 int64_t brv_ctn_param_count(const brv_ctn_config* cfg) {
   Layout l; if (l.init(cfg)) return -1; return l.n_params;
@@ -1112,7 +1099,7 @@ int64_t brv_ctn_param_tensors(const brv_ctn_config* cfg) {
 }
 int64_t brv_ctn_param_offset(const brv_ctn_config* cfg, int64_t index) {
   Layout l; if (l.init(cfg)) return -1;
-  if (index < 0 || index >= (int64_t)l.tensor_offsets.size()) return -1;
+  BRV_REFUSE(index < 0 || index >= (int64_t)l.tensor_offsets.size(), "index outside [0, brv_ctn_param_tensors)");
   return l.tensor_offsets[index];
 }
 int64_t brv_ctn_frames(const brv_ctn_config* cfg, int64_t length) {
@@ -1129,6 +1116,7 @@ int64_t brv_ctn_workspace_bytes(const brv_ctn_config* cfg, int64_t batch, int64_
 int64_t brv_ctn_workspace_offset(const brv_ctn_config* cfg, int64_t batch, int64_t length,
                                  const char* name, int64_t index) {
   Layout l; if (l.init(cfg)) return -1;
+  BRV_REFUSE(!name, "null name");
   Workspace ws; ws.init(l, batch, l.frames(length));
   const std::string n(name);
   if (n == "w") return ws.w;
@@ -1146,8 +1134,7 @@ int64_t brv_ctn_workspace_offset(const brv_ctn_config* cfg, int64_t batch, int64
   if (n == "dwt") return ws.dwt;
   if (n == "h1" && l.causal) return ws.h1 + ws.z_stride*index;
   if (n == "h2" && l.causal) return ws.h2 + ws.z_stride*index;
-  fail(-1, "unknown workspace tensor " + n);
-  return -1;
+  return fail(-1, "unknown workspace tensor " + n);
 }
 
 int brv_ctn_prepare(const brv_ctn_config* cfg, const float* params, void* prepared,
@@ -1208,7 +1195,7 @@ int brv_ctn_prepare(const brv_ctn_config* cfg, const float* params, void* prepar
     }
     hipLaunchKernelGGL(prep_weights_kernel, dim3(8, pb.n), dim3(256), 0, st, params,
                        (bf16_t*)prepared, pb);
-    HIP_OK(hipGetLastError());
+    BRV_HIP_OK(hipGetLastError());
   }
   // fragment-order copies for the persistent GEMMs (default widths only)
   std::vector<PackJob> packs;
@@ -1229,7 +1216,7 @@ int brv_ctn_prepare(const brv_ctn_config* cfg, const float* params, void* prepar
     pb.n = (int)std::min<size_t>(96, packs.size() - i);
     for (int k = 0; k < pb.n; ++k) pb.jobs[k] = packs[i + k];
     hipLaunchKernelGGL(pack_frag_kernel, dim3(16, pb.n), dim3(256), 0, st, (bf16_t*)prepared, pb);
-    HIP_OK(hipGetLastError());
+    BRV_HIP_OK(hipGetLastError());
   }
   if (fused) {
     LazyPrepParams lp; memset(&lp, 0, sizeof(lp));
@@ -1242,11 +1229,11 @@ int brv_ctn_prepare(const brv_ctn_config* cfg, const float* params, void* prepar
     lp.stamp = reinterpret_cast<int*>((bf16_t*)prepared + l.p_stamp); lp.stamp_value = mode_stamp(fused);
     hipLaunchKernelGGL(lazy_prep_kernel, dim3((l.Bnp + l.Scp + 3)/4, l.nb), dim3(256), 0, st, params,
                        (bf16_t*)prepared, lp);
-    HIP_OK(hipGetLastError());
+    BRV_HIP_OK(hipGetLastError());
   } else {
     hipLaunchKernelGGL(stamp_write_kernel, dim3(1), dim3(1), 0, st,
                        reinterpret_cast<int*>((bf16_t*)prepared + l.p_stamp), mode_stamp(fused));
-    HIP_OK(hipGetLastError());
+    BRV_HIP_OK(hipGetLastError());
   }
   return 0;
 }
@@ -1370,7 +1357,7 @@ int brv_ctn_forward(const brv_ctn_config* cfg, const float* params, const void* 
           // workgroups, so that none walks two tiles -- measured no change: 6.49 ms either way, profiles/r05_dwpw2_ablation.txt)
           const int n_wg = n_tiles < cap ? (n_tiles + 7)/8*8 : cap;
           hipLaunchKernelGGL(dwpw2_fused_kernel, dim3(n_wg), dim3(512), 0, st, dp);
-          HIP_OK(hipGetLastError());
+          BRV_HIP_OK(hipGetLastError());
         }
       }
     }
@@ -1384,7 +1371,7 @@ int brv_ctn_forward(const brv_ctn_config* cfg, const float* params, const void* 
       int gx = (int)((T*(l.Scp/8) + 255)/256);
       if (gx > 128) gx = 128;      // (64 / 32 / 16: 136 - 137 us as well, round 5: not the per-workgroup prologue)
       hipLaunchKernelGGL(skip_combine_kernel, dim3(gx, B), dim3(256), 0, st, sc);
-      HIP_OK(hipGetLastError());
+      BRV_HIP_OK(hipGetLastError());
     }
   } else
   for (int i = 0; i < l.nb; ++i) {
@@ -1535,7 +1522,7 @@ static int deferred_wgrads(const Layout& l, const Workspace& ws, char* base, con
     }
     if (fp.n_split > 1)
       hipLaunchKernelGGL(wgrad_full_reduce_kernel, dim3(128, (unsigned)nblk), dim3(256), 0, st, fp);
-    HIP_OK(hipGetLastError());
+    BRV_HIP_OK(hipGetLastError());
   }
   for (int i0 = blk_lo; i0 <= blk_hi; i0 += kWgMaxProb) {
     const int n = std::min(kWgMaxProb, blk_hi + 1 - i0);
@@ -1611,7 +1598,7 @@ static int deferred_wgrads(const Layout& l, const Workspace& ws, char* base, con
       rp.nsplit = ns;
       ProfScope prof("pw1_wgrad", 2.0*n*BT*(double)l.Hp*l.Bnp*2, 2.0*BT*(l.Hp + l.Bnp)*n, st);
       hipLaunchKernelGGL(pw1_wgrad_rc_kernel, dim3(tiles, ns, n), dim3(256), 0, st, rp);
-      HIP_OK(hipGetLastError());
+      BRV_HIP_OK(hipGetLastError());
     }
     // (The owner-computes kernel of the [res | skip] gradient was tried for this product too -- 256 of dz1's channels
     // as its DMA'd operand, x as the 128-wide one, two launches of 24 problems: 580 us against the 429 us of the
@@ -1729,7 +1716,7 @@ int brv_ctn_backward_part(const brv_ctn_config* cfg, const float* params, const 
     int gx = (int)((T*(l.Scp/8) + 255)/256);
     if (gx > 64) gx = 64;
     hipLaunchKernelGGL(gu_dots_kernel, dim3(gx, B), dim3(256), 0, st, gu);
-    HIP_OK(hipGetLastError());
+    BRV_HIP_OK(hipGetLastError());
   }
   // output conv weight / bias gradients, one source at a time
   for (int s = 0; s < l.S; ++s) {
@@ -1869,7 +1856,7 @@ int brv_ctn_backward_part(const brv_ctn_config* cfg, const float* params, const 
         if (l.H == RC_H) hipLaunchKernelGGL(pw1_dgrad_ws_kernel<true>, dim3(grid), dim3(512), 0, st, wp);
         else hipLaunchKernelGGL(pw1_dgrad_ws_kernel<false>, dim3(grid), dim3(512), 0, st, wp);
       }
-      HIP_OK(hipGetLastError());
+      BRV_HIP_OK(hipGetLastError());
       continue;
     }
     if (fuse_dz1) {
@@ -1916,7 +1903,7 @@ int brv_ctn_backward_part(const brv_ctn_config* cfg, const float* params, const 
     if (gx < 1) gx = 1;
     ProfScope prof("gln0_bwd", 0, 2.0*BT*l.Np*(3 + l.S), st);
     hipLaunchKernelGGL(gln0_bwd_combine_kernel, dim3(gx, B), dim3(256), 0, st, cb);
-    HIP_OK(hipGetLastError());
+    BRV_HIP_OK(hipGetLastError());
   }
   // encoder weight gradient: dw^T * frames(wave)
   memset(&wg, 0, sizeof(wg));

@@ -27,23 +27,13 @@
 
 #include "../../include/brever_hip.h"
 #include "common.cuh"
+#include "status.h"
 #include "gemm_f32_big.h"
 
 using namespace brv;
 
 namespace {
 
-}  // namespace
-extern "C" __attribute__((visibility("hidden"))) void brv_internal_set_error(const char* msg);   // convtasnet.hip: feeds brv_last_error()
-namespace {
-int fail32(int code, const std::string& msg) { brv_internal_set_error(msg.c_str()); return code; }
-
-#define HIP_OK32(expr)                                                          \
-  do {                                                                          \
-    hipError_t e_ = (expr);                                                     \
-    if (e_ != hipSuccess)                                                       \
-      return fail32((int)e_, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
 #define OK32(expr) do { if (int r_ = (expr)) return r_; } while (0)
 
 inline long long up(long long x, long long a) { return (x + a - 1)/a*a; }
@@ -58,12 +48,12 @@ struct Lay32 {
   long long enc_w, dec_w, ln_g, ln_b, bott_w, bott_b, tcn_prelu, out_w, out_b, n_params;
   std::vector<Blk32> blk;
   int init(const brv_ctn_config* c) {
-    if (!c) return fail32(-1, "null config");
+    if (!c) return fail(-1, "null config");
     if (c->filters < 1 || c->filter_length < 2 || c->bottleneck_channels < 1 ||
         c->hidden_channels < 1 || c->skip_channels < 1 || c->layers < 1 || c->repeats < 1 ||
         c->output_sources < 1 || c->kernel_size < 1)
-      return fail32(-1, "invalid Conv-TasNet hyper-parameters");
-    if (c->kernel_size > 7) return fail32(-2, "kernel_size must be <= 7 in the fp32 HIP path");
+      return fail(-1, "invalid Conv-TasNet hyper-parameters");
+    if (c->kernel_size > 7) return fail(-2, "kernel_size must be <= 7 in the fp32 HIP path");
     N = c->filters; K = c->filter_length; Bn = c->bottleneck_channels; H = c->hidden_channels;
     Sc = c->skip_channels; P = c->kernel_size; layers = c->layers; nb = c->layers*c->repeats;
     S = c->output_sources; hop = K/2; causal = c->causal != 0;
@@ -644,13 +634,13 @@ int gemm32(const Ctx32& c, const float* a, const float* b, float* d, long long b
     g.scratch = c.f(c.ws.gscratch); g.scratch_floats = c.ws.gscratch_floats;
     if (gemm_f32_big_ok(g)) {
       const int rb = gemm_f32_big(g, c.st);
-      if (rb) return fail32(rb, "fp32 Conv-TasNet path: gemm_f32_big failed");
+      if (rb) return fail(rb, "fp32 Conv-TasNet path: gemm_f32_big failed");
       return 0;
     }
   }
   const int r = brv_gemm_f32(a, b, d, batch, M, N, K, lda, ldb, ldd, abs_, bbs, dbs, ta, tb, kbatch,
                              akbs, bkbs, bias, acc, (brv_stream_t)c.st);
-  if (r) return fail32(r, "brv_gemm_f32 failed inside the fp32 Conv-TasNet path");
+  if (r) return fail(r, "brv_gemm_f32 failed inside the fp32 Conv-TasNet path");
   return 0;
 }
 // rows-major 1x1 convolution: d[rows][n] = a[rows][k] W[n][k]^T (+ col bias | accumulate)
@@ -676,7 +666,7 @@ int norm_forward(const Ctx32& c, const float* z, const float* slope, float* tabl
                      slope, fsum, rows, C);
   hipLaunchKernelGGL(f32_fwd_table_kernel, dim3((unsigned)c.B), dim3(256), 0, c.st, fsum, table,
                      (int)c.T, C, 1e-8f, c.l.causal);
-  HIP_OK32(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 int norm_apply(const Ctx32& c, const float* z, const float* slope, const float* table,
@@ -687,18 +677,18 @@ int norm_apply(const Ctx32& c, const float* z, const float* slope, const float* 
   else
   hipLaunchKernelGGL(f32_norm_apply_kernel, dim3(grid_for(c.BT*C)), dim3(256), 0, c.st, z, slope,
                      table, gain, bias, y, c.BT, C);
-  HIP_OK32(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 int chan_reduce(const Ctx32& c, Red32 r, float* d0, int stride0, int nq_main, float* d1) {
   const int slices = (int)((r.rows + kSliceRows - 1)/kSliceRows);
   const int nq = r.mode == 0 ? 1 : (r.mode == 1 ? 2 : r.P + 1);
   r.part = c.f(c.ws.part);
-  if ((long long)slices*nq*r.C > c.ws.part_floats) return fail32(-1, "fp32 path: reduction scratch too small");
+  if ((long long)slices*nq*r.C > c.ws.part_floats) return fail(-1, "fp32 path: reduction scratch too small");
   hipLaunchKernelGGL(f32_chan_reduce_kernel, dim3(slices, (r.C + 63)/64), dim3(256), 0, c.st, r);
   hipLaunchKernelGGL(f32_chan_fold_kernel, dim3((nq*r.C + 15)/16), dim3(256), 0, c.st, r.part,
                      slices, nq, r.C, d0, d1, stride0, nq_main);
-  HIP_OK32(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 int col_sum(const Ctx32& c, const float* src, int ld, int C, float* dst) {
@@ -733,7 +723,7 @@ int norm_backward(const Ctx32& c, const float* e, const float* z, const float* s
   hipLaunchKernelGGL(f32_norm_bwd_apply_kernel, dim3(g), dim3(256), 0, c.st, e, z, slope_p, table, btab,
                      gain, add, dz, dslope ? part : nullptr, rows, C);
   if (dslope) hipLaunchKernelGGL(f32_fold_scalar_kernel, dim3(1), dim3(256), 0, c.st, part, g, dslope);
-  HIP_OK32(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 
@@ -779,7 +769,7 @@ int big(const Ctx32& c, BigGemm g) {
   g.batch = 1; if (g.kbatch < 1) g.kbatch = 1;
   g.scratch = c.f(c.ws.gscratch); g.scratch_floats = c.ws.gscratch_floats;
   const int r = gemm_f32_big(g, c.st);
-  if (r) return fail32(r, "fp32 Conv-TasNet path: gemm_f32_big refused a product");
+  if (r) return fail(r, "fp32 Conv-TasNet path: gemm_f32_big refused a product");
   return 0;
 }
 // d[rows][n] = op(a)[rows][k] W[n][k]^T + bias[n] (+ add), op = identity or the norm transform `pro`
@@ -842,13 +832,13 @@ int fold(const Ctx32& c, int nq, int C, float* const* dst, const int* stride, lo
   j.part = c.f(c.ws.part); j.slices = (int)(slices < 0 ? fused_slices(c) : slices); j.nq = nq; j.C = C;
   for (int k = 0; k < nq; ++k) { j.dst[k] = dst[k]; j.stride[k] = stride[k]; }
   hipLaunchKernelGGL(f32_fold_kernel, dim3((nq*C + 15)/16), dim3(1024), 0, c.st, j);
-  HIP_OK32(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 int fwd_table(const Ctx32& c, float* table, int C) {
   hipLaunchKernelGGL(f32_fwd_table_kernel, dim3((unsigned)c.B), dim3(256), 0, c.st, c.f(c.ws.fsum), table,
                      (int)c.T, C, 1e-8f, c.l.causal);
-  HIP_OK32(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 // gradient through y = norm(prelu(z)) in two passes (+ tables); `presummed`: pass 1 (frame sums in
@@ -858,7 +848,7 @@ int norm_backward_f(const Ctx32& c, const float* e, const float* z, const float*
                     float* dslope, float* dchan, bool presummed) {
   const FusedCommon fc{c.BT, (int)c.T, C};
   const unsigned slices = fused_slices(c);
-  if ((long long)slices*2*C > c.ws.part_floats) return fail32(-1, "fp32 path: reduction scratch too small");
+  if ((long long)slices*2*C > c.ws.part_floats) return fail(-1, "fp32 path: reduction scratch too small");
   float* fsum = c.f(c.ws.fsum); float* btab = c.f(c.ws.btab);
   if (!presummed) {
     BwdSums q{fc, e, z, table, slope_p, gain, fsum, c.f(c.ws.part)};
@@ -873,7 +863,7 @@ int norm_backward_f(const Ctx32& c, const float* e, const float* z, const float*
   BRV_NJ_LAUNCH(f32_bwd_apply_fused_kernel, C, dim3(slices), c.st, a);
   if (dslope) hipLaunchKernelGGL(f32_fold_scalar_kernel, dim3(1), dim3(256), 0, c.st, c.f(c.ws.scalars), (int)slices, dslope);
   if (dchan) { float* dst[1] = {dchan}; const int stride[1] = {1}; OK32(fold(c, 1, C, dst, stride)); }
-  HIP_OK32(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 
@@ -892,7 +882,7 @@ int brv_ctn_f32_forward(const brv_ctn_config* cfg, const float* params, void* wo
                         brv_stream_t stream) {
   Lay32 l; OK32(l.init(cfg));
   const long long B = batch, L = length, T = l.frames(L);
-  if (B < 1 || T < 1) return fail32(-1, "empty batch or input shorter than one frame");
+  if (B < 1 || T < 1) return fail(-1, "empty batch or input shorter than one frame");
   Ws32 ws; ws.init(l, B, T, L);
   Ctx32 c{l, ws, (float*)workspace, params, nullptr, B, T, L, B*T, (hipStream_t)stream, fused_ok(l, workspace)};
   const long long BT = c.BT;
@@ -979,7 +969,7 @@ int brv_ctn_f32_forward(const brv_ctn_config* cfg, const float* params, void* wo
               nullptr, 0));
   hipLaunchKernelGGL(f32_ola_kernel, dim3(grid_for(B*l.S*L)), dim3(256), 0, st, fr, out, B*l.S,
                      (int)T, l.K, l.hop, L);
-  HIP_OK32(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 
@@ -997,8 +987,8 @@ int brv_ctn_f32_backward_part(const brv_ctn_config* cfg, const float* params, vo
                               int64_t length, int32_t part, int32_t nparts, brv_stream_t stream) {
   Lay32 l; OK32(l.init(cfg));
   const long long B = batch, L = length, T = l.frames(L);
-  if (B < 1 || T < 1) return fail32(-1, "empty batch or input shorter than one frame");
-  if (nparts < 1 || part < 0 || part >= nparts) return fail32(-1, "bad part");
+  if (B < 1 || T < 1) return fail(-1, "empty batch or input shorter than one frame");
+  if (nparts < 1 || part < 0 || part >= nparts) return fail(-1, "bad part");
   if (l.causal && nparts > 1) {
     if (part != nparts - 1) return 0;
     part = 0; nparts = 1;
@@ -1045,7 +1035,7 @@ int brv_ctn_f32_backward_part(const brv_ctn_config* cfg, const float* params, vo
   }
   // every block's skip convolution receives this same gradient (the skip outputs are summed,
   // convtasnet.py:199-203): its column sums = the gradient of every skip bias, taken once
-  HIP_OK32(hipMemsetAsync(c.f(ws.skipb), 0, (size_t)l.Sc*4, st));
+  BRV_HIP_OK(hipMemsetAsync(c.f(ws.skipb), 0, (size_t)l.Sc*4, st));
   OK32(col_sum(c, G + l.Bn, ldg, l.Sc, c.f(ws.skipb)));
   }   // head
   for (int i = blk_hi; i >= blk_lo; --i) {
@@ -1076,7 +1066,7 @@ int brv_ctn_f32_backward_part(const brv_ctn_config* cfg, const float* params, vo
       // pass 1 of the first norm's backward on that e
       {
         const long long dw_slices = slice_count(slice_map((int)T, dil), B, (int)T);
-        if (dw_slices*(l.P + 2)*l.H > ws.part_floats) return fail32(-1, "fp32 path: reduction scratch too small");
+        if (dw_slices*(l.P + 2)*l.H > ws.part_floats) return fail(-1, "fp32 path: reduction scratch too small");
         DwBwd d{{BT, (int)T, l.H}, dz, c.z1b(i), c.tab(1 + 2*i), params + b.prelu1, params + b.n1_g, params + b.n1_b,
                 params + b.dconv_w, e, c.f(ws.fsum), c.f(ws.part), l.P, dil, left};
         BRV_NJP_LAUNCH(f32_dw_bwd_fused_kernel, l.H, l.P, dim3((unsigned)dw_slices), st, d);
@@ -1147,7 +1137,7 @@ int brv_ctn_f32_backward_part(const brv_ctn_config* cfg, const float* params, vo
   OK32(gemm32(c, dz, c.f(ws.wavep), grads + l.enc_w, 1, l.N, l.K, T, l.N, l.hop, l.K, 0, 0, 0, 1, 0, B,
               T*l.N, ws.Lp, nullptr, 1));
   }   // tail
-  HIP_OK32(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   (void)wave; (void)wn;
   return 0;
 }

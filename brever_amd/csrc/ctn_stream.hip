@@ -29,21 +29,11 @@
 
 #include "../../include/brever_hip.h"
 #include "common.cuh"
+#include "status.h"
 
 using namespace brv;
 
-extern "C" __attribute__((visibility("hidden"))) void brv_internal_set_error(const char* msg);   // convtasnet.hip
-
 namespace {
-
-int failS(int code, const std::string& msg) { brv_internal_set_error(msg.c_str()); return code; }
-
-#define HIP_OKS(expr)                                                          \
-  do {                                                                         \
-    hipError_t e_ = (expr);                                                    \
-    if (e_ != hipSuccess)                                                      \
-      return failS((int)e_, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
 
 __host__ __device__ inline long long upS(long long x, long long a) { return (x + a - 1)/a*a; }
 
@@ -64,20 +54,20 @@ struct LayS {
   long long st_stats, st_carry, st_tail, st_ring, st_bytes;     // bytes
   BlkS blk[64];
   int init(const brv_ctn_config* c) {
-    if (!c) return failS(-1, "null config");
+    if (!c) return fail(-1, "null config");
     if (c->filters < 1 || c->filter_length < 2 || c->bottleneck_channels < 1 || c->hidden_channels < 1 ||
         c->skip_channels < 1 || c->layers < 1 || c->repeats < 1 || c->output_sources < 1 || c->kernel_size < 1)
-      return failS(-1, "invalid Conv-TasNet hyper-parameters");
-    if (!c->causal) return failS(-3, "streaming needs a causal Conv-TasNet (the global layer norm is not streamable)");
-    if (c->kernel_size > kMaxP) return failS(-2, "streaming: kernel_size must be <= 8");
-    if (c->layers*c->repeats > 64 || c->layers > 24) return failS(-2, "streaming: at most 64 blocks, 24 layers");
-    if (c->filter_length % 2) return failS(-2, "streaming: filter_length must be even (hop = filter_length/2)");
+      return fail(-1, "invalid Conv-TasNet hyper-parameters");
+    if (!c->causal) return fail(-3, "streaming needs a causal Conv-TasNet (the global layer norm is not streamable)");
+    if (c->kernel_size > kMaxP) return fail(-2, "streaming: kernel_size must be <= 8");
+    if (c->layers*c->repeats > 64 || c->layers > 24) return fail(-2, "streaming: at most 64 blocks, 24 layers");
+    if (c->filter_length % 2) return fail(-2, "streaming: filter_length must be even (hop = filter_length/2)");
     N = c->filters; K = c->filter_length; Bn = c->bottleneck_channels; H = c->hidden_channels;
     Sc = c->skip_channels; P = c->kernel_size; layers = c->layers; nb = c->layers*c->repeats;
     S = c->output_sources; hop = K/2; norms = 1 + 2*nb;
     const int widest = N > H ? N : H;
     if (upS(widest, 32) > kMaxKp || upS(Bn, 32) > kMaxKp || upS(Sc, 32) > kMaxKp || upS(K, 32) > kMaxKp)
-      return failS(-2, "streaming: channel counts must be <= 960");
+      return fail(-2, "streaming: channel counts must be <= 960");
     gmax = (widest + kTileM - 1)/kTileM;
     long long o = 0;
     auto take = [&](long long n) { long long r = o; o += n; return r; };
@@ -472,7 +462,7 @@ int launch_gemm(const Gemm& g, int amp, hipStream_t st) {
   const size_t lds = (size_t)kTileC*(Kp + 4)*sizeof(float);
   const unsigned ntiles = (unsigned)((g.cols + kTileC - 1)/kTileC);
   dim3 grid((g.M + kTileM - 1)/kTileM, ntiles + (MODE == RESSKIP ? g.ring_tiles : 0));
-  if ((long long)ntiles + g.ring_tiles > 65535) return failS(-2, "streaming: too many columns in one call");
+  if ((long long)ntiles + g.ring_tiles > 65535) return fail(-2, "streaming: too many columns in one call");
   if (amp) hipLaunchKernelGGL((stream_gemm_kernel<MODE, 1>), grid, dim3(256), lds, st, g);
   else hipLaunchKernelGGL((stream_gemm_kernel<MODE, 0>), grid, dim3(256), lds, st, g);
   return 0;
@@ -490,7 +480,7 @@ int64_t brv_ctn_stream_state_bytes(const brv_ctn_config* cfg) {
 int64_t brv_ctn_stream_workspace_bytes(const brv_ctn_config* cfg, int64_t n, int64_t hops, int32_t amp) {
   (void)amp;     // both precisions keep fp32 activations between the launches
   LayS l; if (int r = l.init(cfg)) return r;
-  if (n < 1 || hops < 1) return failS(-1, "streaming: n and hops must be >= 1");
+  if (n < 1 || hops < 1) return fail(-1, "streaming: n and hops must be >= 1");
   WsS ws; ws.init(l, n*hops);
   return ws.total*4;
 }
@@ -501,7 +491,7 @@ int brv_ctn_stream_reset(const brv_ctn_config* cfg, void* state, const int32_t* 
   if (n < 1) return 0;
   hipLaunchKernelGGL(stream_reset_kernel, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream,
                      (unsigned char*)state, l.st_bytes, ids, l.st_ring);
-  HIP_OKS(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 
@@ -511,7 +501,7 @@ int brv_ctn_stream_tail(const brv_ctn_config* cfg, const void* state, const int3
   if (n < 1) return 0;
   hipLaunchKernelGGL(stream_tail_kernel, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream,
                      (const unsigned char*)state, l.st_bytes, ids, l.st_tail, l.S*l.hop, y);
-  HIP_OKS(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 
@@ -520,10 +510,10 @@ int brv_ctn_stream_step(const brv_ctn_config* cfg, const float* params, void* st
                         int64_t workspace_bytes, const brv_launch_opts* opts, brv_stream_t stream) {
   (void)opts;    // no option of this entry point yet (size / flags reserved)
   LayS l; if (int r = l.init(cfg)) return r;
-  if (n < 1 || hops < 1) return failS(-1, "streaming: n and hops must be >= 1");
+  if (n < 1 || hops < 1) return fail(-1, "streaming: n and hops must be >= 1");
   const long long C = n*hops;
   WsS ws; ws.init(l, C);
-  if (workspace_bytes < ws.total*4) return failS(-1, "streaming: workspace too small");
+  if (workspace_bytes < ws.total*4) return fail(-1, "streaming: workspace too small");
   hipStream_t st = (hipStream_t)stream;
   float* W = (float*)workspace;
   // row groups of each norm's frame sums: input norm = encoder rows, cLN_1 = H rows, cLN_2 = 1 (depthwise)
@@ -602,7 +592,7 @@ int brv_ctn_stream_step(const brv_ctn_config* cfg, const float* params, void* st
     Commit k{c, W + ws.fr, l.S, l.K, l.norms, g_enc, g_h};
     hipLaunchKernelGGL(stream_commit_kernel, dim3((unsigned)n), dim3(256), 0, st, k);
   }
-  HIP_OKS(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 

@@ -10,21 +10,11 @@
 
 #include "../../include/brever_hip.h"
 #include "common.cuh"
+#include "status.h"
 
 using namespace brv;
 
 namespace {
-
-#define DC_OK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return (int)e_; } while (0)
-
-dim3 flat_grid(long long n) {
-  long long g = (n + 255)/256;
-  if (g < 1) g = 1;
-  if (g > 8192) g = 8192;
-  return dim3((unsigned)g);
-}
-#define GRID_STRIDE(i, n) \
-  for (long long i = (long long)blockIdx.x*256 + threadIdx.x; i < (n); i += (long long)gridDim.x*256)
 
 struct ConvGeom {
   int B, Cin, H, W, Cout, Ho, Wo, kh, kw, sh, sw, ph, pw;
@@ -1369,15 +1359,16 @@ int brv_conv2d_forward(const float* x, const float* w, const float* bias, float*
                        int64_t Cin, int64_t H, int64_t W, int64_t Cout, int64_t kh, int64_t kw,
                        int64_t sh, int64_t sw, int64_t ph, int64_t pw, int64_t x_batch_stride,
                        int64_t y_batch_stride, int accumulate, float sign, brv_stream_t stream) {
+  BRV_REFUSE(sh < 1 || sw < 1, "requires sh >= 1, sw >= 1");
   ConvGeom g;
   g.B = (int)B; g.Cin = (int)Cin; g.H = (int)H; g.W = (int)W; g.Cout = (int)Cout;
   g.kh = (int)kh; g.kw = (int)kw; g.sh = (int)sh; g.sw = (int)sw; g.ph = (int)ph; g.pw = (int)pw;
   g.Ho = (int)((H + 2*ph - kh)/sh + 1); g.Wo = (int)((W + 2*pw - kw)/sw + 1);
   g.x_bs = x_batch_stride; g.y_bs = y_batch_stride;
-  if (B < 1 || g.Ho < 1 || g.Wo < 1) return -1;
+  BRV_REFUSE(B < 1 || g.Ho < 1 || g.Wo < 1, "requires B >= 1, Ho >= 1, Wo >= 1");
   hipLaunchKernelGGL(conv2d_fwd_kernel, flat_grid((long long)B*Cout*g.Ho*g.Wo), dim3(256), 0,
                      (hipStream_t)stream, x, w, bias, y, g, accumulate, sign);
-  DC_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 
@@ -1392,10 +1383,10 @@ int brv_conv_transpose2d_forward(const float* x, const float* w, const float* bi
   g.kh = (int)kh; g.kw = (int)kw; g.sh = (int)sh; g.sw = (int)sw; g.ph = (int)ph; g.pw = (int)pw;
   g.Ho = (int)((H - 1)*sh - 2*ph + kh + oph); g.Wo = (int)((W - 1)*sw - 2*pw + kw + opw);
   g.x_bs = x_batch_stride; g.y_bs = y_batch_stride;
-  if (B < 1 || g.Ho < 1 || g.Wo < 1) return -1;
+  BRV_REFUSE(B < 1 || g.Ho < 1 || g.Wo < 1, "requires B >= 1, Ho >= 1, Wo >= 1");
   hipLaunchKernelGGL(conv_transpose2d_fwd_kernel, flat_grid((long long)B*Cout*g.Ho*g.Wo),
                      dim3(256), 0, (hipStream_t)stream, x, w, bias, y, g, accumulate, sign);
-  DC_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 
@@ -1407,17 +1398,18 @@ static int bn_forward_any(const TI* x, const float* gamma, const float* beta,
                             TO* y, float* save_mean, float* save_invstd, int64_t B, int64_t C,
                             int64_t HW, float eps, float momentum, int training,
                             brv_stream_t stream) {
-  if (B < 1 || C < 1 || HW < 1) return -1;
+  BRV_REFUSE(B < 1 || C < 1 || HW < 1, "requires B >= 1, C >= 1, HW >= 1");
   constexpr bool kF32 = sizeof(TO) == 4 && sizeof(TI) == 4;
-  if (!kF32 && ((HW & 3) || C > 65535 || B > 1024 || ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15)))
-    return -1;                                  // bf16 input / output exist in the four-elements-per-access form only
+  // bf16 input / output exist in the four-elements-per-access form only
+  BRV_REFUSE(!kF32 && ((HW & 3) || C > 65535 || B > 1024 || ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15)),
+             "bf16 input/output: HW must be a multiple of 4, C <= 65535, B <= 1024 and x, y 16-byte aligned");
   hipStream_t st = (hipStream_t)stream;
   if (training) {
     const bool vec = (HW & 3) == 0 && B <= 1024 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
     const int pieces = vec ? (int)(red_slices(HW) > 4 ? 4 : red_slices(HW)) : 0;
     const int slices = vec ? (int)B*pieces : red_slices(B*HW);
     double* part = nullptr;
-    DC_OK(hipMallocAsync((void**)&part, (size_t)C*slices*2*sizeof(double), st));
+    BRV_HIP_OK(hipMallocAsync((void**)&part, (size_t)C*slices*2*sizeof(double), st));
     if (vec) hipLaunchKernelGGL(bn_stats_part4_kernel<TI>, dim3((unsigned)C, (unsigned)slices), dim3(256), 0, st,
                                 x, (int)C, (long long)HW, pieces, part);
     else if constexpr (kF32) hipLaunchKernelGGL(bn_stats_part_kernel, dim3((unsigned)C, (unsigned)slices), dim3(256), 0, st,
@@ -1425,9 +1417,9 @@ static int bn_forward_any(const TI* x, const float* gamma, const float* beta,
     hipLaunchKernelGGL(bn_stats_kernel, dim3((unsigned)((C + 255)/256)), dim3(256), 0, st, part,
                        slices, (int)B, (int)C, (long long)HW, save_mean, save_invstd, running_mean,
                        running_var, eps, momentum);
-    DC_OK(hipFreeAsync(part, st));
+    BRV_HIP_OK(hipFreeAsync(part, st));
   } else {
-    DC_OK(hipMemcpyAsync(save_mean, running_mean, (size_t)C*4, hipMemcpyDeviceToDevice, st));
+    BRV_HIP_OK(hipMemcpyAsync(save_mean, running_mean, (size_t)C*4, hipMemcpyDeviceToDevice, st));
     hipLaunchKernelGGL(invstd_from_var_kernel, dim3((unsigned)((C + 255)/256)), dim3(256), 0, st,
                        running_var, save_invstd, (int)C, eps);
   }
@@ -1440,7 +1432,7 @@ static int bn_forward_any(const TI* x, const float* gamma, const float* beta,
   } else if constexpr (kF32)
   hipLaunchKernelGGL(bn_apply_kernel, flat_grid(total), dim3(256), 0, st, x, save_mean,
                      save_invstd, gamma, beta, prelu_slope, y, (int)C, (long long)HW, total);
-  DC_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 
@@ -1476,7 +1468,8 @@ int brv_batchnorm2d_forward_bf16io(const void* x16, const float* gamma, const fl
 int brv_lstm_recurrent_forward(const float* gates_in, const float* w_hh, const float* bias,
                                float* y, float* act, float* cs, int64_t B, int64_t T, int64_t H,
                                int64_t groups, brv_stream_t stream) {
-  if (B < 1 || T < 1 || H < 1 || groups < 1 || B % groups) return -1;
+  BRV_REFUSE(B < 1 || T < 1 || H < 1 || groups < 1 || B % groups,
+             "requires B >= 1, T >= 1, H >= 1, groups >= 1, B a multiple of groups");
   const int per_group = (int)(B/groups);
   if (H == 128) {
     if (act && cs)
@@ -1493,15 +1486,18 @@ int brv_lstm_recurrent_forward(const float* gates_in, const float* w_hh, const f
   hipLaunchKernelGGL(lstm_recurrent_kernel, dim3((unsigned)B), dim3(256), (size_t)6*H*4,
                      (hipStream_t)stream, gates_in, w_hh, bias, y, act, cs, (int)T, (int)H,
                      per_group);
-  DC_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 
 int brv_lstm_recurrent_forward_bf16(const float* gates_in, const float* w_hh, const float* bias,
                                     float* y, float* act, float* cs, int64_t B, int64_t T, int64_t H,
                                     int64_t groups, brv_stream_t stream) {
-  if (B < 1 || T < 1 || groups < 1 || B % groups) return -1;
-  if (H != 128) return -1;                               // (brv_lstm_recurrent_bf16_supported)
+  BRV_REFUSE(B < 1 || T < 1 || groups < 1 || B % groups,
+             "requires B >= 1, T >= 1, groups >= 1, B a multiple of groups");
+  // (brv_lstm_recurrent_bf16_supported)
+  BRV_REFUSE(H != 128,
+             "H != 128: brv_lstm_recurrent_bf16_supported");
   const int per_group = (int)(B/groups);
   if (act && cs)
     hipLaunchKernelGGL(lstm_fwd_mv_kernel<true>, dim3((unsigned)B), dim3(512), 0, (hipStream_t)stream,
@@ -1509,18 +1505,19 @@ int brv_lstm_recurrent_forward_bf16(const float* gates_in, const float* w_hh, co
   else
     hipLaunchKernelGGL(lstm_fwd_mv_kernel<false>, dim3((unsigned)B), dim3(512), 0, (hipStream_t)stream,
                        gates_in, w_hh, bias, y, act, cs, (int)T, per_group);
-  DC_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 
 int brv_lstm_recurrent_backward_bf16(const float* act, const float* cs, const float* w_hh,
                                      const float* dy, float* dgates, int64_t B, int64_t T, int64_t H,
                                      int64_t groups, brv_stream_t stream) {
-  if (B < 1 || T < 1 || groups < 1 || B % groups) return -1;
-  if (H != 128) return -1;
+  BRV_REFUSE(B < 1 || T < 1 || groups < 1 || B % groups,
+             "requires B >= 1, T >= 1, groups >= 1, B a multiple of groups");
+  BRV_REFUSE(H != 128, "H != 128: brv_lstm_recurrent_bf16_supported");
   hipLaunchKernelGGL(lstm_bwd_mv_kernel, dim3((unsigned)B), dim3(512), 0, (hipStream_t)stream, act, cs,
                      w_hh, dy, dgates, (int)T, (int)(B/groups));
-  DC_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 
@@ -1528,49 +1525,52 @@ int brv_lstm_recurrent_bf16_supported(int64_t H) { return H == 128; }
 
 int brv_combine(const float* a, const float* b, float* out, int64_t n, float sign,
                 brv_stream_t stream) {
-  if (n < 1) return -1;
+  BRV_REFUSE(n < 1, "requires n >= 1");
   hipLaunchKernelGGL(combine_kernel, flat_grid(n), dim3(256), 0, (hipStream_t)stream, a, b, out,
                      (long long)n, sign);
-  DC_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 
 int brv_complex_mix_forward(const float* o, float* real, float* imag, int64_t n, brv_stream_t stream) {
-  if (!o || !real || !imag || n < 4 || (n & 3) ||
-      ((reinterpret_cast<uintptr_t>(o) | reinterpret_cast<uintptr_t>(real) | reinterpret_cast<uintptr_t>(imag)) & 15)) return -1;
+  BRV_REFUSE(!o || !real || !imag || n < 4 || (n & 3) ||
+             ((reinterpret_cast<uintptr_t>(o) | reinterpret_cast<uintptr_t>(real) | reinterpret_cast<uintptr_t>(imag)) & 15),
+             "requires o, real, imag != NULL and 16-byte aligned, n >= 4 and a multiple of 4");
   hipLaunchKernelGGL(complex_mix_fwd_kernel, flat_grid(n/4), dim3(256), 0, (hipStream_t)stream, (const float4*)o,
                      (float4*)real, (float4*)imag, (long long)(n/4));
-  DC_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 
 int brv_complex_mix_backward(const float* greal, const float* gimag, float* dout, int64_t n, brv_stream_t stream) {
-  if (!greal || !gimag || !dout || n < 4 || (n & 3) ||
-      ((reinterpret_cast<uintptr_t>(greal) | reinterpret_cast<uintptr_t>(gimag) | reinterpret_cast<uintptr_t>(dout)) & 15)) return -1;
+  BRV_REFUSE(!greal || !gimag || !dout || n < 4 || (n & 3) ||
+             ((reinterpret_cast<uintptr_t>(greal) | reinterpret_cast<uintptr_t>(gimag) | reinterpret_cast<uintptr_t>(dout)) & 15),
+             "requires greal, gimag, dout != NULL and 16-byte aligned, n >= 4 and a multiple of 4");
   hipLaunchKernelGGL(complex_mix_bwd_kernel, flat_grid(n/4), dim3(256), 0, (hipStream_t)stream, (const float4*)greal,
                      (const float4*)gimag, (float4*)dout, (long long)(n/4));
-  DC_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 
 int brv_dccrn_apply_mask(const float* xr, const float* xi, const float* mr, const float* mi,
                          float* out, int64_t n, brv_stream_t stream) {
-  if (n < 1) return -1;
+  BRV_REFUSE(n < 1, "requires n >= 1");
   hipLaunchKernelGGL(dccrn_mask_kernel, flat_grid(n), dim3(256), 0, (hipStream_t)stream, xr, xi,
                      mr, mi, (float2*)out, (long long)n, 0LL);
-  DC_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 
 int brv_dccrn_apply_mask_batched(const float* x, const float* mask, float* out, int64_t B, int64_t n,
                                  brv_stream_t stream) {
-  if (!x || !mask || !out || B < 1 || B > 65535 || n < 1) return -1;
+  BRV_REFUSE(!x || !mask || !out || B < 1 || B > 65535 || n < 1,
+             "requires x != NULL, mask != NULL, out != NULL, B >= 1, B <= 65535, n >= 1");
   dim3 grid = flat_grid(n);
   if (grid.x > 4096) grid.x = 4096;
   grid.y = (unsigned)B;
   hipLaunchKernelGGL(dccrn_mask_kernel, grid, dim3(256), 0, (hipStream_t)stream, x, x + n, mask, mask + n,
                      (float2*)out, (long long)n, (long long)(2*n));
-  DC_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 
@@ -1583,14 +1583,14 @@ int brv_conv2d_wgrad(const float* x, const float* dy, float* dw, float* dbias, i
   g.B = (int)B; g.Cin = (int)Cin; g.H = (int)H; g.W = (int)W; g.Cout = (int)Cout;
   g.kh = (int)kh; g.kw = (int)kw; g.sh = (int)sh; g.sw = (int)sw; g.ph = (int)ph; g.pw = (int)pw;
   g.Ho = (int)Ho; g.Wo = (int)Wo; g.x_bs = x_batch_stride; g.y_bs = dy_batch_stride;
-  if (B < 1 || Ho < 1 || Wo < 1) return -1;
+  BRV_REFUSE(B < 1 || Ho < 1 || Wo < 1, "requires B >= 1, Ho >= 1, Wo >= 1");
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(conv2d_wgrad_kernel, dim3((unsigned)(Cout*Cin*kh*kw)), dim3(256), 0, st, x,
                      dy, dw, g, accumulate, sign);
   if (dbias)
     hipLaunchKernelGGL(channel_sum_kernel, dim3((unsigned)Cout), dim3(256), 0, st, dy, dbias,
                        (int)B, (long long)Ho*Wo, (long long)dy_batch_stride, accumulate, sign);
-  DC_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 
@@ -1602,18 +1602,21 @@ static int bn_backward_any(const TI* x, const TG* dy, const TG* dy2, const float
                              const float* prelu_slope, TO* dx, float* dgamma, float* dbeta,
                              float* dslope_partial, float* dx_sums, int64_t B, int64_t C, int64_t HW,
                              brv_stream_t stream) {
-  if (B < 1 || C < 1 || HW < 1) return -1;
+  BRV_REFUSE(B < 1 || C < 1 || HW < 1, "requires B >= 1, C >= 1, HW >= 1");
   constexpr bool kF32 = sizeof(TO) == 4 && sizeof(TI) == 4 && sizeof(TG) == 4;
-  if (dy2 && ((HW & 3) || B > 1024 || (reinterpret_cast<uintptr_t>(dy2) & 15))) return -1;     // (the vector kernels only)
-  if ((!kF32 || dx_sums || dy2) && ((HW & 3) || C > 65535 || B > (kF32 ? 65535 : 1024) ||
-      ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(dx)) & 15)))
-    return -1;                                  // bf16 output / dx sums: the 16-byte form only
+  // (the vector kernels only)
+  BRV_REFUSE(dy2 && ((HW & 3) || B > 1024 || (reinterpret_cast<uintptr_t>(dy2) & 15)),
+             "dy2: HW must be a multiple of 4, B <= 1024 and dy2 16-byte aligned");
+  // bf16 output / dx sums: the 16-byte form only
+  BRV_REFUSE((!kF32 || dx_sums || dy2) && ((HW & 3) || C > 65535 || B > (kF32 ? 65535 : 1024) ||
+             ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(dx)) & 15)),
+             "bf16 tensors / dx_sums / dy2: HW must be a multiple of 4, C <= 65535, B <= 1024 (fp32: 65535) and x, dy, dx 16-byte aligned");
   hipStream_t st = (hipStream_t)stream;
   const bool vec = (HW & 3) == 0 && B <= 1024 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy)) & 15) == 0;
   const int pieces = vec ? (int)(red_slices(HW) > 4 ? 4 : red_slices(HW)) : 0;
   const int slices = vec ? (int)B*pieces : red_slices(B*HW);
   double* part = nullptr;
-  DC_OK(hipMallocAsync((void**)&part, (size_t)C*slices*3*sizeof(double), st));
+  BRV_HIP_OK(hipMallocAsync((void**)&part, (size_t)C*slices*3*sizeof(double), st));
   if (vec) hipLaunchKernelGGL((bn_bwd_stats4_kernel<TI, TG>), dim3((unsigned)C, (unsigned)slices), dim3(256), 0, st, x,
                               dy, dy2, save_mean, save_invstd, gamma, beta, prelu_slope, (int)C, (long long)HW,
                               pieces, part);
@@ -1622,27 +1625,27 @@ static int bn_backward_any(const TI* x, const TG* dy, const TG* dy2, const float
                      (long long)HW, part);
   hipLaunchKernelGGL(bn_bwd_final_kernel, dim3((unsigned)((C + 255)/256)), dim3(256), 0, st, part,
                      slices, (int)C, dgamma, dbeta, dslope_partial);
-  DC_OK(hipFreeAsync(part, st));
+  BRV_HIP_OK(hipFreeAsync(part, st));
   const long long total = B*C*HW;
   if ((HW & 3) == 0 && C <= 65535 && B <= 65535 &&
       ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(dx)) & 15) == 0) {
     long long gx = (HW/4 + 1023)/1024;
     if (gx < 1) gx = 1;
     double* sums = nullptr;
-    if (dx_sums) DC_OK(hipMallocAsync((void**)&sums, (size_t)C*B*gx*sizeof(double), st));
+    if (dx_sums) BRV_HIP_OK(hipMallocAsync((void**)&sums, (size_t)C*B*gx*sizeof(double), st));
     hipLaunchKernelGGL((bn_bwd_apply4_kernel<TI, TG, TO>), dim3((unsigned)gx, (unsigned)C, (unsigned)B), dim3(256), 0, st, x, dy, dy2,
                        save_mean, save_invstd, gamma, beta, prelu_slope, dgamma, dbeta, dx, (int)C, (long long)HW,
                        1.f/(float)(B*HW), sums);
     if (dx_sums) {
       hipLaunchKernelGGL(bn_dxsum_kernel, dim3((unsigned)((C + 255)/256)), dim3(256), 0, st, sums, (int)(B*gx), (int)C,
                          dx_sums);
-      DC_OK(hipFreeAsync(sums, st));
+      BRV_HIP_OK(hipFreeAsync(sums, st));
     }
   } else if constexpr (kF32)
   hipLaunchKernelGGL(bn_bwd_apply_kernel, flat_grid(total), dim3(256), 0, st, x, dy, save_mean,
                      save_invstd, gamma, beta, prelu_slope, dgamma, dbeta, dx, (int)C,
                      (long long)HW, total, 1.f/(float)(B*HW));
-  DC_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 
@@ -1681,7 +1684,7 @@ int brv_batchnorm2d_backward_ex(const void* x, int32_t x_bf16, const void* dy_, 
                                 const float* prelu_slope, void* dx, int32_t dx_bf16, float* dgamma, float* dbeta,
                                 float* dslope_partial, float* dx_sums, int64_t B, int64_t C, int64_t HW,
                                 brv_stream_t stream) {
-  if (x_bf16 && !dx_bf16) return -1;
+  BRV_REFUSE(x_bf16 && !dx_bf16, "a bf16 x requires a bf16 dx");
   if (dy_bf16) {           // the gradients with respect to the output as bf16 (what autocast hands a bf16 activation)
     const bf16_t* g = (const bf16_t*)dy_; const bf16_t* g2 = (const bf16_t*)dy2_;
     if (x_bf16) return bn_backward_any<bf16_t, bf16_t, bf16_t>((const bf16_t*)x, g, g2, save_mean, save_invstd, gamma, beta,
@@ -1707,7 +1710,8 @@ int brv_batchnorm2d_backward_ex(const void* x, int32_t x_bf16, const void* dy_, 
 int brv_lstm_recurrent_backward(const float* act, const float* cs, const float* w_hh,
                                 const float* dy, float* dgates, int64_t B, int64_t T, int64_t H,
                                 int64_t groups, brv_stream_t stream) {
-  if (B < 1 || T < 1 || H < 1 || groups < 1 || B % groups) return -1;
+  BRV_REFUSE(B < 1 || T < 1 || H < 1 || groups < 1 || B % groups,
+             "requires B >= 1, T >= 1, H >= 1, groups >= 1, B a multiple of groups");
   const int per_group = (int)(B/groups);
   if (H == 128)
     hipLaunchKernelGGL(lstm_bwd_quad_kernel, dim3((unsigned)B), dim3(512), 0, (hipStream_t)stream, act, cs,
@@ -1718,40 +1722,41 @@ int brv_lstm_recurrent_backward(const float* act, const float* cs, const float* 
   else
   hipLaunchKernelGGL(lstm_bwd_kernel, dim3((unsigned)B), dim3(256), (size_t)6*H*4,
                      (hipStream_t)stream, act, cs, w_hh, dy, dgates, (int)T, (int)H, per_group);
-  DC_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 
 int brv_dccrn_apply_mask_backward(const float* xr, const float* xi, const float* mr,
                                   const float* mi, const float* gout, float* dmr, float* dmi,
                                   int64_t n, brv_stream_t stream) {
-  if (n < 1) return -1;
+  BRV_REFUSE(n < 1, "requires n >= 1");
   hipLaunchKernelGGL(dccrn_mask_bwd_kernel, flat_grid(n), dim3(256), 0, (hipStream_t)stream, xr,
                      xi, mr, mi, (const float2*)gout, dmr, dmi, (long long)n, 0LL);
-  DC_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 
 int brv_dccrn_apply_mask_backward_batched(const float* x, const float* mask, const float* gout, float* dmask,
                                           int64_t B, int64_t n, brv_stream_t stream) {
-  if (!x || !mask || !gout || !dmask || B < 1 || B > 65535 || n < 1) return -1;
+  BRV_REFUSE(!x || !mask || !gout || !dmask || B < 1 || B > 65535 || n < 1,
+             "requires x != NULL, mask != NULL, gout != NULL, dmask != NULL, B >= 1, B <= 65535, n >= 1");
   dim3 grid = flat_grid(n);
   if (grid.x > 4096) grid.x = 4096;
   grid.y = (unsigned)B;
   hipLaunchKernelGGL(dccrn_mask_bwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, x, x + n, mask, mask + n,
                      (const float2*)gout, dmask, dmask + n, (long long)n, (long long)(2*n));
-  DC_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 
 int brv_istft_env_divide(const float* dy, const float* window, float* out, int64_t rows,
                          int64_t length, int64_t frame_length, int64_t hop_length, int64_t frames,
                          brv_stream_t stream) {
-  if (rows < 1 || length < 1) return -1;
+  BRV_REFUSE(rows < 1 || length < 1, "requires rows >= 1, length >= 1");
   hipLaunchKernelGGL(env_divide_kernel, flat_grid(rows*length), dim3(256), 0, (hipStream_t)stream,
                      dy, window, out, (int)rows, (int)length, (int)frame_length, (int)hop_length,
                      (int)frames);
-  DC_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 
@@ -1760,30 +1765,32 @@ template <typename ColT>
 static int im2col_any(const float* x, ColT* col, int64_t B, int64_t C, int64_t H, int64_t W, int64_t kh,
                       int64_t kw, int64_t sh, int64_t sw, int64_t ph, int64_t pw, int64_t Ho,
                       int64_t Wo, brv_stream_t stream) {
-  if (B < 1 || C < 1 || Ho < 1 || Wo < 1) return -1;
+  BRV_REFUSE(B < 1 || C < 1 || Ho < 1 || Wo < 1, "requires B >= 1, C >= 1, Ho >= 1, Wo >= 1");
   ConvGeom g;
   g.B = (int)B; g.Cin = (int)C; g.H = (int)H; g.W = (int)W; g.Cout = 0;
   g.kh = (int)kh; g.kw = (int)kw; g.sh = (int)sh; g.sw = (int)sw; g.ph = (int)ph; g.pw = (int)pw;
   g.Ho = (int)Ho; g.Wo = (int)Wo; g.x_bs = C*H*W; g.y_bs = 0;
-  if (C*kh*kw > 65535 || B > 65535 || H*W >= (1LL << 31) || Ho*Wo >= (1LL << 31)) return -2;
+  BRV_UNSUPPORTED(C*kh*kw > 65535 || B > 65535 || H*W >= (1LL << 31) || Ho*Wo >= (1LL << 31),
+                  "requires C*kh*kw <= 65535, B <= 65535, H*W < 2^31, Ho*Wo < 2^31");
   hipLaunchKernelGGL(im2col_kernel<ColT>, dim3((unsigned)((Ho*Wo + 1023)/1024), (unsigned)(C*kh*kw),
                                                (unsigned)B), dim3(256), 0, (hipStream_t)stream, x, col, g);
-  DC_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 template <typename ColT>
 static int col2im_any(const ColT* col, const float* bias, float* y, int64_t B, int64_t C, int64_t H,
                       int64_t W, int64_t kh, int64_t kw, int64_t sh, int64_t sw, int64_t ph, int64_t pw,
                       int64_t Ho, int64_t Wo, brv_stream_t stream) {
-  if (B < 1 || C < 1 || H < 1 || W < 1) return -1;
+  BRV_REFUSE(B < 1 || C < 1 || H < 1 || W < 1, "requires B >= 1, C >= 1, H >= 1, W >= 1");
   ConvGeom g;
   g.B = (int)B; g.Cin = (int)C; g.H = (int)H; g.W = (int)W; g.Cout = 0;
   g.kh = (int)kh; g.kw = (int)kw; g.sh = (int)sh; g.sw = (int)sw; g.ph = (int)ph; g.pw = (int)pw;
   g.Ho = (int)Ho; g.Wo = (int)Wo; g.x_bs = 0; g.y_bs = C*H*W;
-  if (C > 65535 || B > 65535 || H*W >= (1LL << 31) || Ho*Wo >= (1LL << 31)) return -2;
+  BRV_UNSUPPORTED(C > 65535 || B > 65535 || H*W >= (1LL << 31) || Ho*Wo >= (1LL << 31),
+                  "requires C <= 65535, B <= 65535, H*W < 2^31, Ho*Wo < 2^31");
   hipLaunchKernelGGL(col2im_kernel<ColT>, dim3((unsigned)((H*W + 255)/256), (unsigned)C, (unsigned)B),
                      dim3(256), 0, (hipStream_t)stream, col, bias, y, g);
-  DC_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 }  // extern "C++"
@@ -1810,96 +1817,96 @@ int brv_col2im_bf16(const void* col, const float* bias, float* y, int64_t B, int
 }
 int brv_complex_weight_pack(const float* wr, const float* wi, float* wc, int64_t R, int64_t C,
                             float sign, brv_stream_t stream) {
-  if (R < 1 || C < 1) return -1;
+  BRV_REFUSE(R < 1 || C < 1, "requires R >= 1, C >= 1");
   hipLaunchKernelGGL(cweight_pack_kernel, flat_grid(4*R*C), dim3(256), 0, (hipStream_t)stream, wr,
                      wi, wc, (int)R, (int)C, sign);
-  DC_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 int brv_complex_weight_unpack(const float* dwc, float* dwr, float* dwi, int64_t R, int64_t C,
                               float sign, brv_stream_t stream) {
-  if (R < 1 || C < 1) return -1;
+  BRV_REFUSE(R < 1 || C < 1, "requires R >= 1, C >= 1");
   hipLaunchKernelGGL(cweight_unpack_kernel, flat_grid(R*C), dim3(256), 0, (hipStream_t)stream, dwc,
                      dwr, dwi, (int)R, (int)C, sign);
-  DC_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 
 int brv_complex_bias_pack(const float* br, const float* bi, float* out, int64_t C, brv_stream_t stream) {
-  if (!br || !bi || !out || C < 1) return -1;
+  BRV_REFUSE(!br || !bi || !out || C < 1, "requires br != NULL, bi != NULL, out != NULL, C >= 1");
   hipLaunchKernelGGL(cbias_pack_kernel, dim3((unsigned)((C + 255)/256)), dim3(256), 0, (hipStream_t)stream, br, bi,
                      out, (int)C);
-  DC_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 int brv_complex_bias_unpack(const float* sums, float* dbr, float* dbi, int64_t C, brv_stream_t stream) {
-  if (!sums || !dbr || !dbi || C < 1) return -1;
+  BRV_REFUSE(!sums || !dbr || !dbi || C < 1, "requires sums != NULL, dbr != NULL, dbi != NULL, C >= 1");
   hipLaunchKernelGGL(cbias_unpack_kernel, dim3((unsigned)((C + 255)/256)), dim3(256), 0, (hipStream_t)stream, sums,
                      dbr, dbi, (int)C);
-  DC_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 
 int brv_cplx_moments(const float* x, float* moments, int64_t B, int64_t C, int64_t HW,
                      brv_stream_t stream) {
-  if (B < 1 || C < 1 || HW < 1) return -1;
+  BRV_REFUSE(B < 1 || C < 1 || HW < 1, "requires B >= 1, C >= 1, HW >= 1");
   hipStream_t st = (hipStream_t)stream;
   const int slices = red_slices(B*HW);
   double* part = nullptr;
-  DC_OK(hipMallocAsync((void**)&part, (size_t)C*slices*5*sizeof(double), st));
+  BRV_HIP_OK(hipMallocAsync((void**)&part, (size_t)C*slices*5*sizeof(double), st));
   hipLaunchKernelGGL(cplx_moments_part_kernel, dim3((unsigned)C, (unsigned)slices), dim3(256), 0, st,
                      x, (int)B, (int)C, (long long)HW, part);
   hipLaunchKernelGGL(slice_final_kernel, dim3((unsigned)((5*C + 255)/256)), dim3(256), 0, st, part,
                      slices, 5, (int)C, 1.0/((double)B*(double)HW), moments);
-  DC_OK(hipFreeAsync(part, st));
-  DC_OK(hipGetLastError());
+  BRV_HIP_OK(hipFreeAsync(part, st));
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 int brv_cplx_affine_forward(const float* x, const float* A, const float* o, const float* prelu_slope,
                             float* y, int64_t B, int64_t C, int64_t HW, brv_stream_t stream) {
-  if (B < 1 || C < 1 || HW < 1) return -1;
+  BRV_REFUSE(B < 1 || C < 1 || HW < 1, "requires B >= 1, C >= 1, HW >= 1");
   const long long total = B*C*HW;
   hipLaunchKernelGGL(cplx_affine_fwd_kernel, flat_grid(total), dim3(256), 0, (hipStream_t)stream, x,
                      A, o, prelu_slope, y, (int)C, (long long)HW, total);
-  DC_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 int brv_cplx_affine_backward(const float* x, const float* dy, const float* A, const float* o,
                              const float* prelu_slope, float* dx, float* dA, float* d_o,
                              float* dslope_partial, int64_t B, int64_t C, int64_t HW,
                              brv_stream_t stream) {
-  if (B < 1 || C < 1 || HW < 1) return -1;
+  BRV_REFUSE(B < 1 || C < 1 || HW < 1, "requires B >= 1, C >= 1, HW >= 1");
   hipStream_t st = (hipStream_t)stream;
   const int slices = red_slices(B*HW);
   double* part = nullptr;
   float* sums = nullptr;
-  DC_OK(hipMallocAsync((void**)&part, (size_t)C*slices*7*sizeof(double), st));
-  DC_OK(hipMallocAsync((void**)&sums, (size_t)7*C*sizeof(float), st));
+  BRV_HIP_OK(hipMallocAsync((void**)&part, (size_t)C*slices*7*sizeof(double), st));
+  BRV_HIP_OK(hipMallocAsync((void**)&sums, (size_t)7*C*sizeof(float), st));
   hipLaunchKernelGGL(cplx_affine_bwd_part_kernel, dim3((unsigned)C, (unsigned)slices), dim3(256), 0,
                      st, x, dy, A, o, prelu_slope, (int)B, (int)C, (long long)HW, part);
   hipLaunchKernelGGL(slice_final_kernel, dim3((unsigned)((7*C + 255)/256)), dim3(256), 0, st, part,
                      slices, 7, (int)C, 1.0, sums);
-  DC_OK(hipMemcpyAsync(dA, sums, (size_t)4*C*4, hipMemcpyDeviceToDevice, st));
-  DC_OK(hipMemcpyAsync(d_o, sums + 4*C, (size_t)2*C*4, hipMemcpyDeviceToDevice, st));
+  BRV_HIP_OK(hipMemcpyAsync(dA, sums, (size_t)4*C*4, hipMemcpyDeviceToDevice, st));
+  BRV_HIP_OK(hipMemcpyAsync(d_o, sums + 4*C, (size_t)2*C*4, hipMemcpyDeviceToDevice, st));
   if (dslope_partial)
-    DC_OK(hipMemcpyAsync(dslope_partial, sums + 6*C, (size_t)C*4, hipMemcpyDeviceToDevice, st));
-  DC_OK(hipFreeAsync(part, st));
-  DC_OK(hipFreeAsync(sums, st));
+    BRV_HIP_OK(hipMemcpyAsync(dslope_partial, sums + 6*C, (size_t)C*4, hipMemcpyDeviceToDevice, st));
+  BRV_HIP_OK(hipFreeAsync(part, st));
+  BRV_HIP_OK(hipFreeAsync(sums, st));
   const long long total = B*C*HW;
   hipLaunchKernelGGL(cplx_affine_bwd_apply_kernel, flat_grid(total), dim3(256), 0, st, x, dy, A, o,
                      prelu_slope, (const float*)nullptr, dx, (int)C, (long long)HW, total);
-  DC_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 int brv_cplx_moments_backward(const float* x, const float* gm, float* dx, int64_t B, int64_t C,
                               int64_t HW, brv_stream_t stream) {
-  if (B < 1 || C < 1 || HW < 1) return -1;
+  BRV_REFUSE(B < 1 || C < 1 || HW < 1, "requires B >= 1, C >= 1, HW >= 1");
   const long long total = B*C*HW;
   hipLaunchKernelGGL(cplx_affine_bwd_apply_kernel, flat_grid(total), dim3(256), 0,
                      (hipStream_t)stream, x, (const float*)nullptr, (const float*)nullptr,
                      (const float*)nullptr, (const float*)nullptr, gm, dx, (int)C, (long long)HW,
                      total);
-  DC_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 

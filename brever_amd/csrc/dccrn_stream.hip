@@ -36,21 +36,11 @@
 
 #include "../../include/brever_hip.h"
 #include "common.cuh"
+#include "status.h"
 
 using namespace brv;
 
-extern "C" __attribute__((visibility("hidden"))) void brv_internal_set_error(const char* msg);   // convtasnet.hip
-
 namespace {
-
-int failD(int code, const std::string& msg) { brv_internal_set_error(msg.c_str()); return code; }
-
-#define HIP_OKD(expr)                                                          \
-  do {                                                                         \
-    hipError_t e_ = (expr);                                                    \
-    if (e_ != hipSuccess)                                                      \
-      return failD((int)e_, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
 
 constexpr int kMaxL = BRV_DCCRN_STREAM_MAX_LEVELS;
 constexpr int kNB = 2*kMaxL + 2;       // level buffers
@@ -69,29 +59,29 @@ struct Geo {
   long long st_ring[kNB];                 // floats from the end of the slot header
   long long st_hist, st_tail, st_lstm, st_floats, st_bytes;
   int init(const brv_dccrn_stream_config* c) {
-    if (!c) return failD(-1, "null config");
+    if (!c) return fail(-1, "null config");
     n = c->n_fft; hop = c->hop; L = c->levels; kf = c->kf; kt = c->kt; sf = c->sf; pf = c->pf;
     cbn = c->complex_bn; lh = c->lstm_hidden; ll = c->lstm_layers;
     if (n < 2 || hop < 1 || L < 1 || kf < 1 || kt < 1 || sf < 1 || pf < 0 || c->opf < 0)
-      return failD(-1, "invalid DCCRN hyper-parameters");
+      return fail(-1, "invalid DCCRN hyper-parameters");
     if (c->st != 1 || c->pt != 0 || c->opt != 0)
-      return failD(-2, "streaming: the time axis needs stride 1, padding 0 and output padding 0");
-    if (n % (2*hop)) return failD(-2, "streaming: n_fft must be a multiple of 2 hop");
-    if (n > kMaxN) return failD(-2, "streaming: n_fft must be <= 4096");
-    if (L > kMaxL) return failD(-2, "streaming: at most 8 encoder levels");
-    if (kf*kt > 64) return failD(-2, "streaming: kernel_size[0] * kernel_size[1] must be <= 64");
-    if (lh < 1 || lh > kMaxH || ll < 1 || ll > 4) return failD(-2, "streaming: lstm_channels <= 512, lstm_layers <= 4");
+      return fail(-2, "streaming: the time axis needs stride 1, padding 0 and output padding 0");
+    if (n % (2*hop)) return fail(-2, "streaming: n_fft must be a multiple of 2 hop");
+    if (n > kMaxN) return fail(-2, "streaming: n_fft must be <= 4096");
+    if (L > kMaxL) return fail(-2, "streaming: at most 8 encoder levels");
+    if (kf*kt > 64) return fail(-2, "streaming: kernel_size[0] * kernel_size[1] must be <= 64");
+    if (lh < 1 || lh > kMaxH || ll < 1 || ll > 4) return fail(-2, "streaming: lstm_channels <= 512, lstm_layers <= 4");
     P = n/(2*hop); G = kt - 1; D = L*G; lagh = 2*P - 1 + D; Fq0 = n/2; bins = n/2 + 1;
     C[0] = 1; H[0] = Fq0;
     for (int e = 1; e <= L; ++e) {
       C[e] = c->channels[e - 1];
-      if (C[e] < 1 || C[e] > kMaxC) return failD(-2, "streaming: channel counts must be in [1, 1024]");
+      if (C[e] < 1 || C[e] > kMaxC) return fail(-2, "streaming: channel counts must be in [1, 1024]");
       H[e] = (H[e - 1] + 2*pf - kf)/sf + 1;
-      if (H[e - 1] + 2*pf < kf || H[e] < 1) return failD(-2, "streaming: the encoder runs out of frequency bins");
+      if (H[e - 1] + 2*pf < kf || H[e] < 1) return fail(-2, "streaming: the encoder runs out of frequency bins");
     }
     for (int e = L; e >= 1; --e)
       if ((H[e] - 1)*sf - 2*pf + kf + c->opf != H[e - 1])
-        return failD(-2, "streaming: the decoder's frequency axis does not retrace the encoder's");
+        return fail(-2, "streaming: the decoder's frequency axis does not retrace the encoder's");
     feat = C[L]*H[L];
     nbuf = 2*L + 2;
     elems[0] = 2*Fq0; off[0] = 0; lim[0] = 0; ring[0] = D > G ? D : G;
@@ -548,18 +538,18 @@ int run(const brv_dccrn_stream_config* cfg, const Geo& g, const float* params, c
   hipLaunchKernelGGL(mask_kernel, dim3(blocks_for(C*g.Fq0)), dim3(256), 0, st, c);
   hipLaunchKernelGGL(idft_kernel, dim3((unsigned)C), dim3(256), 0, st, c, synth);
   hipLaunchKernelGGL(commit_kernel, dim3((unsigned)n), dim3(256), 0, st, c, window, y, ylen);
-  HIP_OKD(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 
 int check_cfg_params(const brv_dccrn_stream_config* cfg, const Geo& g) {
   for (int b = 0; b < 2*g.L; ++b) {
     const int64_t* o = cfg->off_block[b];
-    for (int i = 0; i < 4; ++i) if (o[i] < 0) return failD(-1, "streaming: missing convolution parameter offset");
+    for (int i = 0; i < 4; ++i) if (o[i] < 0) return fail(-1, "streaming: missing convolution parameter offset");
     const bool last = b == 2*g.L - 1;
     if (!last && (o[4] < 0 || o[5] < 0 || o[6] < 0 || !cfg->run_mean[b] || !cfg->run_var[b]))
-      return failD(-1, "streaming: missing norm / PReLU of a block");
-    if (last && (o[4] >= 0 || o[6] >= 0)) return failD(-2, "streaming: the last decoder block has no norm / PReLU");
+      return fail(-1, "streaming: missing norm / PReLU of a block");
+    if (last && (o[4] >= 0 || o[6] >= 0)) return fail(-2, "streaming: the last decoder block has no norm / PReLU");
   }
   return 0;
 }
@@ -570,14 +560,14 @@ int step_common(const brv_dccrn_stream_config* cfg, const float* params, const f
                 hipStream_t st) {
   Geo g; if (int r = g.init(cfg)) return r;
   if (int r = check_cfg_params(cfg, g)) return r;
-  if (n < 1 || hops < 1) return failD(-1, "streaming: n and hops must be >= 1");
+  if (n < 1 || hops < 1) return fail(-1, "streaming: n and hops must be >= 1");
   long long widest = 16LL*g.lh > 2LL*g.feat ? 16LL*g.lh : 2LL*g.feat;
   for (int e = 0; e <= g.L; ++e) widest = (long long)g.C[e]*g.H[e] > widest ? (long long)g.C[e]*g.H[e] : widest;
-  if (hops > (1 << 20) || n*hops > (1LL << 30)/widest*256) return failD(-2, "streaming: too many columns in one call");
+  if (hops > (1 << 20) || n*hops > (1LL << 30)/widest*256) return fail(-2, "streaming: too many columns in one call");
   if (!params || !window || !basis || !synth || !state || !ids || !y || !workspace)
-    return failD(-1, "streaming: null pointer argument");
+    return fail(-1, "streaming: null pointer argument");
   WsD w; w.init(g, n*hops, (int)hops);
-  if (workspace_bytes < w.total*4) return failD(-1, "streaming: workspace too small");
+  if (workspace_bytes < w.total*4) return fail(-1, "streaming: workspace too small");
   if (amp) return run<1>(cfg, g, params, window, basis, synth, state, ids, n, x, (int)hops, end_rest, y, ylen,
                          workspace, st);
   return run<0>(cfg, g, params, window, basis, synth, state, ids, n, x, (int)hops, end_rest, y, ylen, workspace, st);
@@ -595,7 +585,7 @@ int64_t brv_dccrn_stream_state_bytes(const brv_dccrn_stream_config* cfg) {
 int64_t brv_dccrn_stream_workspace_bytes(const brv_dccrn_stream_config* cfg, int64_t n, int64_t hops, int32_t amp) {
   (void)amp;     // both precisions keep fp32 activations between the launches
   Geo g; if (int r = g.init(cfg)) return r;
-  if (n < 1 || hops < 1) return failD(-1, "streaming: n and hops must be >= 1");
+  if (n < 1 || hops < 1) return fail(-1, "streaming: n and hops must be >= 1");
   WsD w; w.init(g, n*hops, (int)hops);
   return w.total*4;
 }
@@ -606,7 +596,7 @@ int brv_dccrn_stream_reset(const brv_dccrn_stream_config* cfg, void* state, cons
   if (n < 1) return 0;
   hipLaunchKernelGGL(reset_kernel, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, (unsigned char*)state,
                      g.st_bytes, ids);
-  HIP_OKD(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 
@@ -615,7 +605,7 @@ int brv_dccrn_stream_step(const brv_dccrn_stream_config* cfg, const float* param
                           int64_t n, const float* x, int64_t hops, float* y, int32_t amp, void* workspace,
                           int64_t workspace_bytes, const brv_launch_opts* opts, brv_stream_t stream) {
   (void)opts;    // no option of this entry point yet (size / flags reserved)
-  if (!x) return failD(-1, "streaming: null input");
+  if (!x) return fail(-1, "streaming: null input");
   Geo g; if (int r = g.init(cfg)) return r;
   return step_common(cfg, params, window, basis, synthesis, state, ids, n, x, hops, -1, y, hops*g.hop, amp,
                      workspace, workspace_bytes, (hipStream_t)stream);
@@ -627,18 +617,18 @@ int brv_dccrn_stream_tail(const brv_dccrn_stream_config* cfg, const float* param
                           int64_t workspace_bytes, const brv_launch_opts* opts, brv_stream_t stream) {
   (void)opts;
   Geo g; if (int e = g.init(cfg)) return e;
-  if (r < 0 || r >= g.hop) return failD(-1, "streaming: the rest must be shorter than one hop");
-  if (r > 0 && !rest) return failD(-1, "streaming: null rest");
-  if (n < 1) return failD(-1, "streaming: n must be >= 1");
+  if (r < 0 || r >= g.hop) return fail(-1, "streaming: the rest must be shorter than one hop");
+  if (r > 0 && !rest) return fail(-1, "streaming: null rest");
+  if (n < 1) return fail(-1, "streaming: n must be >= 1");
   const long long hops = g.lagh + (r > 0 ? 1 : 0);
   WsD w; w.init(g, n*hops, (int)hops);
-  if (!workspace || workspace_bytes < w.total*4) return failD(-1, "streaming: workspace too small");
+  if (!workspace || workspace_bytes < w.total*4) return fail(-1, "streaming: workspace too small");
   hipStream_t st = (hipStream_t)stream;
   float* xin = (float*)workspace + w.xin;
   const long long per = hops*g.hop;
   hipLaunchKernelGGL(tail_input_kernel, dim3(blocks_for(per), (unsigned)n), dim3(256), 0, st, rest, (long long)r,
                      xin, per);
-  HIP_OKD(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return step_common(cfg, params, window, basis, synthesis, state, ids, n, nullptr, hops, r, y,
                      (long long)g.lagh*g.hop + r, amp, workspace, workspace_bytes, st);
 }

@@ -9,21 +9,13 @@
 
 #include "../../include/brever_hip.h"
 #include "common.cuh"
+#include "status.h"
 
 using namespace brv;
 
 namespace {
 
-#define FF_OK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return (int)e_; } while (0)
-
-dim3 flat_grid(long long n) {
-  long long g = (n + 255)/256;
-  if (g < 1) g = 1;
-  if (g > 4096) g = 4096;
-  return dim3((unsigned)g);
-}
-#define GRID_STRIDE(i, n) \
-  for (long long i = (long long)blockIdx.x*256 + threadIdx.x; i < (n); i += (long long)gridDim.x*256)
+constexpr long long kGridCap = 4096;      // workgroups per launch of this file (flat_grid, status.h)
 
 // out[b][i] = mean_c |spec[b][c][i]|^2                      (features.py:186-188)
 __global__ __launch_bounds__(256) void fbe_power_kernel(const float2* spec, float* out, int C,
@@ -245,122 +237,122 @@ __global__ __launch_bounds__(256) void masked_mean_spec_kernel(const float2* spe
 extern "C" {
 
 int brv_fbe_power(const float* spec, float* out, int64_t B, int64_t C, int64_t n, brv_stream_t stream) {
-  if (B < 1 || C < 1 || n < 1) return -1;
-  hipLaunchKernelGGL(fbe_power_kernel, flat_grid(B*n), dim3(256), 0, (hipStream_t)stream,
+  BRV_REFUSE(B < 1 || C < 1 || n < 1, "requires B >= 1, C >= 1, n >= 1");
+  hipLaunchKernelGGL(fbe_power_kernel, flat_grid(B*n, kGridCap), dim3(256), 0, (hipStream_t)stream,
                      (const float2*)spec, out, (int)C, (long long)n, (long long)(B*n));
-  FF_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 int brv_compress(const float* x, float* out, int64_t n, int mode, float eps, brv_stream_t stream) {
-  if (n < 1 || mode < 0 || mode > 3) return -1;
-  hipLaunchKernelGGL(compress_kernel, flat_grid(n), dim3(256), 0, (hipStream_t)stream, x, out,
+  BRV_REFUSE(n < 1 || mode < 0 || mode > 3, "requires n >= 1, mode >= 0, mode <= 3");
+  hipLaunchKernelGGL(compress_kernel, flat_grid(n, kGridCap), dim3(256), 0, (hipStream_t)stream, x, out,
                      (long long)n, mode, eps);
-  FF_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 int brv_binaural(const float* spec, float* out, int64_t B, int64_t n, int mode, float eps,
                  brv_stream_t stream) {
-  if (B < 1 || n < 1 || mode < 0 || mode > 1) return -1;
-  hipLaunchKernelGGL(binaural_kernel, flat_grid(B*n), dim3(256), 0, (hipStream_t)stream,
+  BRV_REFUSE(B < 1 || n < 1 || mode < 0 || mode > 1, "requires B >= 1, n >= 1, mode >= 0, mode <= 1");
+  hipLaunchKernelGGL(binaural_kernel, flat_grid(B*n, kGridCap), dim3(256), 0, (hipStream_t)stream,
                      (const float2*)spec, out, (long long)n, (long long)(B*n), mode, eps);
-  FF_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 int brv_interaural_coherence(const float* spec, float* out, int64_t B, int64_t bins, int64_t F,
                              float alpha, brv_stream_t stream) {
-  if (B < 1 || bins < 1 || F < 1) return -1;
-  hipLaunchKernelGGL(ic_kernel, flat_grid(B*bins), dim3(256), 0, (hipStream_t)stream,
+  BRV_REFUSE(B < 1 || bins < 1 || F < 1, "requires B >= 1, bins >= 1, F >= 1");
+  hipLaunchKernelGGL(ic_kernel, flat_grid(B*bins, kGridCap), dim3(256), 0, (hipStream_t)stream,
                      (const float2*)spec, out, (int)bins, (int)F, (long long)(B*bins), alpha);
-  FF_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 int brv_col_normalize(float* x, int64_t B, int64_t M, int64_t T, float eps, brv_stream_t stream) {
-  if (B < 1 || M < 1 || T < 1) return -1;
-  hipLaunchKernelGGL(col_normalize_kernel, flat_grid(B*T), dim3(256), 0, (hipStream_t)stream, x,
+  BRV_REFUSE(B < 1 || M < 1 || T < 1, "requires B >= 1, M >= 1, T >= 1");
+  hipLaunchKernelGGL(col_normalize_kernel, flat_grid(B*T, kGridCap), dim3(256), 0, (hipStream_t)stream, x,
                      (int)M, (int)T, (long long)(B*T), eps);
-  FF_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 int brv_deltas(const float* x, float* out, int64_t B, int64_t M, int64_t T, brv_stream_t stream) {
-  if (B < 1 || M < 1 || T < 1) return -1;
-  hipLaunchKernelGGL(deltas_kernel, flat_grid(B*M*T), dim3(256), 0, (hipStream_t)stream, x, out,
+  BRV_REFUSE(B < 1 || M < 1 || T < 1, "requires B >= 1, M >= 1, T >= 1");
+  hipLaunchKernelGGL(deltas_kernel, flat_grid(B*M*T, kGridCap), dim3(256), 0, (hipStream_t)stream, x, out,
                      (int)M, (int)T, (long long)(B*M*T));
-  FF_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 int brv_irm(const float* fg, const float* bg, float* out, int64_t n, float eps, brv_stream_t stream) {
-  if (n < 1) return -1;
-  hipLaunchKernelGGL(irm_kernel, flat_grid(n), dim3(256), 0, (hipStream_t)stream, fg, bg, out,
+  BRV_REFUSE(n < 1, "requires n >= 1");
+  hipLaunchKernelGGL(irm_kernel, flat_grid(n, kGridCap), dim3(256), 0, (hipStream_t)stream, fg, bg, out,
                      (long long)n, eps);
-  FF_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 int brv_stack_frames(const float* x, float* out, int64_t B, int64_t nf, int64_t T, int64_t stacks,
                      brv_stream_t stream) {
-  if (B < 1 || nf < 1 || T < 1 || stacks < 0) return -1;
+  BRV_REFUSE(B < 1 || nf < 1 || T < 1 || stacks < 0, "requires B >= 1, nf >= 1, T >= 1, stacks >= 0");
   const long long total = B*(stacks + 1)*nf*T;
-  hipLaunchKernelGGL(stack_kernel, flat_grid(total), dim3(256), 0, (hipStream_t)stream, x, out,
+  hipLaunchKernelGGL(stack_kernel, flat_grid(total, kGridCap), dim3(256), 0, (hipStream_t)stream, x, out,
                      (int)nf, (int)T, (int)stacks, total);
-  FF_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 int brv_static_norm(const float* x, const float* mean, const float* stdv, float* out, int64_t B,
                     int64_t rows, int64_t T, brv_stream_t stream) {
-  if (B < 1 || rows < 1 || T < 1) return -1;
+  BRV_REFUSE(B < 1 || rows < 1 || T < 1, "requires B >= 1, rows >= 1, T >= 1");
   const long long total = B*rows*T;
-  hipLaunchKernelGGL(static_norm_kernel, flat_grid(total), dim3(256), 0, (hipStream_t)stream, x,
+  hipLaunchKernelGGL(static_norm_kernel, flat_grid(total, kGridCap), dim3(256), 0, (hipStream_t)stream, x,
                      mean, stdv, out, (int)rows, (int)T, total);
-  FF_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 int brv_cumulative_norm(const float* x, float* out, int64_t nrows, int64_t T, float eps,
                         brv_stream_t stream) {
-  if (nrows < 1 || T < 1) return -1;
-  hipLaunchKernelGGL(cumulative_norm_kernel, flat_grid(nrows), dim3(256), 0, (hipStream_t)stream,
+  BRV_REFUSE(nrows < 1 || T < 1, "requires nrows >= 1, T >= 1");
+  hipLaunchKernelGGL(cumulative_norm_kernel, flat_grid(nrows, kGridCap), dim3(256), 0, (hipStream_t)stream,
                      x, out, (int)T, (long long)nrows, eps);
-  FF_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 int brv_relu_dropout_forward(const float* x, const float* mask, float* out, int64_t n, float scale,
                              brv_stream_t stream) {
-  if (n < 1) return -1;
-  hipLaunchKernelGGL(relu_dropout_fwd_kernel, flat_grid(n), dim3(256), 0, (hipStream_t)stream, x,
+  BRV_REFUSE(n < 1, "requires n >= 1");
+  hipLaunchKernelGGL(relu_dropout_fwd_kernel, flat_grid(n, kGridCap), dim3(256), 0, (hipStream_t)stream, x,
                      mask, out, (long long)n, scale);
-  FF_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 int brv_relu_dropout_backward(const float* x, const float* mask, const float* dy, float* dx,
                               int64_t n, float scale, brv_stream_t stream) {
-  if (n < 1) return -1;
-  hipLaunchKernelGGL(relu_dropout_bwd_kernel, flat_grid(n), dim3(256), 0, (hipStream_t)stream, x,
+  BRV_REFUSE(n < 1, "requires n >= 1");
+  hipLaunchKernelGGL(relu_dropout_bwd_kernel, flat_grid(n, kGridCap), dim3(256), 0, (hipStream_t)stream, x,
                      mask, dy, dx, (long long)n, scale);
-  FF_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 int brv_dropout_apply(const float* x, const float* mask, float* out, int64_t n, float scale,
                       brv_stream_t stream) {
-  if (n < 1 || !mask) return -1;
-  hipLaunchKernelGGL(dropout_apply_kernel, flat_grid(n), dim3(256), 0, (hipStream_t)stream, x, mask,
+  BRV_REFUSE(n < 1 || !mask, "requires n >= 1, mask != NULL");
+  hipLaunchKernelGGL(dropout_apply_kernel, flat_grid(n, kGridCap), dim3(256), 0, (hipStream_t)stream, x, mask,
                      out, (long long)n, scale);
-  FF_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 int brv_sigmoid_forward(const float* x, float* out, int64_t n, brv_stream_t stream) {
-  if (n < 1) return -1;
-  hipLaunchKernelGGL(sigmoid_fwd_kernel, flat_grid(n), dim3(256), 0, (hipStream_t)stream, x, out,
+  BRV_REFUSE(n < 1, "requires n >= 1");
+  hipLaunchKernelGGL(sigmoid_fwd_kernel, flat_grid(n, kGridCap), dim3(256), 0, (hipStream_t)stream, x, out,
                      (long long)n);
-  FF_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 int brv_sigmoid_backward(const float* y, const float* dy, float* dx, int64_t n, brv_stream_t stream) {
-  if (n < 1) return -1;
-  hipLaunchKernelGGL(sigmoid_bwd_kernel, flat_grid(n), dim3(256), 0, (hipStream_t)stream, y, dy,
+  BRV_REFUSE(n < 1, "requires n >= 1");
+  hipLaunchKernelGGL(sigmoid_bwd_kernel, flat_grid(n, kGridCap), dim3(256), 0, (hipStream_t)stream, y, dy,
                      dx, (long long)n);
-  FF_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 int brv_row_sum(const float* x, float* out, int64_t B, int64_t M, int64_t T, brv_stream_t stream) {
-  if (B < 1 || M < 1 || T < 1) return -1;
+  BRV_REFUSE(B < 1 || M < 1 || T < 1, "requires B >= 1, M >= 1, T >= 1");
   hipStream_t st = (hipStream_t)stream;
   long long slices = (B*T + 16383)/16384;
   if (slices > 64) slices = 64;
@@ -369,13 +361,13 @@ int brv_row_sum(const float* x, float* out, int64_t B, int64_t M, int64_t T, brv
     if (pieces > 4) pieces = 4;
     const long long sl = B*pieces;
     double* part = nullptr;
-    FF_OK(hipMallocAsync((void**)&part, (size_t)M*sl*sizeof(double), st));
+    BRV_HIP_OK(hipMallocAsync((void**)&part, (size_t)M*sl*sizeof(double), st));
     hipLaunchKernelGGL(row_sum4_kernel, dim3((unsigned)M, (unsigned)sl), dim3(256), 0, st, x, part, (int)M,
                        (long long)T, (int)pieces);
     hipLaunchKernelGGL(row_sum_final_kernel, dim3((unsigned)((M + 255)/256)), dim3(256), 0, st, part,
                        out, (int)M, (int)sl);
-    FF_OK(hipFreeAsync(part, st));
-    FF_OK(hipGetLastError());
+    BRV_HIP_OK(hipFreeAsync(part, st));
+    BRV_HIP_OK(hipGetLastError());
     return 0;
   }
   if (slices <= 1) {
@@ -383,22 +375,22 @@ int brv_row_sum(const float* x, float* out, int64_t B, int64_t M, int64_t T, brv
                        (double*)nullptr, (int)B, (int)M, (int)T);
   } else {
     double* part = nullptr;
-    FF_OK(hipMallocAsync((void**)&part, (size_t)M*slices*sizeof(double), st));
+    BRV_HIP_OK(hipMallocAsync((void**)&part, (size_t)M*slices*sizeof(double), st));
     hipLaunchKernelGGL(row_sum_kernel, dim3((unsigned)M, (unsigned)slices), dim3(256), 0, st, x, out,
                        part, (int)B, (int)M, (int)T);
     hipLaunchKernelGGL(row_sum_final_kernel, dim3((unsigned)((M + 255)/256)), dim3(256), 0, st, part,
                        out, (int)M, (int)slices);
-    FF_OK(hipFreeAsync(part, st));
+    BRV_HIP_OK(hipFreeAsync(part, st));
   }
-  FF_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 int brv_masked_mean_spec(const float* spec, const float* mask, float* out, int64_t B, int64_t C,
                          int64_t n, brv_stream_t stream) {
-  if (B < 1 || C < 1 || n < 1) return -1;
-  hipLaunchKernelGGL(masked_mean_spec_kernel, flat_grid(B*n), dim3(256), 0, (hipStream_t)stream,
+  BRV_REFUSE(B < 1 || C < 1 || n < 1, "requires B >= 1, C >= 1, n >= 1");
+  hipLaunchKernelGGL(masked_mean_spec_kernel, flat_grid(B*n, kGridCap), dim3(256), 0, (hipStream_t)stream,
                      (const float2*)spec, mask, (float2*)out, (int)C, (long long)n, (long long)(B*n));
-  FF_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 

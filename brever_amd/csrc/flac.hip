@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/brever_hip.h"
+#include "status.h"
 
 namespace {
 
@@ -185,16 +186,19 @@ int decode_subframe(BitReader& br, int64_t* out, int blocksize, int bps, std::ve
   return br.fail ? -26 : 0;
 }
 
+// the decoder's own negative codes (-10 ... -51, one per check above and below) name the damaged field
+int malformed(int64_t code) { return brv::fail((int)code, "malformed FLAC stream: decoder code " + std::to_string(code)); }
+
 }  // namespace
 
 extern "C" {
 
 int brv_flac_info(const uint8_t* data, int64_t size, int64_t* frames, int32_t* sample_rate,
                   int32_t* channels, int32_t* bits_per_sample) {
-  if (!data || size < 0) return -1;
+  BRV_REFUSE(!data || size < 0, "requires data != NULL, size >= 0");
   StreamInfo si;
   const int64_t off = parse_metadata(data, (size_t)size, si);
-  if (off < 0) return (int)off;
+  if (off < 0) return malformed(off);
   if (frames) *frames = si.total;
   if (sample_rate) *sample_rate = si.rate;
   if (channels) *channels = si.channels;
@@ -202,8 +206,7 @@ int brv_flac_info(const uint8_t* data, int64_t size, int64_t* frames, int32_t* s
   return 0;
 }
 
-int64_t brv_flac_decode(const uint8_t* data, int64_t size, float* out, int64_t capacity_frames) {
-  if (!data || !out || size < 0) return -1;
+static int64_t decode_frames(const uint8_t* data, int64_t size, float* out, int64_t capacity_frames) {
   StreamInfo si;
   int64_t off = parse_metadata(data, (size_t)size, si);
   if (off < 0) return off;
@@ -277,6 +280,11 @@ int64_t brv_flac_decode(const uint8_t* data, int64_t size, float* out, int64_t c
   if (si.total > 0 && done > si.total) done = si.total;
   return done;
 }
+int64_t brv_flac_decode(const uint8_t* data, int64_t size, float* out, int64_t capacity_frames) {
+  BRV_REFUSE(!data || !out || size < 0, "requires data != NULL, out != NULL, size >= 0");
+  const int64_t r = decode_frames(data, size, out, capacity_frames);
+  return r < 0 ? malformed(r) : r;
+}
 
 }  // extern "C"
 
@@ -313,7 +321,8 @@ inline uint64_t rice_bits(const int64_t* r, int count, int k) {
 
 extern "C" int64_t brv_flac_encode16(const int16_t* pcm, int64_t frames, int32_t sample_rate, uint8_t* out,
                                      int64_t capacity) {
-  if (!pcm || frames < 0 || sample_rate <= 0 || sample_rate >= (1 << 20)) return -1;
+  BRV_REFUSE(!pcm || frames < 0 || sample_rate <= 0 || sample_rate >= (1 << 20),
+             "requires pcm != NULL, frames >= 0, 0 < sample_rate < 2^20");
   const int BS = 4096;
   std::vector<uint8_t> buf;
   buf.reserve((size_t)frames*2 + 1024);
@@ -421,7 +430,8 @@ extern "C" int64_t brv_flac_encode16(const int16_t* pcm, int64_t frames, int32_t
     buf.push_back((uint8_t)(c16 >> 8)); buf.push_back((uint8_t)(c16 & 0xff));
   }
   if (out == nullptr) return (int64_t)buf.size();          // size query
-  if ((int64_t)buf.size() > capacity) return -2;
+  BRV_UNSUPPORTED((int64_t)buf.size() > capacity,
+                  "capacity is smaller than the encoded stream (out == NULL queries its size)");
   memcpy(out, buf.data(), buf.size());
   return (int64_t)buf.size();
 }

@@ -30,6 +30,7 @@
 #include <stdint.h>
 
 #include "common.cuh"
+#include "status.h"
 #include "gemm_f32_big.h"
 
 // Compile-time ablations of tools/gemm_f32_bench.py (bit mask): 1 no MFMA, 2 no global loads,
@@ -687,7 +688,7 @@ long long gemm_f32_big_scratch(const BigGemm& g) {
 }
 
 int gemm_f32_big(const BigGemm& g_in, hipStream_t st) {
-  if (!gemm_f32_big_ok(g_in)) return -1;
+  BRV_REFUSE(!gemm_f32_big_ok(g_in), "the product does not fit the large fp32 kernel: gemm_f32_big_ok");
   BigDev p;
   p.g = g_in;
   if (!p.g.D2 || p.g.n_split > 0) { p.g.m_split = p.g.M; if (!p.g.D2) { p.g.D2 = p.g.D; p.g.add2 = p.g.add; } }
@@ -733,7 +734,8 @@ int gemm_f32_big(const BigGemm& g_in, hipStream_t st) {
     const long long n = (long long)p.g.batch*p.g.M*p.g.N;
     hipLaunchKernelGGL(gemm_f32_big_reduce_kernel, dim3((unsigned)((n + 63)/64)), dim3(256), 0, st, p);
   }
-  return (int)hipGetLastError();
+  BRV_HIP_OK(hipGetLastError());
+  return 0;
 }
 
 }  // namespace brv

@@ -25,6 +25,7 @@
 
 #include "../../include/brever_hip.h"
 #include "common.cuh"
+#include "status.h"
 
 namespace {
 
@@ -677,7 +678,8 @@ int brv_lstm_tile_forward(const float* gates_in, const float* w_hh, const float*
                           float* act, float* cs, int64_t B, int64_t T, int64_t H, int64_t groups,
                           int64_t reverse_mask, int64_t y_ld, int64_t y_group_offset, int lowp,
                           brv_stream_t stream) {
-  if (H != LH || B < 1 || T < 1 || groups < 1 || groups > 30 || B % groups) return -1;
+  BRV_REFUSE(H != LH || B < 1 || T < 1 || groups < 1 || groups > 30 || B % groups,
+             "requires H == 128, B >= 1, T >= 1, groups >= 1, groups <= 30, B a multiple of groups");
   const int per_group = (int)(B/groups);
   const unsigned grid = (unsigned)(groups*((per_group + LC - 1)/LC));
   if (q4_pays(B, groups) && lowp) {
@@ -688,7 +690,8 @@ int brv_lstm_tile_forward(const float* gates_in, const float* w_hh, const float*
     else
       hipLaunchKernelGGL(lstm_q4_fwd_kernel<false>, dim3(g4), dim3(512), 0, (hipStream_t)stream, gates_in, w_hh, bias,
                          y, act, cs, per_group, (int)T, (int)reverse_mask, (long long)y_ld, (long long)y_group_offset);
-    return (int)hipGetLastError();
+    BRV_HIP_OK(hipGetLastError());
+    return 0;
   }
   if (lowp == 2)
     hipLaunchKernelGGL(lstm_tile_fwd_bf16_kernel<true>, dim3(grid), dim3(512), 0, (hipStream_t)stream,
@@ -702,14 +705,16 @@ int brv_lstm_tile_forward(const float* gates_in, const float* w_hh, const float*
   hipLaunchKernelGGL(lstm_tile_fwd_kernel, dim3(grid), dim3(512), 0, (hipStream_t)stream, gates_in,
                      w_hh, bias, y, act, cs, per_group, (int)T, (int)reverse_mask, (long long)y_ld,
                      (long long)y_group_offset);
-  return (int)hipGetLastError();
+  BRV_HIP_OK(hipGetLastError());
+  return 0;
 }
 
 int brv_lstm_tile_backward(const float* act, const float* cs, const float* w_hh, const float* dy,
                            float* dgates, int64_t B, int64_t T, int64_t H, int64_t groups,
                            int64_t reverse_mask, int64_t dy_ld, int64_t dy_group_offset, int lowp,
                            brv_stream_t stream) {
-  if (H != LH || B < 1 || T < 1 || groups < 1 || groups > 30 || B % groups) return -1;
+  BRV_REFUSE(H != LH || B < 1 || T < 1 || groups < 1 || groups > 30 || B % groups,
+             "requires H == 128, B >= 1, T >= 1, groups >= 1, groups <= 30, B a multiple of groups");
   const int per_group = (int)(B/groups);
   const unsigned grid = (unsigned)(groups*((per_group + LC - 1)/LC));
   if (q4_pays(B, groups) && lowp) {
@@ -720,7 +725,8 @@ int brv_lstm_tile_backward(const float* act, const float* cs, const float* w_hh,
     else
       hipLaunchKernelGGL(lstm_q4_bwd_kernel<false>, dim3(g4), dim3(512), 0, (hipStream_t)stream, act, cs, w_hh, dy,
                          dgates, per_group, (int)T, (int)reverse_mask, (long long)dy_ld, (long long)dy_group_offset);
-    return (int)hipGetLastError();
+    BRV_HIP_OK(hipGetLastError());
+    return 0;
   }
   if (lowp == 2)
     hipLaunchKernelGGL(lstm_tile_bwd_bf16_kernel<true>, dim3(grid), dim3(512), 0, (hipStream_t)stream,
@@ -734,7 +740,8 @@ int brv_lstm_tile_backward(const float* act, const float* cs, const float* w_hh,
   hipLaunchKernelGGL(lstm_tile_bwd_kernel, dim3(grid), dim3(512), 0, (hipStream_t)stream, act, cs,
                      w_hh, dy, dgates, per_group, (int)T, (int)reverse_mask, (long long)dy_ld,
                      (long long)dy_group_offset);
-  return (int)hipGetLastError();
+  BRV_HIP_OK(hipGetLastError());
+  return 0;
 }
 
 }  // extern "C"

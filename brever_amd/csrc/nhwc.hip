@@ -9,12 +9,12 @@
 
 #include "../../include/brever_hip.h"
 #include "common.cuh"
+#include "status.h"
 
 using namespace brv;
 
 namespace {
 
-#define NH_OK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return (int)e_; } while (0)
 
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef float f32x8 __attribute__((ext_vector_type(8)));
@@ -918,25 +918,28 @@ extern "C" {
 
 int brv_nchw_to_nhwc_f16(const float* x, void* y, int64_t B, int64_t C, int64_t Cs, int64_t HW,
                          brv_stream_t stream) {
-  if (B < 1 || C < 1 || Cs < C || (Cs & 7) || HW < 1) return -1;
+  BRV_REFUSE(B < 1 || C < 1 || Cs < C || (Cs & 7) || HW < 1,
+             "requires B >= 1, C >= 1, Cs >= C, Cs a multiple of 8, HW >= 1");
   hipLaunchKernelGGL(nchw_to_nhwc_kernel, dim3((unsigned)((HW + 255)/256), (unsigned)(Cs/8), (unsigned)B),
                      dim3(256), 0, (hipStream_t)stream, x, (_Float16*)y, (int)C, (int)Cs, (long long)HW);
-  NH_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 
 int brv_nhwc_f16_to_nchw(const void* x, float* y, int64_t B, int64_t C, int64_t Cs, int64_t HW,
                          brv_stream_t stream) {
-  if (B < 1 || C < 1 || Cs < C || (Cs & 7) || HW < 1) return -1;
+  BRV_REFUSE(B < 1 || C < 1 || Cs < C || (Cs & 7) || HW < 1,
+             "requires B >= 1, C >= 1, Cs >= C, Cs a multiple of 8, HW >= 1");
   hipLaunchKernelGGL(nhwc_to_nchw_kernel, dim3((unsigned)((HW + 255)/256), (unsigned)((C + 7)/8), (unsigned)B),
                      dim3(256), 0, (hipStream_t)stream, (const _Float16*)x, y, (int)C, (int)Cs, (long long)HW);
-  NH_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 
 int brv_nhwc_chan_stats(const void* x, double* sums, int64_t B, int64_t C, int64_t Cs, int64_t HW,
                         int64_t c_off, int64_t Ctot, brv_stream_t stream) {
-  if (B < 1 || C < 1 || Cs < C || (Cs & 7) || Cs > 2048 || HW < 1 || c_off < 0 || c_off + C > Ctot) return -1;
+  BRV_REFUSE(B < 1 || C < 1 || Cs < C || (Cs & 7) || Cs > 2048 || HW < 1 || c_off < 0 || c_off + C > Ctot,
+             "requires B >= 1, C >= 1, Cs >= C, Cs a multiple of 8, Cs <= 2048, HW >= 1, c_off >= 0, c_off + C <= Ctot");
   const int oct = (int)(Cs/8), lanes = 256/oct;
   long long slice = (long long)lanes*64;            // <= 64 pixels per thread
   const long long min_slice = (HW + 1023)/1024;     // <= 1024 workgroups per item
@@ -945,7 +948,7 @@ int brv_nhwc_chan_stats(const void* x, double* sums, int64_t B, int64_t C, int64
   hipLaunchKernelGGL(chan_stats_kernel, dim3(ns, (unsigned)B), dim3(256), 0, (hipStream_t)stream,
                      (const _Float16*)x, sums, (int)C, (int)Cs, (long long)HW, (int)c_off, (int)Ctot,
                      slice);
-  NH_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 
@@ -953,11 +956,12 @@ int brv_groupnorm_fold_chan(const double* sums, const float* add_bc, const float
                             const float* beta, const float* adm_scale, const float* adm_shift,
                             float* scale_bc, float* shift_bc, int64_t B, int64_t C, int64_t HW,
                             int64_t groups, float eps, brv_stream_t stream) {
-  if (B < 1 || C < 1 || groups < 1 || C % groups || HW < 1) return -1;
+  BRV_REFUSE(B < 1 || C < 1 || groups < 1 || C % groups || HW < 1,
+             "requires B >= 1, C >= 1, groups >= 1, C a multiple of groups, HW >= 1");
   hipLaunchKernelGGL(chan_fold_kernel, dim3((unsigned)(B*groups)), dim3(64), 0, (hipStream_t)stream,
                      sums, (const double*)nullptr, (int)C, add_bc, gamma, beta, adm_scale, adm_shift,
                      scale_bc, shift_bc, (int)C, (long long)HW, (int)groups, eps);
-  NH_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 
@@ -967,28 +971,31 @@ int brv_groupnorm_fold_chan2(const double* sums1, int64_t C1, const double* sums
                              float* shift_bc, int64_t B, int64_t HW, int64_t groups, float eps,
                              brv_stream_t stream) {
   const int64_t C = C1 + (sums2 ? C2 : 0);
-  if (B < 1 || C1 < 1 || groups < 1 || C % groups || HW < 1) return -1;
+  BRV_REFUSE(B < 1 || C1 < 1 || groups < 1 || C % groups || HW < 1,
+             "requires B >= 1, C1 >= 1, groups >= 1, C a multiple of groups, HW >= 1");
   hipLaunchKernelGGL(chan_fold_kernel, dim3((unsigned)(B*groups)), dim3(64), 0, (hipStream_t)stream,
                      sums1, sums2, (int)C1, add_bc, gamma, beta, adm_scale, adm_shift, scale_bc,
                      shift_bc, (int)C, (long long)HW, (int)groups, eps);
-  NH_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 
 int brv_nhwc_affine_act(const void* x, const float* scale_bc, const float* shift_bc, void* y,
                         int64_t B, int64_t C, int64_t Cs, int64_t HW, int act, brv_stream_t stream) {
-  if (B < 1 || C < 1 || Cs < C || (Cs & 7) || HW < 1) return -1;
+  BRV_REFUSE(B < 1 || C < 1 || Cs < C || (Cs & 7) || HW < 1,
+             "requires B >= 1, C >= 1, Cs >= C, Cs a multiple of 8, HW >= 1");
   hipLaunchKernelGGL(nhwc_affine_act_kernel, nh_grid(HW*(Cs/8), B), dim3(256), 0, (hipStream_t)stream,
                      (const _Float16*)x, scale_bc, shift_bc, (_Float16*)y, (int)C, (int)Cs,
                      (long long)HW, act);
-  NH_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 
 int brv_nhwc_fir_resample2d(const void* x, const float* kernel, void* y, int64_t B, int64_t Cs,
                             int64_t H, int64_t W, int64_t Ho, int64_t Wo, int64_t K, int64_t pad_h,
                             int64_t pad_w, int up, float gain, brv_stream_t stream) {
-  if (B < 1 || (Cs & 7) || Cs < 8 || H < 1 || W < 1 || Ho < 1 || Wo < 1 || K < 1) return -1;
+  BRV_REFUSE(B < 1 || (Cs & 7) || Cs < 8 || H < 1 || W < 1 || Ho < 1 || Wo < 1 || K < 1,
+             "requires B >= 1, Cs a multiple of 8, Cs >= 8, H >= 1, W >= 1, Ho >= 1, Wo >= 1, K >= 1");
   const dim3 grid = nh_grid(Ho*Wo*(Cs/8), B);
   if (up)
     hipLaunchKernelGGL(nhwc_fir_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream,
@@ -998,7 +1005,7 @@ int brv_nhwc_fir_resample2d(const void* x, const float* kernel, void* y, int64_t
     hipLaunchKernelGGL(nhwc_fir_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream,
                        (const _Float16*)x, kernel, (_Float16*)y, (int)Cs, (int)H, (int)W, (int)Ho,
                        (int)Wo, (int)K, (int)pad_h, (int)pad_w, gain);
-  NH_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 
@@ -1006,9 +1013,9 @@ int brv_nhwc_fir_resample2d_dual(const void* x, const float* scale_bc, const flo
                                  const float* kernel, void* y_raw, void* y_act, int64_t B, int64_t C,
                                  int64_t Cs, int64_t H, int64_t W, int64_t Ho, int64_t Wo, int64_t K,
                                  int64_t pad_h, int64_t pad_w, int up, float gain, brv_stream_t stream) {
-  if (B < 1 || (Cs & 7) || Cs < 8 || C < 1 || C > Cs || H < 1 || W < 1 || Ho < 1 || Wo < 1 || K < 1 ||
-      K > 4 || B > 65535 || !scale_bc || !shift_bc)
-    return -1;
+  BRV_REFUSE(B < 1 || (Cs & 7) || Cs < 8 || C < 1 || C > Cs || H < 1 || W < 1 || Ho < 1 || Wo < 1 || K < 1 ||
+             K > 4 || B > 65535 || !scale_bc || !shift_bc,
+             "requires 1 <= B <= 65535, Cs a multiple of 8, 1 <= C <= Cs, H, W, Ho, Wo >= 1, 1 <= K <= 4, scale_bc and shift_bc != NULL");
   FirDualParams p;
   p.x = (const _Float16*)x; p.scale = scale_bc; p.shift = shift_bc; p.k = kernel;
   p.y_raw = (_Float16*)y_raw; p.y_act = (_Float16*)y_act;
@@ -1019,44 +1026,45 @@ int brv_nhwc_fir_resample2d_dual(const void* x, const float* scale_bc, const flo
   const dim3 grid((unsigned)(p.tiles_w*((Ho + TH - 1)/TH)), (unsigned)((Cs/8 + 3)/4), (unsigned)B);
   if (up) hipLaunchKernelGGL(nhwc_fir_dual_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, p);
   else hipLaunchKernelGGL(nhwc_fir_dual_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, p);
-  NH_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 
 int brv_nhwc_axpby(const void* a, float alpha, const void* b, float beta, void* out, int64_t n,
                    brv_stream_t stream) {
-  if (n < 0 || (n & 7)) return -1;
+  BRV_REFUSE(n < 0 || (n & 7), "requires n >= 0, n a multiple of 8");
   if (n == 0) return 0;
   hipLaunchKernelGGL(nhwc_axpby_kernel, nh_grid(n/8, 1), dim3(256), 0, (hipStream_t)stream,
                      (const _Float16*)a, alpha, (const _Float16*)b, beta, (_Float16*)out,
                      (long long)(n/8));
-  NH_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 
 int64_t brv_nhwc_conv1x1_packed_size(int64_t Cout, int64_t C1, int64_t C2) {
-  if (Cout < 1 || C1 < 1 || C2 < 0) return -1;
+  BRV_REFUSE(Cout < 1 || C1 < 1 || C2 < 0, "requires Cout >= 1, C1 >= 1, C2 >= 0");
   return ((Cout + 127)/128)*128*(((C1 + 15)/16) + ((C2 + 15)/16))*16;
 }
 
 int brv_nhwc_conv1x1_pack(const float* w, void* wp, int64_t Cout, int64_t C1, int64_t C2,
                           brv_stream_t stream) {
   const int64_t total = brv_nhwc_conv1x1_packed_size(Cout, C1, C2);
-  if (total < 0) return -1;
+  BRV_REFUSE(total < 0, "the packed size overflows");
   long long g = (total + 255)/256;
   if (g > 4096) g = 4096;
   const int n_ks1 = (int)((C1 + 15)/16), n_ks = n_ks1 + (int)((C2 + 15)/16);
   hipLaunchKernelGGL(conv1x1_pack_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, w,
                      (_Float16*)wp, (int)Cout, (int)C1, (int)C2, n_ks1, n_ks, (long long)total);
-  NH_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 
 int brv_nhwc_conv1x1_forward(const void* x1, int64_t C1, int64_t C1s, const void* x2, int64_t C2,
                              int64_t C2s, const void* wp, const float* bias, void* y, int64_t Cys,
                              int64_t npx, int64_t Cout, float out_scale, brv_stream_t stream) {
-  if (npx < 1 || C1 < 1 || Cout < 1 || (C1s & 7) || C1 > C1s || (Cys & 7) || Cout > Cys) return -1;
-  if (x2 && (C2 < 1 || (C2s & 7) || C2 > C2s)) return -1;
+  BRV_REFUSE(npx < 1 || C1 < 1 || Cout < 1 || (C1s & 7) || C1 > C1s || (Cys & 7) || Cout > Cys,
+             "requires npx >= 1, C1 >= 1, Cout >= 1, C1s a multiple of 8, C1 <= C1s, Cys a multiple of 8, Cout <= Cys");
+  BRV_REFUSE(x2 && (C2 < 1 || (C2s & 7) || C2 > C2s), "x2 requires C2 >= 1, C2s a multiple of 8, C2 <= C2s");
   Pw1Params p;
   p.x1 = (const _Float16*)x1; p.x2 = (const _Float16*)x2; p.wp = (const h8*)wp; p.bias = bias;
   p.y = (_Float16*)y; p.C1 = (int)C1; p.C1s = (int)C1s; p.C2 = x2 ? (int)C2 : 0; p.C2s = (int)C2s;
@@ -1088,15 +1096,15 @@ int brv_nhwc_conv1x1_forward(const void* x1, int64_t C1, int64_t C1s, const void
     hipLaunchKernelGGL(nhwc_conv1x1_kernel<1>, dim3((n_pt + 7)/8*8*n_cob), dim3(256), 0, (hipStream_t)stream, p);
   else
     hipLaunchKernelGGL(nhwc_conv1x1_kernel<1>, dim3(n_pt, n_cob), dim3(256), 0, (hipStream_t)stream, p);
-  NH_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 
 int brv_nhwc_conv3x3_small_pack(const float* w, void* w16, int64_t Cout, int64_t C, brv_stream_t stream) {
-  if (Cout < 1 || Cout > 8 || C < 1) return -1;
+  BRV_REFUSE(Cout < 1 || Cout > 8 || C < 1, "requires Cout >= 1, Cout <= 8, C >= 1");
   hipLaunchKernelGGL(small_pack_kernel, dim3((unsigned)((9*Cout*C + 255)/256)), dim3(256), 0,
                      (hipStream_t)stream, w, (_Float16*)w16, (int)Cout, (int)C);
-  NH_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 
@@ -1104,7 +1112,8 @@ int brv_nhwc_conv3x3_small(const void* x, const void* w16, const float* bias, co
                            const float* shift_bc, int silu, const float* y_in, float* y, int64_t B,
                            int64_t C, int64_t Cs, int64_t H, int64_t W, int64_t Cout,
                            brv_stream_t stream) {
-  if (B < 1 || C < 1 || (C & 7) || Cs < C || (Cs & 7) || H < 1 || W < 1 || Cout < 1 || Cout > 8) return -1;
+  BRV_REFUSE(B < 1 || C < 1 || (C & 7) || Cs < C || (Cs & 7) || H < 1 || W < 1 || Cout < 1 || Cout > 8,
+             "requires B >= 1, C >= 1, C a multiple of 8, Cs >= C, Cs a multiple of 8, H >= 1, W >= 1, Cout >= 1, Cout <= 8");
   SmallCoutParams p;
   p.x = (const _Float16*)x; p.w16 = (const _Float16*)w16; p.bias = bias; p.scale = scale_bc;
   p.shift = shift_bc; p.yin = y_in; p.y = y; p.C = (int)C; p.Cs = (int)Cs; p.Cout = (int)Cout;
@@ -1114,14 +1123,15 @@ int brv_nhwc_conv3x3_small(const void* x, const void* w16, const float* bias, co
     hipLaunchKernelGGL(nhwc_conv3x3_small_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, p);
   else
     hipLaunchKernelGGL(nhwc_conv3x3_small_kernel<8>, grid, dim3(256), 0, (hipStream_t)stream, p);
-  NH_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 
 int brv_nhwc_add_pointwise(const void* x, const float* aux, const float* w, const float* bias,
                            void* y, int64_t B, int64_t C, int64_t Cs, int64_t K, int64_t HW,
                            float out_scale, brv_stream_t stream) {
-  if (B < 1 || C < 1 || Cs < C || (Cs & 7) || K < 1 || K > 8 || HW < 1) return -1;
+  BRV_REFUSE(B < 1 || C < 1 || Cs < C || (Cs & 7) || K < 1 || K > 8 || HW < 1,
+             "requires B >= 1, C >= 1, Cs >= C, Cs a multiple of 8, K >= 1, K <= 8, HW >= 1");
   // (eight elements per thread: the per-thread weights and biases are loaded once for them; with one element per
   // thread -- nh_grid -- they were loaded per element)
   long long gx = (HW*(Cs/8) + 2047)/2048;
@@ -1130,7 +1140,7 @@ int brv_nhwc_add_pointwise(const void* x, const float* aux, const float* w, cons
   hipLaunchKernelGGL(nhwc_add_pointwise_kernel, dim3((unsigned)gx, (unsigned)B), dim3(256), 0, (hipStream_t)stream,
                      (const _Float16*)x, aux, w, bias, (_Float16*)y, (int)C, (int)Cs, (int)K,
                      (long long)HW, out_scale);
-  NH_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 

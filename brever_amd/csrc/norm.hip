@@ -14,12 +14,12 @@
 
 #include "../../include/brever_hip.h"
 #include "common.cuh"
+#include "status.h"
 
 using namespace brv;
 
 namespace {
 
-#define CN_OK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return (int)e_; } while (0)
 
 // out[bg][t] = (sum_r a, sum_r b) with (a, b) = (x, x^2) or (dxhat, dxhat*xhat)
 template <bool BWD>
@@ -159,7 +159,8 @@ int64_t brv_causal_groupnorm_scratch_bytes(int64_t B, int64_t groups, int64_t T)
 int brv_causal_groupnorm_forward(const float* x, const float* gain, const float* bias, float* y,
                                  float* stats, void* scratch, int64_t B, int64_t C, int64_t inner,
                                  int64_t T, int64_t groups, float eps, brv_stream_t stream) {
-  if (B < 1 || C < 1 || inner < 1 || T < 1 || groups < 1 || C % groups) return -1;
+  BRV_REFUSE(B < 1 || C < 1 || inner < 1 || T < 1 || groups < 1 || C % groups,
+             "requires B >= 1, C >= 1, inner >= 1, T >= 1, groups >= 1, C a multiple of groups");
   hipStream_t st = (hipStream_t)stream;
   const int R = (int)(C/groups*inner);
   const dim3 fgrid((unsigned)((T + 255)/256), (unsigned)(B*groups));
@@ -170,14 +171,15 @@ int brv_causal_groupnorm_forward(const float* x, const float* gain, const float*
   const long long total = B*C*inner*T;
   hipLaunchKernelGGL(cgn_apply_kernel, flat(total), dim3(256), 0, st, x, (const float2*)stats, gain,
                      bias, y, R, (int)T, (int)groups, (int)inner, total);
-  CN_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 int brv_causal_groupnorm_backward(const float* x, const float* dy, const float* gain,
                                   const float* stats, float* dx, float* dgain, float* dbias,
                                   void* scratch, float* uv_scratch, int64_t B, int64_t C,
                                   int64_t inner, int64_t T, int64_t groups, brv_stream_t stream) {
-  if (B < 1 || C < 1 || inner < 1 || T < 1 || groups < 1 || C % groups) return -1;
+  BRV_REFUSE(B < 1 || C < 1 || inner < 1 || T < 1 || groups < 1 || C % groups,
+             "requires B >= 1, C >= 1, inner >= 1, T >= 1, groups >= 1, C a multiple of groups");
   hipStream_t st = (hipStream_t)stream;
   const int R = (int)(C/groups*inner);
   const dim3 fgrid((unsigned)((T + 255)/256), (unsigned)(B*groups));
@@ -191,7 +193,7 @@ int brv_causal_groupnorm_backward(const float* x, const float* dy, const float* 
   hipLaunchKernelGGL(cgn_param_grads_kernel, dim3((unsigned)C), dim3(256), 0, st, x, dy,
                      (const float2*)stats, dgain, dbias, (int)B, (int)C, (int)groups, (int)inner,
                      (int)T);
-  CN_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 

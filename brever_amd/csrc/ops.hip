@@ -6,20 +6,11 @@
 
 #include "../../include/brever_hip.h"
 #include "misc_kernels.cuh"
+#include "status.h"
 
 using namespace brv;
 
 namespace {
-int ops_fail(int code, const char* what, hipError_t e) {
-  (void)what; (void)e;
-  return code;
-}
-#define OPS_OK(expr)                                                   \
-  do {                                                                 \
-    hipError_t e_ = (expr);                                            \
-    if (e_ != hipSuccess) return ops_fail((int)e_, #expr, e_);         \
-  } while (0)
-
 // scratch layout: mom [rows][6] f64 | cross [B][S][S] f64 | coef [rows][8] f32
 struct LossScratch {
   double* mom; double* cross; float* coef; size_t zero_bytes;
@@ -34,7 +25,7 @@ struct LossScratch {
 int moments(const float* x, const float* y, const int64_t* lengths, int64_t B, int64_t S,
             int64_t L, int64_t stride, const LossScratch& sc, hipStream_t st, int64_t ybs = -1,
             int64_t yss = -1) {
-  OPS_OK(hipMemsetAsync(sc.mom, 0, sc.zero_bytes, st));
+  BRV_HIP_OK(hipMemsetAsync(sc.mom, 0, sc.zero_bytes, st));
   MomentsParams p;
   p.x = x; p.y = y; p.stride = stride; p.L = (int)L;
   p.ybs = ybs < 0 ? S*stride : ybs; p.yss = yss < 0 ? stride : yss;
@@ -43,7 +34,7 @@ int moments(const float* x, const float* y, const int64_t* lengths, int64_t B, i
   if (gx < 1) gx = 1;
   if (gx > 256) gx = 256;
   hipLaunchKernelGGL(masked_moments_kernel, dim3(gx, (unsigned)(B*S)), dim3(256), 0, st, p);
-  OPS_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 }  // namespace
@@ -64,13 +55,13 @@ int brv_snr_forward_strided(const float* x, const float* y, int64_t y_batch_stri
                             int64_t y_source_stride, const int64_t* lengths, int64_t B, int64_t S,
                             int64_t L, int64_t stride, void* scratch, float* loss,
                             brv_stream_t stream) {
-  if (B < 1 || S < 1 || L < 1) return -1;
+  BRV_REFUSE(B < 1 || S < 1 || L < 1, "requires B >= 1, S >= 1, L >= 1");
   hipStream_t st = (hipStream_t)stream;
   LossScratch sc(scratch, B, S);
   if (int r = moments(x, y, lengths, B, S, L, stride, sc, st, y_batch_stride, y_source_stride)) return r;
   hipLaunchKernelGGL(snr_finalize_kernel, dim3((unsigned)((B + 63)/64)), dim3(64), 0, st,
                      sc.mom, (int)B, (int)S, loss, sc.coef);
-  OPS_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 
@@ -85,7 +76,7 @@ int brv_snr_backward_strided(const float* x, const float* y, int64_t y_batch_str
                              int64_t y_source_stride, const int64_t* lengths, int64_t B, int64_t S,
                              int64_t L, int64_t stride, const void* scratch, const float* gscale,
                              float* dx, brv_stream_t stream) {
-  if (B < 1 || S < 1 || L < 1) return -1;
+  BRV_REFUSE(B < 1 || S < 1 || L < 1, "requires B >= 1, S >= 1, L >= 1");
   hipStream_t st = (hipStream_t)stream;
   LossScratch sc(const_cast<void*>(scratch), B, S);
   SnrBwdParams p;
@@ -96,14 +87,14 @@ int brv_snr_backward_strided(const float* x, const float* y, int64_t y_batch_str
   if (gx < 1) gx = 1;
   if (gx > 512) gx = 512;
   hipLaunchKernelGGL(snr_bwd_kernel, dim3(gx, (unsigned)(B*S)), dim3(256), 0, st, p);
-  OPS_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 
 int brv_sisnr_forward(const float* x, const float* y, const int64_t* lengths, int64_t B,
                       int64_t S, int64_t L, int64_t stride, void* scratch, float* loss,
                       brv_stream_t stream) {
-  if (B < 1 || S < 1 || S > 4 || L < 1) return -1;
+  BRV_REFUSE(B < 1 || S < 1 || S > 4 || L < 1, "requires B >= 1, S >= 1, S <= 4, L >= 1");
   hipStream_t st = (hipStream_t)stream;
   LossScratch sc(scratch, B, S);
   if (int r = moments(x, y, lengths, B, S, L, stride, sc, st)) return r;
@@ -115,17 +106,17 @@ int brv_sisnr_forward(const float* x, const float* y, const int64_t* lengths, in
   if (gx > 256) gx = 256;
   hipLaunchKernelGGL(masked_cross_kernel, dim3(gx, (unsigned)B, (unsigned)(S*S)), dim3(256),
                      0, st, c);
-  OPS_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   hipLaunchKernelGGL(sisnr_finalize_kernel, dim3((unsigned)((B + 63)/64)), dim3(64), 0, st,
                      sc.mom, sc.cross, (int)B, (int)S, (const long long*)lengths, loss, sc.coef);
-  OPS_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 
 int brv_sisnr_backward(const float* x, const float* y, const int64_t* lengths, int64_t B,
                        int64_t S, int64_t L, int64_t stride, const void* scratch,
                        const float* gscale, float* dx, brv_stream_t stream) {
-  if (B < 1 || S < 1 || S > 4 || L < 1) return -1;
+  BRV_REFUSE(B < 1 || S < 1 || S > 4 || L < 1, "requires B >= 1, S >= 1, S <= 4, L >= 1");
   hipStream_t st = (hipStream_t)stream;
   LossScratch sc(const_cast<void*>(scratch), B, S);
   SisnrBwdParams p;
@@ -135,14 +126,14 @@ int brv_sisnr_backward(const float* x, const float* y, const int64_t* lengths, i
   if (gx < 1) gx = 1;
   if (gx > 512) gx = 512;
   hipLaunchKernelGGL(sisnr_bwd_kernel, dim3(gx, (unsigned)(B*S)), dim3(256), 0, st, p);
-  OPS_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 
 int brv_mse_backward(const float* x, const float* y, const int64_t* lengths,
                      const float* weight, int64_t B, int64_t S, int64_t L, int64_t stride,
                      const float* gscale, float* dx, brv_stream_t stream) {
-  if (B < 1 || S < 1 || L < 1) return -1;
+  BRV_REFUSE(B < 1 || S < 1 || L < 1, "requires B >= 1, S >= 1, L >= 1");
   hipStream_t st = (hipStream_t)stream;
   MseBwdParams p;
   p.x = x; p.y = y; p.dx = dx; p.stride = stride; p.L = (int)L;
@@ -151,20 +142,20 @@ int brv_mse_backward(const float* x, const float* y, const int64_t* lengths,
   if (gx < 1) gx = 1;
   if (gx > 512) gx = 512;
   hipLaunchKernelGGL(mse_bwd_kernel, dim3(gx, (unsigned)(B*S)), dim3(256), 0, st, p);
-  OPS_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 
 int brv_mse_forward(const float* x, const float* y, const int64_t* lengths,
                     const float* weight, int64_t B, int64_t S, int64_t L, int64_t stride,
                     void* scratch, float* loss, brv_stream_t stream) {
-  if (B < 1 || S < 1 || L < 1) return -1;
+  BRV_REFUSE(B < 1 || S < 1 || L < 1, "requires B >= 1, S >= 1, L >= 1");
   hipStream_t st = (hipStream_t)stream;
   LossScratch sc(scratch, B, S);
   if (int r = moments(x, y, lengths, B, S, L, stride, sc, st)) return r;
   hipLaunchKernelGGL(mse_finalize_kernel, dim3((unsigned)((B + 63)/64)), dim3(64), 0, st,
                      sc.mom, (int)B, (int)S, (const long long*)lengths, weight, loss);
-  OPS_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 
@@ -179,49 +170,49 @@ dim3 row_grid(int64_t rows, int64_t n, int per_thread) {
 
 int brv_apply_mask(const float* x, const int64_t* lengths, float* out, int64_t B, int64_t S,
                    int64_t L, brv_stream_t stream) {
-  if (B < 1 || S < 1 || L < 1) return -1;
+  BRV_REFUSE(B < 1 || S < 1 || L < 1, "requires B >= 1, S >= 1, L >= 1");
   hipLaunchKernelGGL(mask_rows_kernel, row_grid(B*S, L, 8), dim3(256), 0, (hipStream_t)stream,
                      x, (const long long*)lengths, out, (int)S, (long long)L);
-  OPS_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 
 int brv_l1_forward(const float* x, const float* y, double* sums, int64_t rows, int64_t n,
                    brv_stream_t stream) {
-  if (rows < 1 || n < 1) return -1;
+  BRV_REFUSE(rows < 1 || n < 1, "requires rows >= 1, n >= 1");
   hipStream_t st = (hipStream_t)stream;
-  OPS_OK(hipMemsetAsync(sums, 0, (size_t)rows*sizeof(double), st));
+  BRV_HIP_OK(hipMemsetAsync(sums, 0, (size_t)rows*sizeof(double), st));
   hipLaunchKernelGGL(l1_fwd_kernel, row_grid(rows, n, 16), dim3(256), 0, st, x, y, sums, (long long)n);
-  OPS_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 
 int brv_l1_backward(const float* x, const float* y, const float* grow, float* dx, int64_t rows,
                     int64_t n, int accumulate, brv_stream_t stream) {
-  if (rows < 1 || n < 1) return -1;
+  BRV_REFUSE(rows < 1 || n < 1, "requires rows >= 1, n >= 1");
   hipLaunchKernelGGL(l1_bwd_kernel, row_grid(rows, n, 8), dim3(256), 0, (hipStream_t)stream,
                      x, y, grow, dx, (long long)n, accumulate);
-  OPS_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 
 int brv_mag_l1_forward(const float* xspec, const float* yspec, double* sums, int64_t rows,
                        int64_t n, brv_stream_t stream) {
-  if (rows < 1 || n < 1) return -1;
+  BRV_REFUSE(rows < 1 || n < 1, "requires rows >= 1, n >= 1");
   hipStream_t st = (hipStream_t)stream;
-  OPS_OK(hipMemsetAsync(sums, 0, (size_t)rows*sizeof(double), st));
+  BRV_HIP_OK(hipMemsetAsync(sums, 0, (size_t)rows*sizeof(double), st));
   hipLaunchKernelGGL(mag_l1_fwd_kernel, row_grid(rows, n, 8), dim3(256), 0, st,
                      (const float2*)xspec, (const float2*)yspec, sums, (long long)n);
-  OPS_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 
 int brv_mag_l1_backward(const float* xspec, const float* yspec, const float* grow,
                         float* dxspec, int64_t rows, int64_t n, brv_stream_t stream) {
-  if (rows < 1 || n < 1) return -1;
+  BRV_REFUSE(rows < 1 || n < 1, "requires rows >= 1, n >= 1");
   hipLaunchKernelGGL(mag_l1_bwd_kernel, row_grid(rows, n, 4), dim3(256), 0, (hipStream_t)stream,
                      (const float2*)xspec, (const float2*)yspec, grow, (float2*)dxspec, (long long)n);
-  OPS_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 
@@ -229,15 +220,15 @@ int brv_clip_adam_step(float* params, float* grads, float* exp_avg, float* exp_a
                        int64_t n, float grad_scale, float max_norm, float lr, float beta1,
                        float beta2, float eps, int64_t step, void* scratch,
                        float* norm_out, brv_stream_t stream) {
-  if (n < 1 || step < 1) return -1;
+  BRV_REFUSE(n < 1 || step < 1, "requires n >= 1, step >= 1");
   hipStream_t st = (hipStream_t)stream;
   double* acc = (double*)scratch;
-  OPS_OK(hipMemsetAsync(acc, 0, sizeof(double), st));
+  BRV_HIP_OK(hipMemsetAsync(acc, 0, sizeof(double), st));
   int gx = (int)((n/4 + 255)/256);
   if (gx < 1) gx = 1;
   if (gx > 1024) gx = 1024;
   hipLaunchKernelGGL(sumsq_kernel, dim3(gx), dim3(256), 0, st, grads, (long long)n, acc);
-  OPS_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   AdamParams a;
   a.p = params; a.g = grads; a.m = exp_avg; a.v = exp_avg_sq; a.n = n;
   a.sumsq = acc; a.grad_scale = grad_scale; a.max_norm = max_norm;
@@ -248,7 +239,7 @@ int brv_clip_adam_step(float* params, float* grads, float* exp_avg, float* exp_a
   int ga = (int)((n + 255)/256);
   if (ga > 2048) ga = 2048;
   hipLaunchKernelGGL(clip_adam_kernel, dim3(ga), dim3(256), 0, st, a);
-  OPS_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 
@@ -260,7 +251,7 @@ int brv_clip_adam_step2(float* params, float* grads, float* grads2, float* exp_a
                         float* exp_avg_sq, int64_t n, float grad_scale, float max_norm, float lr,
                         float beta1, float beta2, float eps, int64_t step, void* scratch,
                         int32_t slot, float* norm_out, brv_stream_t stream) {
-  if (n < 1 || step < 1 || (slot != 0 && slot != 1)) return -1;
+  BRV_REFUSE(n < 1 || step < 1 || (slot != 0 && slot != 1), "requires n >= 1, step >= 1, slot 0 or 1");
   hipStream_t st = (hipStream_t)stream;
   double* acc = (double*)scratch + slot;
   int gx = (int)((n/4 + 255)/256);
@@ -268,7 +259,7 @@ int brv_clip_adam_step2(float* params, float* grads, float* grads2, float* exp_a
   if (gx > 1024) gx = 1024;
   if (grads2) hipLaunchKernelGGL(sum_sumsq_kernel, dim3(gx), dim3(256), 0, st, grads, grads2, (long long)n, acc);
   else hipLaunchKernelGGL(sumsq_kernel, dim3(gx), dim3(256), 0, st, grads, (long long)n, acc);
-  OPS_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   AdamParams a;
   a.p = params; a.g = grads; a.m = exp_avg; a.v = exp_avg_sq; a.n = n;
   a.sumsq = acc; a.grad_scale = grad_scale; a.max_norm = max_norm;
@@ -279,21 +270,21 @@ int brv_clip_adam_step2(float* params, float* grads, float* grads2, float* exp_a
   int ga = (int)((n + 255)/256);
   if (ga > 2048) ga = 2048;
   hipLaunchKernelGGL(clip_adam_kernel, dim3(ga), dim3(256), 0, st, a);
-  OPS_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 
 int brv_memset_zero(void* ptr, int64_t bytes, brv_stream_t stream) {
-  if (bytes < 0) return -1;
+  BRV_REFUSE(bytes < 0, "requires bytes >= 0");
   if (bytes == 0) return 0;
-  OPS_OK(hipMemsetAsync(ptr, 0, (size_t)bytes, (hipStream_t)stream));
+  BRV_HIP_OK(hipMemsetAsync(ptr, 0, (size_t)bytes, (hipStream_t)stream));
   return 0;
 }
 
 int brv_mean_f32(const float* x, int64_t n, float* out, brv_stream_t stream) {
-  if (n < 1 || n > (1 << 20)) return -1;
+  BRV_REFUSE(n < 1 || n > (1 << 20), "requires n >= 1, n <= 2^20");
   hipLaunchKernelGGL(mean_small_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, x, (int)n, out);
-  OPS_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 
@@ -312,12 +303,12 @@ __global__ __launch_bounds__(256) void ema_update_kernel(float* ema, const float
 }
 int brv_ema_update(float* ema, const float* param, float one_minus_beta, int64_t n,
                    brv_stream_t stream) {
-  if (n < 1) return -1;
+  BRV_REFUSE(n < 1, "requires n >= 1");
   long long g = (n + 255)/256;
   if (g > 4096) g = 4096;
   hipLaunchKernelGGL(ema_update_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, ema,
                      param, one_minus_beta, (long long)n);
-  OPS_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 
@@ -370,19 +361,19 @@ __global__ __launch_bounds__(256) void si_scale_bwd_kernel(const float* g, const
 int brv_si_scale_forward(const float* x, const float* y, const int64_t* lengths, float* out,
                          double* stats, int64_t B, int64_t S, int64_t L, float eps,
                          brv_stream_t stream) {
-  if (B < 1 || S < 1 || L < 1) return -1;
+  BRV_REFUSE(B < 1 || S < 1 || L < 1, "requires B >= 1, S >= 1, L >= 1");
   hipLaunchKernelGGL(si_scale_fwd_kernel, dim3((unsigned)(B*S)), dim3(256), 0, (hipStream_t)stream,
                      x, y, (const long long*)lengths, out, stats, (int)S, (long long)L, eps);
-  OPS_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 int brv_si_scale_backward(const float* g, const float* x, const float* y, const int64_t* lengths,
                           const double* stats, float* dx, int64_t B, int64_t S, int64_t L,
                           brv_stream_t stream) {
-  if (B < 1 || S < 1 || L < 1) return -1;
+  BRV_REFUSE(B < 1 || S < 1 || L < 1, "requires B >= 1, S >= 1, L >= 1");
   hipLaunchKernelGGL(si_scale_bwd_kernel, dim3((unsigned)(B*S)), dim3(256), 0, (hipStream_t)stream,
                      g, x, y, (const long long*)lengths, stats, dx, (int)S, (long long)L);
-  OPS_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 }  // extern "C"

@@ -8,21 +8,11 @@
 
 #include "../../include/brever_hip.h"
 #include "common.cuh"
+#include "status.h"
 
 using namespace brv;
 
 namespace {
-
-#define SG_OK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return (int)e_; } while (0)
-
-dim3 flat_grid(long long n) {
-  long long g = (n + 255)/256;
-  if (g < 1) g = 1;
-  if (g > 8192) g = 8192;
-  return dim3((unsigned)g);
-}
-#define GRID_STRIDE(i, n) \
-  for (long long i = (long long)blockIdx.x*256 + threadIdx.x; i < (n); i += (long long)gridDim.x*256)
 
 __device__ __forceinline__ float silu(float v) { return v/(1.f + expf(-v)); }
 
@@ -352,7 +342,8 @@ int brv_groupnorm_fold(const float* x, const float* add_bc, const float* gamma, 
                        const float* adm_scale, const float* adm_shift, void* scratch, float* scale,
                        float* shift, float* mu_bc, float* rstd_bc, int64_t B, int64_t C, int64_t HW,
                        int64_t groups, float eps, brv_stream_t stream) {
-  if (B < 1 || C < 1 || HW < 1 || groups < 1 || C % groups) return -1;
+  BRV_REFUSE(B < 1 || C < 1 || HW < 1 || groups < 1 || C % groups,
+             "requires B >= 1, C >= 1, HW >= 1, groups >= 1, C a multiple of groups");
   hipStream_t st = (hipStream_t)stream;
   const long long n = (C/groups)*HW;
   long long nsplit = (n + 16383)/16384;
@@ -363,16 +354,16 @@ int brv_groupnorm_fold(const float* x, const float* add_bc, const float* gamma, 
   hipLaunchKernelGGL(gn_fold_kernel, dim3((unsigned)(B*groups)), dim3(64), 0, st,
                      (double*)scratch, add_bc, gamma, beta, adm_scale, adm_shift, scale, shift,
                      mu_bc, rstd_bc, (int)C, (long long)HW, (int)groups, eps);
-  SG_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 int brv_affine_act(const float* x, const float* scale_bc, const float* shift_bc, float* y,
                    int64_t B, int64_t C, int64_t HW, int act_silu, brv_stream_t stream) {
-  if (B < 1 || C < 1 || HW < 1) return -1;
+  BRV_REFUSE(B < 1 || C < 1 || HW < 1, "requires B >= 1, C >= 1, HW >= 1");
   const long long total = B*C*HW;
   hipLaunchKernelGGL(affine_act_kernel, flat_grid(total/4 + 1), dim3(256), 0, (hipStream_t)stream,
                      x, scale_bc, shift_bc, y, (long long)HW, total, act_silu);
-  SG_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 int brv_groupnorm_backward(const float* x, const float* dy, const float* scale_bc,
@@ -380,23 +371,24 @@ int brv_groupnorm_backward(const float* x, const float* dy, const float* scale_b
                            const float* gamma, float* dx, float* s1_bc, float* s2_bc, float* dadd_bc,
                            float* coef_scratch, int64_t B, int64_t C, int64_t HW, int64_t groups,
                            int act_silu, brv_stream_t stream) {
-  if (B < 1 || C < 1 || HW < 1 || groups < 1 || C % groups || C/groups > 64) return -1;
+  BRV_REFUSE(B < 1 || C < 1 || HW < 1 || groups < 1 || C % groups || C/groups > 64,
+             "requires B >= 1, C >= 1, HW >= 1, groups >= 1, C a multiple of groups, C/groups <= 64");
   hipStream_t st = (hipStream_t)stream;
   long long slices = (HW + 16383)/16384;
   if (slices > 32) slices = 32;
   double* part = nullptr;
-  SG_OK(hipMallocAsync((void**)&part, (size_t)B*C*slices*3*sizeof(double), st));
+  BRV_HIP_OK(hipMallocAsync((void**)&part, (size_t)B*C*slices*3*sizeof(double), st));
   hipLaunchKernelGGL(gn_bwd_sums_kernel, dim3((unsigned)(B*C), (unsigned)slices), dim3(256), 0, st, x,
                      dy, scale_bc, shift_bc, mu_bc, rstd_bc, part, (long long)HW, act_silu);
   float* k1 = coef_scratch; float* k2 = k1 + B*C; float* k3 = k2 + B*C;
   hipLaunchKernelGGL(gn_bwd_coef_kernel, dim3((unsigned)(B*groups)), dim3(64), 0, st, part,
                      (int)slices, gamma, rstd_bc, k1, k2, k3, s1_bc, s2_bc, dadd_bc, (int)C,
                      (long long)HW, (int)groups);
-  SG_OK(hipFreeAsync(part, st));
+  BRV_HIP_OK(hipFreeAsync(part, st));
   const long long total = B*C*HW;
   hipLaunchKernelGGL(gn_bwd_apply_kernel, flat_grid(total), dim3(256), 0, st, x, dy, scale_bc,
                      shift_bc, mu_bc, rstd_bc, k1, k2, k3, dx, (long long)HW, total, act_silu);
-  SG_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 // backward of y = act(scale[b][c]*x + shift[b][c]) (brv_affine_act): dx = scale*u, d scale =
@@ -406,56 +398,56 @@ int brv_affine_act_backward(const float* x, const float* dy, const float* scale_
                             const float* shift_bc, const float* zeros_bc, const float* ones_bc,
                             float* dx, float* dscale_bc, float* dshift_bc, int64_t B, int64_t C,
                             int64_t HW, int act_silu, brv_stream_t stream) {
-  if (B < 1 || C < 1 || HW < 1) return -1;
+  BRV_REFUSE(B < 1 || C < 1 || HW < 1, "requires B >= 1, C >= 1, HW >= 1");
   hipStream_t st = (hipStream_t)stream;
   long long slices = (HW + 16383)/16384;
   if (slices > 32) slices = 32;
   double* part = nullptr;
-  SG_OK(hipMallocAsync((void**)&part, (size_t)B*C*slices*3*sizeof(double), st));
+  BRV_HIP_OK(hipMallocAsync((void**)&part, (size_t)B*C*slices*3*sizeof(double), st));
   hipLaunchKernelGGL(gn_bwd_sums_kernel, dim3((unsigned)(B*C), (unsigned)slices), dim3(256), 0, st, x,
                      dy, scale_bc, shift_bc, zeros_bc, ones_bc, part, (long long)HW, act_silu);
   hipLaunchKernelGGL(affine_bwd_final_kernel, dim3((unsigned)((B*C + 255)/256)), dim3(256), 0, st,
                      part, (int)slices, dshift_bc, dscale_bc, (int)(B*C));
-  SG_OK(hipFreeAsync(part, st));
+  BRV_HIP_OK(hipFreeAsync(part, st));
   const long long total = B*C*HW;
   hipLaunchKernelGGL(gn_bwd_apply_kernel, flat_grid(total), dim3(256), 0, st, x, dy, scale_bc,
                      shift_bc, zeros_bc, ones_bc, scale_bc, zeros_bc, zeros_bc, dx, (long long)HW,
                      total, act_silu);
-  SG_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 int brv_silu_backward(const float* x, const float* dy, float* dx, int64_t n, brv_stream_t stream) {
-  if (n < 1) return -1;
+  BRV_REFUSE(n < 1, "requires n >= 1");
   hipLaunchKernelGGL(silu_bwd_kernel, flat_grid(n), dim3(256), 0, (hipStream_t)stream, x, dy, dx,
                      (long long)n);
-  SG_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 int brv_softmax_rows_backward(const float* p, const float* dy, float* dx, int64_t rows, int64_t cols,
                               brv_stream_t stream) {
-  if (rows < 1 || cols < 1) return -1;
+  BRV_REFUSE(rows < 1 || cols < 1, "requires rows >= 1, cols >= 1");
   hipLaunchKernelGGL(softmax_bwd_kernel, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, p,
                      dy, dx, (int)cols);
-  SG_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 int brv_silu(const float* x, float* y, int64_t n, brv_stream_t stream) {
-  if (n < 1) return -1;
+  BRV_REFUSE(n < 1, "requires n >= 1");
   hipLaunchKernelGGL(silu_kernel, flat_grid(n), dim3(256), 0, (hipStream_t)stream, x, y, (long long)n);
-  SG_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 int brv_softmax_rows(const float* x, float* y, int64_t rows, int64_t cols, brv_stream_t stream) {
-  if (rows < 1 || cols < 1) return -1;
+  BRV_REFUSE(rows < 1 || cols < 1, "requires rows >= 1, cols >= 1");
   hipLaunchKernelGGL(softmax_kernel, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, x, y,
                      (int)cols);
-  SG_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 int brv_fir_resample2d(const float* x, const float* kernel, float* y, int64_t planes, int64_t H,
                        int64_t W, int64_t Ho, int64_t Wo, int64_t K, int64_t pad_h, int64_t pad_w,
                        int up, float gain, brv_stream_t stream) {
-  if (planes < 1 || Ho < 1 || Wo < 1 || Ho > 65535) return -1;
+  BRV_REFUSE(planes < 1 || Ho < 1 || Wo < 1 || Ho > 65535, "requires planes >= 1, Ho >= 1, Wo >= 1, Ho <= 65535");
   // grid.z carries the planes: at most 65 535 per launch
   for (int64_t p0 = 0; p0 < planes; p0 += 65535) {
     const int64_t np = planes - p0 < 65535 ? planes - p0 : 65535;
@@ -471,23 +463,23 @@ int brv_fir_resample2d(const float* x, const float* kernel, float* y, int64_t pl
                          (long long)np, (int)H, (int)W, (int)Ho, (int)Wo, (int)K, (int)pad_h,
                          (int)pad_w);
   }
-  SG_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 int brv_axpby(const float* a, float alpha, const float* b, float beta, float* out, int64_t n,
               brv_stream_t stream) {
-  if (n < 1) return -1;
+  BRV_REFUSE(n < 1, "requires n >= 1");
   hipLaunchKernelGGL(axpby_kernel, flat_grid(n), dim3(256), 0, (hipStream_t)stream, a, alpha, b,
                      beta, out, (long long)n);
-  SG_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 int brv_fourier_features(const float* x, const float* b, float* out, int64_t n, int64_t m,
                          brv_stream_t stream) {
-  if (n < 1 || m < 1) return -1;
+  BRV_REFUSE(n < 1 || m < 1, "requires n >= 1, m >= 1");
   hipLaunchKernelGGL(fourier_kernel, flat_grid(n*m), dim3(256), 0, (hipStream_t)stream, x, b, out,
                      (int)n, (int)m);
-  SG_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 

@@ -13,6 +13,7 @@
 
 #include "../../include/brever_hip.h"
 #include "common.cuh"
+#include "status.h"
 #include <type_traits>
 #include "gemm_f32_big.h"
 
@@ -605,7 +606,8 @@ int launch_g32(const G32& p, int batch, hipStream_t st) {
   if (p.M <= 0 || p.N <= 0 || batch <= 0) return 0;
   dim3 grid((p.N + TN - 1)/TN, (p.M + TM - 1)/TM, batch);
   hipLaunchKernelGGL((gemm32_kernel<AM, BM, SM>), grid, dim3(256), 0, st, p);
-  return (int)hipGetLastError();
+  BRV_HIP_OK(hipGetLastError());
+  return 0;
 }
 
 // ---- the same framed products with fp64 accumulation (STFT.forward / STFT.backward) ------------
@@ -798,7 +800,8 @@ int launch_g64(const G32& p, int batch, hipStream_t st) {
   if (p.M <= 0 || p.N <= 0 || batch <= 0) return 0;
   dim3 grid((p.N + TN - 1)/TN, (p.M + TM - 1)/TM, batch);
   hipLaunchKernelGGL((gemm64_kernel<AM, BM, SM>), grid, dim3(256), 0, st, p);
-  return (int)hipGetLastError();
+  BRV_HIP_OK(hipGetLastError());
+  return 0;
 }
 
 // Y = scale |X|^(c-1) X (magnitude compression + scaling, stft.py:85-87) and its gradient:
@@ -836,7 +839,8 @@ extern "C" {
 
 int64_t brv_stft_frames(int64_t length, int64_t frame_length, int64_t hop_length) {
   // STFT.frame_count + the n/2 centre padding on both sides (stft.py:140-149, :72)
-  if (length < 0 || frame_length < 2 || hop_length < 1) return -1;
+  BRV_REFUSE(length < 0 || frame_length < 2 || hop_length < 1,
+             "requires length >= 0, frame_length >= 2, hop_length >= 1");
   const int64_t d = length > frame_length ? length - frame_length : 0;
   const int64_t nc = (d + hop_length - 1)/hop_length + 1;
   const int64_t padded = (nc - 1)*hop_length + frame_length;     // after STFT.pad
@@ -847,7 +851,7 @@ int brv_stft_forward(const float* x, const float* basis, float* spec, int64_t ro
                      int64_t length, int64_t frame_length, int64_t hop_length,
                      float compression, float scale, brv_stream_t stream) {
   const int64_t F = brv_stft_frames(length, frame_length, hop_length);
-  if (rows < 1 || F < 1) return -1;
+  BRV_REFUSE(rows < 1 || F < 1, "requires rows >= 1, F >= 1");
   const int bins = (int)(frame_length/2 + 1);
   G32 p; memset(&p, 0, sizeof(p));
   p.M = 2*bins; p.N = (int)F; p.K = (int)frame_length;
@@ -863,7 +867,8 @@ int brv_istft_backward(const float* spec, const float* inv_basis, const float* w
                        float* frames_scratch, float* y, int64_t rows, int64_t frames,
                        int64_t frame_length, int64_t hop_length, float compression,
                        float scale, brv_stream_t stream) {
-  if (rows < 1 || frames < 1 || frame_length < 2 || hop_length < 1) return -1;
+  BRV_REFUSE(rows < 1 || frames < 1 || frame_length < 2 || hop_length < 1,
+             "requires rows >= 1, frames >= 1, frame_length >= 2, hop_length >= 1");
   hipStream_t st = (hipStream_t)stream;
   const int bins = (int)(frame_length/2 + 1);
   G32 p; memset(&p, 0, sizeof(p));
@@ -881,7 +886,8 @@ int brv_istft_backward(const float* spec, const float* inv_basis, const float* w
   o.pad_left = (int)(frame_length/2);
   int gx = (o.out_len + 255)/256; if (gx > 1024) gx = 1024; if (gx < 1) gx = 1;
   hipLaunchKernelGGL(istft_ola_kernel, dim3(gx, (unsigned)rows), dim3(256), 0, st, o);
-  return (int)hipGetLastError();
+  BRV_HIP_OK(hipGetLastError());
+  return 0;
 }
 
 // Adjoint of brv_stft_forward with respect to x (compression 1): the gradient of a loss
@@ -892,7 +898,7 @@ int brv_stft_adjoint(const float* dspec, const float* basis, float* frames_scrat
                      int64_t rows, int64_t length, int64_t frame_length, int64_t hop_length,
                      float scale, brv_stream_t stream) {
   const int64_t F = brv_stft_frames(length, frame_length, hop_length);
-  if (rows < 1 || F < 1) return -1;
+  BRV_REFUSE(rows < 1 || F < 1, "requires rows >= 1, F >= 1");
   hipStream_t st = (hipStream_t)stream;
   const int bins = (int)(frame_length/2 + 1);
   G32 p; memset(&p, 0, sizeof(p));
@@ -909,7 +915,8 @@ int brv_stft_adjoint(const float* dspec, const float* basis, float* frames_scrat
   o.f_bs = (long long)F*frame_length; o.y_bs = length;
   int gx = (o.out_len + 255)/256; if (gx > 1024) gx = 1024; if (gx < 1) gx = 1;
   hipLaunchKernelGGL(istft_ola_kernel, dim3(gx, (unsigned)rows), dim3(256), 0, st, o);
-  return (int)hipGetLastError();
+  BRV_HIP_OK(hipGetLastError());
+  return 0;
 }
 
 // Framed DFT with explicit geometry (ConvSTFT, brever/modules/stft.py:201-319: the STFT as a
@@ -919,7 +926,8 @@ int brv_framed_dft_forward(const float* x, const float* basis, float* spec, int6
                            int64_t length, int64_t frame_length, int64_t hop_length,
                            int64_t pad_left, int64_t frames, float compression, float scale,
                            brv_stream_t stream) {
-  if (rows < 1 || frames < 1 || frame_length < 2 || hop_length < 1) return -1;
+  BRV_REFUSE(rows < 1 || frames < 1 || frame_length < 2 || hop_length < 1,
+             "requires rows >= 1, frames >= 1, frame_length >= 2, hop_length >= 1");
   const int bins = (int)(frame_length/2 + 1);
   G32 p; memset(&p, 0, sizeof(p));
   p.M = 2*bins; p.N = (int)frames; p.K = (int)frame_length;
@@ -938,7 +946,7 @@ int brv_framed_dft_transpose(const float* spec, const float* basis, float* frame
                              float* y, int64_t rows, int64_t frames, int64_t frame_length,
                              int64_t hop_length, int64_t pad_left, int64_t out_len,
                              float compression, float scale, brv_stream_t stream) {
-  if (rows < 1 || frames < 1 || out_len < 1) return -1;
+  BRV_REFUSE(rows < 1 || frames < 1 || out_len < 1, "requires rows >= 1, frames >= 1, out_len >= 1");
   hipStream_t st = (hipStream_t)stream;
   const int bins = (int)(frame_length/2 + 1);
   G32 p; memset(&p, 0, sizeof(p));
@@ -955,7 +963,8 @@ int brv_framed_dft_transpose(const float* spec, const float* basis, float* frame
   o.f_bs = (long long)frames*frame_length; o.y_bs = out_len;
   int gx = (o.out_len + 255)/256; if (gx > 1024) gx = 1024; if (gx < 1) gx = 1;
   hipLaunchKernelGGL(istft_ola_kernel, dim3(gx, (unsigned)rows), dim3(256), 0, st, o);
-  return (int)hipGetLastError();
+  BRV_HIP_OK(hipGetLastError());
+  return 0;
 }
 
 // General fp32 GEMM on the exact-fp32 MFMA (the Linear layers of the FFNN model and their
@@ -969,9 +978,10 @@ static int gemm_any(int lowp, const float* a, const float* b, float* d, int64_t 
                     int64_t b_kbatch_stride, const float* row_bias, int accumulate,
                     brv_stream_t stream, int flags = 0, const int* conv = nullptr,
                     float* ws = nullptr, long long ws_floats = 0) {
-  if (batch < 1 || M < 1 || N < 1 || K < 1) return -1;
-  if (conv && !lowp) return -1;
-  if (flags && (!lowp || ((flags & 2) && accumulate == 1))) return -1;
+  BRV_REFUSE(batch < 1 || M < 1 || N < 1 || K < 1, "requires batch >= 1, M >= 1, N >= 1, K >= 1");
+  BRV_REFUSE(conv && !lowp, "an implicit-convolution operand requires a bf16 / fp16 product");
+  BRV_REFUSE(flags && (!lowp || ((flags & 2) && accumulate == 1)),
+             "flags require a bf16 / fp16 product, and flag 2 does not combine with accumulate == 1");
   G32 p; memset(&p, 0, sizeof(p));
   p.M = (int)M; p.N = (int)N; p.K = (int)K;
   p.A = a; p.a_bs = a_batch_stride; p.lda = (int)lda;
@@ -1037,14 +1047,13 @@ static int gemm_any(int lowp, const float* a, const float* b, float* d, int64_t 
     if (ldd == N && (batch == 1 || d_batch_stride == M*N)) {
       // (one fill for a contiguous batch: sixteen 5-us fills in a row stood in front of the LSTM weight-gradient
       // products of the DCCRN step -- profiles/r05_dccrn_trace.txt)
-      if (hipMemsetAsync(d, 0, (size_t)batch*M*N*4, st) != hipSuccess) return -2;
+      BRV_HIP_OK(hipMemsetAsync(d, 0, (size_t)batch*M*N*4, st));
     } else if (ldd == N) {
       for (int64_t z = 0; z < batch; ++z)
-        if (hipMemsetAsync(d + z*d_batch_stride, 0, (size_t)M*N*4, st) != hipSuccess) return -2;
+        BRV_HIP_OK(hipMemsetAsync(d + z*d_batch_stride, 0, (size_t)M*N*4, st));
     } else {
       for (int64_t z = 0; z < batch; ++z)
-        if (hipMemset2DAsync(d + z*d_batch_stride, (size_t)ldd*4, 0, (size_t)N*4, (size_t)M, st)
-            != hipSuccess) return -2;
+        BRV_HIP_OK(hipMemset2DAsync(d + z*d_batch_stride, (size_t)ldd*4, 0, (size_t)N*4, (size_t)M, st));
     }
   }
   const dim3 grid((unsigned)((N + BN2 - 1)/BN2), (unsigned)((M + BM2 - 1)/BM2),
@@ -1072,7 +1081,8 @@ static int gemm_any(int lowp, const float* a, const float* b, float* d, int64_t 
     else if (trans_b) BRV_BF16_LAUNCH(false, true);
     else BRV_BF16_LAUNCH(false, false);
 #undef BRV_BF16_LAUNCH
-    return (int)hipGetLastError();
+    BRV_HIP_OK(hipGetLastError());
+    return 0;
   }
   if (trans_a && trans_b)
     hipLaunchKernelGGL((gemm_f32_kernel<true, true>), grid, dim3(256), 0, st, p, (int)ksplit);
@@ -1082,7 +1092,8 @@ static int gemm_any(int lowp, const float* a, const float* b, float* d, int64_t 
     hipLaunchKernelGGL((gemm_f32_kernel<false, true>), grid, dim3(256), 0, st, p, (int)ksplit);
   else
     hipLaunchKernelGGL((gemm_f32_kernel<false, false>), grid, dim3(256), 0, st, p, (int)ksplit);
-  return (int)hipGetLastError();
+  BRV_HIP_OK(hipGetLastError());
+  return 0;
 }
 
 int brv_gemm_f32(const float* a, const float* b, float* d, int64_t batch, int64_t M, int64_t N,
@@ -1110,7 +1121,8 @@ int brv_gemm_f32_ws(const float* a, const float* b, float* d, int64_t batch, int
                     int64_t kbatch, int64_t a_kbatch_stride, int64_t b_kbatch_stride,
                     const float* row_bias, int accumulate, float* workspace, int64_t workspace_bytes,
                     brv_stream_t stream) {
-  if (workspace && (((uintptr_t)workspace & 15) || workspace_bytes < 0)) return -1;
+  BRV_REFUSE(workspace && (((uintptr_t)workspace & 15) || workspace_bytes < 0),
+             "workspace must be 16-byte aligned and workspace_bytes >= 0");
   return gemm_any(0, a, b, d, batch, M, N, K, lda, ldb, ldd, a_batch_stride, b_batch_stride,
                   d_batch_stride, trans_a, trans_b, kbatch, a_kbatch_stride, b_kbatch_stride,
                   row_bias, accumulate, stream, 0, nullptr, workspace, workspace ? workspace_bytes/4 : 0);
@@ -1131,11 +1143,12 @@ int brv_gemm_bf16_conv(const float* a, const float* image, float* d, int64_t bat
                        const float* row_bias, int accumulate, int mode, int64_t C, int64_t H,
                        int64_t W, int64_t kh, int64_t kw, int64_t sh, int64_t sw, int64_t ph,
                        int64_t pw, int64_t Ho, int64_t Wo, brv_stream_t stream) {
-  if ((mode != 1 && mode != 2) || C < 1 || H < 1 || W < 1 || kh < 1 || kw < 1 || sh < 1 || sw < 1 ||
-      Ho < 1 || Wo < 1) return -1;
+  BRV_REFUSE((mode != 1 && mode != 2) || C < 1 || H < 1 || W < 1 || kh < 1 || kw < 1 || sh < 1 || sw < 1 ||
+             Ho < 1 || Wo < 1, "requires mode 1 or 2 and C, H, W, kh, kw, sh, sw, Ho, Wo >= 1");
   // the column matrix is (C*kh*kw) x (Ho*Wo): it is op_b's K x N (trans_b: N x K)
   const int64_t rows = C*kh*kw, pix = Ho*Wo;
-  if ((trans_b ? N : K) != rows || (trans_b ? K : N) != pix || pix >= (1LL << 31)) return -1;
+  BRV_REFUSE((trans_b ? N : K) != rows || (trans_b ? K : N) != pix || pix >= (1LL << 31),
+             "the convolution operand must be C*kh*kw rows by B*Ho*Wo < 2^31 columns of op(b)");
   const int conv[12] = {mode, (int)C, (int)H, (int)W, (int)kh, (int)kw, (int)sh, (int)sw, (int)ph,
                         (int)pw, (int)Ho, (int)Wo};
   return gemm_any(1, a, image, d, batch, M, N, K, lda, pix, ldd, a_batch_stride, image_batch_stride,
@@ -1158,7 +1171,8 @@ int brv_gemm_bf16(const float* a, const float* b, float* d, int64_t batch, int64
 int brv_dft64_forward(const float* x, const double* basis, float* spec, int64_t rows, int64_t length,
                       int64_t n, int64_t hop, int64_t pad_left, int64_t frames, int64_t bins,
                       float compression, float scale, brv_stream_t stream) {
-  if (rows < 1 || frames < 1 || n < 2 || hop < 1 || bins < 1) return -1;
+  BRV_REFUSE(rows < 1 || frames < 1 || n < 2 || hop < 1 || bins < 1,
+             "requires rows >= 1, frames >= 1, n >= 2, hop >= 1, bins >= 1");
   G32 p; memset(&p, 0, sizeof(p));
   p.M = (int)(2*bins); p.N = (int)frames; p.K = (int)n;
   p.A64 = basis; p.A = nullptr; p.a_bs = 0; p.lda = (int)n;
@@ -1174,7 +1188,7 @@ int brv_dft64_forward(const float* x, const double* basis, float* spec, int64_t 
 int brv_dft64_synthesis(const float* spec, const double* tbasis, float* frames_out, int64_t rows,
                         int64_t frames, int64_t n, int64_t bins, float compression, float scale,
                         brv_stream_t stream) {
-  if (rows < 1 || frames < 1 || n < 2 || bins < 1) return -1;
+  BRV_REFUSE(rows < 1 || frames < 1 || n < 2 || bins < 1, "requires rows >= 1, frames >= 1, n >= 2, bins >= 1");
   G32 p; memset(&p, 0, sizeof(p));
   p.M = (int)frames; p.N = (int)n; p.K = (int)(2*bins);
   p.A = spec; p.a_bs = (long long)bins*frames*2; p.frames = (int)frames;
@@ -1188,61 +1202,70 @@ int brv_dft64_synthesis(const float* spec, const double* tbasis, float* frames_o
 int brv_overlap_add(const float* frames_in, const float* window, float* y, int64_t rows,
                     int64_t frames, int64_t n, int64_t hop, int64_t pad_left, int64_t out_len,
                     brv_stream_t stream) {
-  if (rows < 1 || frames < 1 || out_len < 1 || hop < 1) return -1;
+  BRV_REFUSE(rows < 1 || frames < 1 || out_len < 1 || hop < 1,
+             "requires rows >= 1, frames >= 1, out_len >= 1, hop >= 1");
   OlaParams o;
   o.frames = frames_in; o.y = y; o.win = window; o.F = (int)frames; o.n = (int)n; o.hop = (int)hop;
   o.out_len = (int)out_len; o.normalize = window != nullptr; o.pad_left = (int)pad_left;
   o.f_bs = (long long)frames*n; o.y_bs = out_len;
   int gx = (int)((out_len + 255)/256); if (gx > 1024) gx = 1024; if (gx < 1) gx = 1;
   hipLaunchKernelGGL(istft_ola_kernel, dim3(gx, (unsigned)rows), dim3(256), 0, (hipStream_t)stream, o);
-  return (int)hipGetLastError();
+  BRV_HIP_OK(hipGetLastError());
+  return 0;
 }
 
 int brv_pad_signal(const float* x, float* y, int64_t rows, int64_t length, int64_t left,
                    int64_t out_len, int mode, brv_stream_t stream) {
-  if (rows < 1 || length < 1 || out_len < 1 || mode < 0 || mode > 3) return -1;
-  if (mode == 1 && (left >= length || out_len - left - length >= length)) return -2;
+  BRV_REFUSE(rows < 1 || length < 1 || out_len < 1 || mode < 0 || mode > 3,
+             "requires rows >= 1, length >= 1, out_len >= 1, mode >= 0, mode <= 3");
+  BRV_UNSUPPORTED(mode == 1 && (left >= length || out_len - left - length >= length),
+                  "reflect padding requires both pads shorter than length");
   int gx = (int)((rows*out_len + 255)/256); if (gx > 4096) gx = 4096;
   hipLaunchKernelGGL(pad_signal_kernel, dim3(gx), dim3(256), 0, (hipStream_t)stream, x, y,
                      (long long)rows, (long long)length, (long long)left, (long long)out_len, mode);
-  return (int)hipGetLastError();
+  BRV_HIP_OK(hipGetLastError());
+  return 0;
 }
 int brv_polar(const float* mag, const float* phase, float* out, int64_t n, brv_stream_t stream) {
-  if (n < 1) return -1;
+  BRV_REFUSE(n < 1, "requires n >= 1");
   int gx = (int)((n + 255)/256); if (gx > 4096) gx = 4096;
   hipLaunchKernelGGL(polar_kernel, dim3(gx), dim3(256), 0, (hipStream_t)stream, mag, phase,
                      (float2*)out, (long long)n);
-  return (int)hipGetLastError();
+  BRV_HIP_OK(hipGetLastError());
+  return 0;
 }
 int brv_mag_phase(const float* x, float* mag, float* phase, int64_t n, brv_stream_t stream) {
-  if (n < 1) return -1;
+  BRV_REFUSE(n < 1, "requires n >= 1");
   int gx = (int)((n + 255)/256); if (gx > 4096) gx = 4096;
   hipLaunchKernelGGL(mag_phase_kernel, dim3(gx), dim3(256), 0, (hipStream_t)stream,
                      (const float2*)x, mag, phase, (long long)n);
-  return (int)hipGetLastError();
+  BRV_HIP_OK(hipGetLastError());
+  return 0;
 }
 
 int brv_spec_compress(const float* x, float* y, int64_t n, float compression, float scale,
                       brv_stream_t stream) {
-  if (n < 1) return -1;
+  BRV_REFUSE(n < 1, "requires n >= 1");
   int gx = (int)((n + 255)/256); if (gx > 4096) gx = 4096;
   hipLaunchKernelGGL(spec_compress_kernel, dim3(gx), dim3(256), 0, (hipStream_t)stream,
                      (const float2*)x, (float2*)y, (long long)n, compression, scale);
-  return (int)hipGetLastError();
+  BRV_HIP_OK(hipGetLastError());
+  return 0;
 }
 int brv_spec_compress_backward(const float* x, const float* gy, float* gx_out, int64_t n,
                                float compression, float scale, brv_stream_t stream) {
-  if (n < 1) return -1;
+  BRV_REFUSE(n < 1, "requires n >= 1");
   int gx = (int)((n + 255)/256); if (gx > 4096) gx = 4096;
   hipLaunchKernelGGL(spec_compress_bwd_kernel, dim3(gx), dim3(256), 0, (hipStream_t)stream,
                      (const float2*)x, (const float2*)gy, (float2*)gx_out, (long long)n,
                      compression, scale);
-  return (int)hipGetLastError();
+  BRV_HIP_OK(hipGetLastError());
+  return 0;
 }
 
 int brv_matmul_f32(const float* a, const float* b, float* d, int64_t batch, int64_t M,
                    int64_t N, int64_t K, int64_t a_batch_stride, brv_stream_t stream) {
-  if (batch < 1 || M < 1 || N < 1 || K < 1) return -1;
+  BRV_REFUSE(batch < 1 || M < 1 || N < 1 || K < 1, "requires batch >= 1, M >= 1, N >= 1, K >= 1");
   G32 p; memset(&p, 0, sizeof(p));
   p.M = (int)M; p.N = (int)N; p.K = (int)K;
   p.A = a; p.a_bs = a_batch_stride; p.lda = (int)K;

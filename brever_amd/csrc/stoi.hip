@@ -19,6 +19,7 @@
 
 #include "../../include/brever_hip.h"
 #include "common.cuh"
+#include "status.h"
 
 using namespace brv;
 
@@ -252,13 +253,15 @@ extern "C" {
 int brv_resample_poly(const float* x, const float* hpad, float* y, const int64_t* lengths,
                       int64_t rows, int64_t in_stride, int64_t out_stride, int64_t up, int64_t down,
                       int64_t hpad_len, int64_t n_pre_remove, brv_stream_t stream) {
-  if (rows < 1 || in_stride < 1 || out_stride < 1 || up < 1 || down < 1 || hpad_len < 1) return -1;
+  BRV_REFUSE(rows < 1 || in_stride < 1 || out_stride < 1 || up < 1 || down < 1 || hpad_len < 1,
+             "requires rows >= 1, in_stride >= 1, out_stride >= 1, up >= 1, down >= 1, hpad_len >= 1");
   int gx = (int)((out_stride + 255)/256);
   if (gx > 4096) gx = 4096;
   hipLaunchKernelGGL(resample_poly_kernel, dim3(gx, (unsigned)rows), dim3(256), 0, (hipStream_t)stream,
                      x, hpad, y, lengths, (long long)in_stride, (long long)out_stride, (int)up,
                      (int)down, (int)hpad_len, (int)n_pre_remove);
-  return (int)hipGetLastError();
+  BRV_HIP_OK(hipGetLastError());
+  return 0;
 }
 
 int64_t brv_stoi_frames(int64_t length) { return frame_count(length); }
@@ -267,7 +270,8 @@ int brv_stoi_compact(const float* clean, const float* proc, const int64_t* lengt
                      int64_t stride, float* clean_out, float* proc_out, int64_t out_stride,
                      int32_t* geom, float* energy_scratch, int32_t* kept_scratch, int64_t nf_max,
                      float dyn_range, brv_stream_t stream) {
-  if (rows < 1 || stride < 1 || nf_max < 1 || out_stride < 1) return -1;
+  BRV_REFUSE(rows < 1 || stride < 1 || nf_max < 1 || out_stride < 1,
+             "requires rows >= 1, stride >= 1, nf_max >= 1, out_stride >= 1");
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(stoi_energy_kernel, dim3((unsigned)((nf_max + 3)/4), (unsigned)rows), dim3(256), 0,
                      st, clean, lengths, energy_scratch, (long long)stride, (int)nf_max);
@@ -279,31 +283,34 @@ int brv_stoi_compact(const float* clean, const float* proc, const int64_t* lengt
                      geom, clean_out, (long long)stride, (long long)out_stride, (int)nf_max);
   hipLaunchKernelGGL(stoi_ola_kernel, dim3(gx, (unsigned)rows), dim3(256), 0, st, proc, kept_scratch,
                      geom, proc_out, (long long)stride, (long long)out_stride, (int)nf_max);
-  return (int)hipGetLastError();
+  BRV_HIP_OK(hipGetLastError());
+  return 0;
 }
 
 int brv_stoi_bands(const float* spec, const int32_t* edges, float* tob, int64_t rows, int64_t nf_max,
                    int64_t ncols, int64_t bin0, brv_stream_t stream) {
-  if (rows < 1 || nf_max < 1 || ncols < 2) return -1;
+  BRV_REFUSE(rows < 1 || nf_max < 1 || ncols < 2, "requires rows >= 1, nf_max >= 1, ncols >= 2");
   const long long total = (long long)rows*kBands*nf_max;
   int gx = (int)((total + 255)/256);
   if (gx > 8192) gx = 8192;
   hipLaunchKernelGGL(stoi_bands_kernel, dim3(gx), dim3(256), 0, (hipStream_t)stream, spec, edges, tob,
                      (int)rows, (int)nf_max, (int)ncols, (int)bin0);
-  return (int)hipGetLastError();
+  BRV_HIP_OK(hipGetLastError());
+  return 0;
 }
 
 int brv_stoi_correlate(const float* tob_clean, const float* tob_proc, const int32_t* geom,
                        float* partial_scratch, float* out, int64_t rows, int64_t nf_max,
                        int extended, float clip, brv_stream_t stream) {
-  if (rows < 1 || nf_max < 1) return -1;
+  BRV_REFUSE(rows < 1 || nf_max < 1, "requires rows >= 1, nf_max >= 1");
   hipStream_t st = (hipStream_t)stream;
   const int nseg_max = nf_max >= kSeg ? (int)nf_max - kSeg + 1 : 1;
   hipLaunchKernelGGL(stoi_segment_kernel, dim3((unsigned)nseg_max, (unsigned)rows), dim3(64), 0, st,
                      tob_clean, tob_proc, geom, partial_scratch, (int)nf_max, nseg_max, extended, clip);
   hipLaunchKernelGGL(stoi_mean_kernel, dim3((unsigned)rows), dim3(256), 0, st, partial_scratch, geom, out,
                      nseg_max, extended);
-  return (int)hipGetLastError();
+  BRV_HIP_OK(hipGetLastError());
+  return 0;
 }
 
 }  // extern "C"

@@ -18,12 +18,12 @@
 
 #include "../../include/brever_hip.h"
 #include "common.cuh"
+#include "status.h"
 
 using namespace brv;
 
 namespace {
 
-#define TG_OK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return (int)e_; } while (0)
 
 // row slices of the parameter-gradient reduction: enough workgroups to fill the chip whatever the
 // row length (32 ... 4 128), at most 1 024 partial tables
@@ -609,14 +609,17 @@ extern "C" {
 
 int brv_head_permute(const float* in, float* out, int64_t B, int64_t T, int64_t F, int64_t H, int64_t E, int merge,
                      brv_stream_t stream) {
-  if (!in || !out || B < 1 || T < 1 || F < 1 || H < 1 || E < 1 || B > 65535) return -1;
+  BRV_REFUSE(!in || !out || B < 1 || T < 1 || F < 1 || H < 1 || E < 1 || B > 65535,
+             "requires in != NULL, out != NULL, B >= 1, T >= 1, F >= 1, H >= 1, E >= 1, B <= 65535");
   const size_t lds = (size_t)H*E*(F | 1)*sizeof(float);
-  if (lds > 64*1024) return -1;                    // (brv_head_permute_supported)
+  // (brv_head_permute_supported)
+  BRV_REFUSE(lds > 64*1024,
+             "one (T, E) head tile exceeds 64 KiB of LDS: brv_head_permute_supported");
   if (merge) hipLaunchKernelGGL(head_permute_kernel<true>, dim3((unsigned)T, (unsigned)B), dim3(256), lds,
                                 (hipStream_t)stream, in, out, (int)T, (int)F, (int)H, (int)E);
   else hipLaunchKernelGGL(head_permute_kernel<false>, dim3((unsigned)T, (unsigned)B), dim3(256), lds,
                           (hipStream_t)stream, in, out, (int)T, (int)F, (int)H, (int)E);
-  TG_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 int brv_head_permute_supported(int64_t F, int64_t H, int64_t E) {
@@ -626,7 +629,8 @@ int brv_head_permute_supported(int64_t F, int64_t H, int64_t E) {
 int brv_rownorm_forward(const float* x, const float* slope, const float* gain, const float* bias,
                         float* y, float* stats, int64_t rows, int64_t n, int64_t inner,
                         int64_t groups, float eps, brv_stream_t stream) {
-  if (rows < 1 || n < 1 || inner < 1 || groups < 1 || rows % (inner*groups)) return -1;
+  BRV_REFUSE(rows < 1 || n < 1 || inner < 1 || groups < 1 || rows % (inner*groups),
+             "requires rows >= 1, n >= 1, inner >= 1, groups >= 1, rows a multiple of inner*groups");
   hipStream_t st = (hipStream_t)stream;
   if (n <= 64) {
     int npad = 1;
@@ -639,7 +643,7 @@ int brv_rownorm_forward(const float* x, const float* slope, const float* gain, c
   hipLaunchKernelGGL(rownorm_fwd_kernel, dim3((unsigned)((rows + 3)/4)), dim3(256), 0, st, x, slope,
                      gain, bias, y, reinterpret_cast<float2*>(stats), (long long)rows, (int)n,
                      (int)inner, (int)groups, eps);
-  TG_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 
@@ -651,7 +655,8 @@ int brv_rownorm_backward(const float* x, const float* dy, const float* slope, co
                          const float* stats, float* dx, float* dgain, float* dbias,
                          float* dslope_rows, void* scratch, int64_t rows, int64_t n, int64_t inner,
                          int64_t groups, brv_stream_t stream) {
-  if (rows < 1 || n < 1 || inner < 1 || groups < 1 || rows % (inner*groups)) return -1;
+  BRV_REFUSE(rows < 1 || n < 1 || inner < 1 || groups < 1 || rows % (inner*groups),
+             "requires rows >= 1, n >= 1, inner >= 1, groups >= 1, rows a multiple of inner*groups");
   hipStream_t st = (hipStream_t)stream;
   const float2* stp = reinterpret_cast<const float2*>(stats);
   if (n <= 64) {
@@ -673,7 +678,7 @@ int brv_rownorm_backward(const float* x, const float* dy, const float* slope, co
   const long long total = (long long)groups*n;
   hipLaunchKernelGGL(rownorm_pgrad_fold_kernel, dim3((unsigned)((total + 31)/32)), dim3(256), 0,
                      st, part, dgain, dbias, total, kSlices);
-  TG_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 
@@ -682,7 +687,8 @@ int64_t brv_col_sum_scratch_bytes(int64_t batch, int64_t cols) {
 }
 int brv_col_sum(const float* x, float* out, void* scratch, int64_t batch, int64_t rows, int64_t cols,
                 brv_stream_t stream) {
-  if (batch < 1 || rows < 1 || cols < 1 || batch > 65535) return -1;
+  BRV_REFUSE(batch < 1 || rows < 1 || cols < 1 || batch > 65535,
+             "requires batch >= 1, rows >= 1, cols >= 1, batch <= 65535");
   hipStream_t st = (hipStream_t)stream;
   if (cols % 4 == 0 && (((uintptr_t)x | (uintptr_t)scratch) & 15) == 0)
     hipLaunchKernelGGL(col_sum_part4_kernel, dim3((unsigned)((cols/4 + 63)/64), kColSlices, (unsigned)batch),
@@ -692,7 +698,7 @@ int brv_col_sum(const float* x, float* out, void* scratch, int64_t batch, int64_
                        dim3(256), 0, st, x, (float*)scratch, (long long)rows, (int)cols);
   hipLaunchKernelGGL(col_sum_fold_kernel, dim3((unsigned)((cols + 255)/256), (unsigned)batch), dim3(256),
                      0, st, (const float*)scratch, out, (int)cols);
-  TG_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 int brv_linear_small_supported(int64_t M, int64_t N, int64_t K) {
@@ -700,9 +706,9 @@ int brv_linear_small_supported(int64_t M, int64_t N, int64_t K) {
 }
 int brv_linear_small(const float* x, const float* w, const float* bias, float* y, int64_t M, int64_t N, int64_t K,
                      int64_t lda, int64_t ldw, int64_t ldd, int trans_b, int accumulate, brv_stream_t stream) {
-  if (!brv_linear_small_supported(M, N, K) || (lda & 3) || (ldd & 3) || lda < K || ldd < N ||
-      (((uintptr_t)x | (uintptr_t)y) & 15) || ldw < (trans_b ? K : N) || M > (1LL << 38))
-    return -1;
+  BRV_REFUSE(!brv_linear_small_supported(M, N, K) || (lda & 3) || (ldd & 3) || lda < K || ldd < N ||
+             (((uintptr_t)x | (uintptr_t)y) & 15) || ldw < (trans_b ? K : N) || M > (1LL << 38),
+             "requires brv_linear_small_supported, lda >= K and ldd >= N multiples of 4, x, y 16-byte aligned, ldw >= the row length of w, M <= 2^38");
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid((unsigned)((M + 255)/256));
 #define BRV_LS2(N_, K_) do { \
@@ -715,7 +721,7 @@ int brv_linear_small(const float* x, const float* w, const float* bias, float* y
   if (N == 16) BRV_LS(16); else if (N == 32) BRV_LS(32); else BRV_LS(64);
 #undef BRV_LS2
 #undef BRV_LS
-  TG_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 int brv_linear_small_wgrad_supported(int64_t rows, int64_t MI, int64_t NJ) {
@@ -724,9 +730,9 @@ int brv_linear_small_wgrad_supported(int64_t rows, int64_t MI, int64_t NJ) {
 int64_t brv_linear_small_wgrad_scratch_bytes(int64_t MI, int64_t NJ) { return (int64_t)kWgSlices*MI*NJ*4; }
 int brv_linear_small_wgrad(const float* a, const float* b, float* d, void* scratch, int64_t rows, int64_t MI,
                            int64_t NJ, int64_t lda, int64_t ldb, int64_t ldd, brv_stream_t stream) {
-  if (!brv_linear_small_wgrad_supported(rows, MI, NJ) || (lda & 3) || (ldb & 3) || lda < MI || ldb < NJ ||
-      ldd < NJ || (((uintptr_t)a | (uintptr_t)b | (uintptr_t)scratch) & 15) || !scratch)
-    return -1;
+  BRV_REFUSE(!brv_linear_small_wgrad_supported(rows, MI, NJ) || (lda & 3) || (ldb & 3) || lda < MI || ldb < NJ ||
+             ldd < NJ || (((uintptr_t)a | (uintptr_t)b | (uintptr_t)scratch) & 15) || !scratch,
+             "requires brv_linear_small_wgrad_supported, lda >= MI and ldb >= NJ multiples of 4, ldd >= NJ, a, b, scratch 16-byte aligned, scratch != NULL");
   hipStream_t st = (hipStream_t)stream;
   const long long per = ((rows + kWgSlices - 1)/kWgSlices + kWgChunk - 1)/kWgChunk*kWgChunk;
   const int slices = (int)((rows + per - 1)/per);
@@ -740,33 +746,33 @@ int brv_linear_small_wgrad(const float* a, const float* b, float* d, void* scrat
 #undef BRV_WS
   hipLaunchKernelGGL(wgrad_small_fold_kernel, dim3((unsigned)(MI*NJ/32)), dim3(256), 0, st, part, d,
                      (int)MI, (int)NJ, (long long)ldd, slices);
-  TG_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 int brv_col_sum_bf16(const void* x, float* out, void* scratch, int64_t batch, int64_t rows, int64_t cols,
                      brv_stream_t stream) {
-  if (batch < 1 || rows < 1 || cols < 8 || batch > 65535 || cols % 8 != 0 ||
-      (((uintptr_t)x | (uintptr_t)scratch) & 15))
-    return -1;
+  BRV_REFUSE(batch < 1 || rows < 1 || cols < 8 || batch > 65535 || cols % 8 != 0 ||
+             (((uintptr_t)x | (uintptr_t)scratch) & 15),
+             "requires 1 <= batch <= 65535, rows >= 1, cols >= 8 and a multiple of 8, x and scratch 16-byte aligned");
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(col_sum_part8h_kernel, dim3((unsigned)((cols/8 + 63)/64), kColSlices, (unsigned)batch),
                      dim3(256), 0, st, (const unsigned short*)x, (float*)scratch, (long long)rows, (int)cols);
   hipLaunchKernelGGL(col_sum_fold_kernel, dim3((unsigned)((cols + 255)/256), (unsigned)batch), dim3(256),
                      0, st, (const float*)scratch, out, (int)cols);
-  TG_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 int brv_row_std(const float* x, float* out, int64_t rows, int64_t n, brv_stream_t stream) {
-  if (rows < 1 || n < 2) return -1;
+  BRV_REFUSE(rows < 1 || n < 2, "requires rows >= 1, n >= 2");
   hipLaunchKernelGGL(row_std_kernel, dim3((unsigned)rows), dim3(1024), 0, (hipStream_t)stream, x,
                      out, (long long)n);
-  TG_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 
 int brv_row_scale(const float* x, const float* s, float* y, int64_t rows, int64_t n, int divide,
                   brv_stream_t stream) {
-  if (rows < 1 || n < 1 || rows > 65535) return -1;
+  BRV_REFUSE(rows < 1 || n < 1 || rows > 65535, "requires rows >= 1, n >= 1, rows <= 65535");
   const unsigned gx = (unsigned)min((long long)1024, (long long)((n + 255)/256));
   if (divide)
     hipLaunchKernelGGL(row_scale_kernel<true>, dim3(gx, (unsigned)rows), dim3(256), 0,
@@ -774,7 +780,7 @@ int brv_row_scale(const float* x, const float* s, float* y, int64_t rows, int64_
   else
     hipLaunchKernelGGL(row_scale_kernel<false>, dim3(gx, (unsigned)rows), dim3(256), 0,
                        (hipStream_t)stream, x, s, y, (long long)n);
-  TG_OK(hipGetLastError());
+  BRV_HIP_OK(hipGetLastError());
   return 0;
 }
 

@@ -10,7 +10,9 @@
  *     allocator); the library allocates nothing and keeps no global state;
  *   - every call takes the HIP stream to launch on and never synchronises;
  *   - return value: 0 ok, < 0 invalid argument / unsupported configuration,
- *     > 0 a hipError_t; brv_last_error() gives a thread-local message.
+ *     > 0 a hipError_t; brv_last_error() gives a thread-local message. A call
+ *     that returns non-zero (a query that returns < 0) has set that message; a
+ *     call that returns 0 leaves it unspecified.
  *
  * Activations inside the library are channels-last bf16 ([item][frame][channel],
  * channels padded to a multiple of 64); this never leaks through the ABI: inputs
