@@ -97,7 +97,7 @@ __global__ __launch_bounds__(256) void cln_scan_kernel(const ClnParams p) {
     s1 += fs[2*t]; s2 += fs[2*t + 1];
     const double n = (double)p.C*(double)(t + 1);
     const double mean = s1/n;
-    const double var = s2/n - mean*mean;
+    const double var = fmax(s2/n - mean*mean, 0.0);         // constant input: the rounding of an exact 0
     tb[2*t] = (float)mean;
     tb[2*t + 1] = (float)(1.0/sqrt(var + (double)p.eps));
   }

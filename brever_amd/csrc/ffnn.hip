@@ -132,18 +132,23 @@ __global__ __launch_bounds__(256) void static_norm_kernel(const float* x, const 
   }
 }
 // running mean / variance along time, one thread per (b, row)   (ffnn.py:195-203)
+// Sums, mean, variance and rstd in fp64, one rounding to fp32 at the store: E[x^2] - E[x]^2 of
+// log-mel rows (mean many standard deviations from zero) cancels to nothing in fp32, and on a
+// constant row (digital silence, padding) comes out below -eps, so sqrtf returned NaN. The
+// clamp keeps the rounding of an exactly-zero variance from ever reaching the square root.
 __global__ __launch_bounds__(256) void cumulative_norm_kernel(const float* x, float* out, int T,
                                                               long long nrows, float eps) {
   GRID_STRIDE(r, nrows) {
     const float* xi = x + r*T;
     float* oi = out + r*T;
-    float s = 0.f, q = 0.f;
+    double s = 0.0, q = 0.0;
     for (int t = 0; t < T; ++t) {
-      s += xi[t]; q += xi[t]*xi[t];
-      const float n = (float)(t + 1);
-      const float mean = s/n;
-      const float var = q/n - mean*mean;
-      oi[t] = (xi[t] - mean)/sqrtf(var + eps);
+      const double v = (double)xi[t];
+      s += v; q += v*v;
+      const double n = (double)(t + 1);
+      const double mean = s/n;
+      const double var = fmax(q/n - mean*mean, 0.0);
+      oi[t] = (float)((v - mean)/sqrt(var + (double)eps));
     }
   }
 }

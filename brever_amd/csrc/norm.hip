@@ -7,8 +7,8 @@
 //   mean_t = S1_t/n_t, var_t = S2_t/n_t - mean_t^2, y = (x - mean_t) rstd_t gain_c + bias_c.
 // Forward: per-frame sums (coalesced along t) -> blocked prefix scan per (item, group) in fp64
 // -> apply. Backward: per-frame sums of dxhat and dxhat*xhat -> SUFFIX scan of the gradients of
-// S1 / S2 (a frame's statistics feed every later frame) -> dx = dxhat rstd + U + 2 x V; the
-// gain / bias gradients are per-channel reductions.
+// S1 / S2 (a frame's statistics feed every later frame) -> dx = dxhat rstd + U + 2 x V (fp64 terms, one
+// rounding); the gain / bias gradients are per-channel reductions.
 #include <hip/hip_runtime.h>
 #include <math.h>
 
@@ -78,13 +78,13 @@ __global__ __launch_bounds__(256) void cgn_scan_kernel(double2* fs, float2* stat
   blocked_scan<false>(v, T, [&](int t, const double2& c) {
     const double n = (double)R*(t + 1);
     const double mean = c.x/n;
-    const double var = c.y/n - mean*mean;
+    const double var = fmax(c.y/n - mean*mean, 0.0);     // constant input: the rounding of an exact 0
     st[t] = make_float2((float)mean, (float)(1.0/sqrt(var + (double)eps)));
   });
 }
-// in: (A_t, B_t) -> (dS1_t, dS2_t) in place, then suffix sums (U, V)
-__global__ __launch_bounds__(256) void cgn_bwd_scan_kernel(double2* ab, const float2* stats,
-                                                           float2* uv, int R, int T) {
+// in: (A_t, B_t) -> (dS1_t, dS2_t) in place, then their suffix sums (U, V), again in place and in fp64:
+// blocked_scan reads and writes a frame only from the thread that owns its segment
+__global__ __launch_bounds__(256) void cgn_bwd_scan_kernel(double2* ab, const float2* stats, int R, int T) {
   double2* v = ab + (long long)blockIdx.x*T;
   const float2* st = stats + (long long)blockIdx.x*T;
   for (int t = threadIdx.x; t < T; t += 256) {
@@ -95,8 +95,7 @@ __global__ __launch_bounds__(256) void cgn_bwd_scan_kernel(double2* ab, const fl
     v[t] = make_double2((-r*A + Bq*r*r*mean)/n, -0.5*Bq*r*r/n);
   }
   __syncthreads();
-  float2* o = uv + (long long)blockIdx.x*T;
-  blocked_scan<true>(v, T, [&](int t, const double2& c) { o[t] = make_float2((float)c.x, (float)c.y); });
+  blocked_scan<true>(v, T, [&](int t, const double2& c) { v[t] = c; });
 }
 __global__ __launch_bounds__(256) void cgn_apply_kernel(const float* x, const float2* stats,
                                                         const float* gain, const float* bias,
@@ -111,8 +110,12 @@ __global__ __launch_bounds__(256) void cgn_apply_kernel(const float* x, const fl
     y[idx] = (x[idx] - st.x)*st.y*gain[c] + bias[c];
   }
 }
+// dx = dxhat rstd + U + 2 x V, summed in fp64 from the fp64 suffix sums and rounded once. Where a frame's
+// variance is (nearly) zero -- frame 0 of an instance norm without inner dimensions is one value, var = 0,
+// rstd = 1/sqrt(eps) = 1e5 -- dxhat rstd and U are 1e5 times the gradient and cancel; fp32 terms left an error of
+// 1e5 ulp there. dxhat is the fp32 product the frame sums added up, so that the cancellation is exact.
 __global__ __launch_bounds__(256) void cgn_bwd_apply_kernel(const float* x, const float* dy,
-                                                            const float2* stats, const float2* uv,
+                                                            const float2* stats, const double2* uv,
                                                             const float* gain, float* dx, int R,
                                                             int T, int G, int inner,
                                                             long long total) {
@@ -121,8 +124,10 @@ __global__ __launch_bounds__(256) void cgn_bwd_apply_kernel(const float* x, cons
     const int t = (int)(idx % T);
     const long long row = idx / T, bg = row / R;
     const int c = (int)(bg % G)*(R/inner) + (int)(row % R)/inner;
-    const float2 st = stats[bg*T + t], w = uv[bg*T + t];
-    dx[idx] = dy[idx]*gain[c]*st.y + w.x + 2.f*x[idx]*w.y;
+    const float rstd = stats[bg*T + t].y;
+    const double2 w = uv[bg*T + t];
+    const float dxh = dy[idx]*gain[c];
+    dx[idx] = (float)((double)dxh*(double)rstd + w.x + 2.0*(double)x[idx]*w.y);
   }
 }
 // dgain[c] = sum dy*xhat, dbias[c] = sum dy over (batch, inner, frames): one workgroup per channel
@@ -186,10 +191,10 @@ int brv_causal_groupnorm_backward(const float* x, const float* dy, const float* 
   hipLaunchKernelGGL((cgn_frame_sums_kernel<true>), fgrid, dim3(256), 0, st, x, dy, gain,
                      (const float2*)stats, (double2*)scratch, R, (int)T, (int)groups, (int)inner);
   hipLaunchKernelGGL(cgn_bwd_scan_kernel, dim3((unsigned)(B*groups)), dim3(256), 0, st,
-                     (double2*)scratch, (const float2*)stats, (float2*)uv_scratch, R, (int)T);
+                     (double2*)scratch, (const float2*)stats, R, (int)T);
   const long long total = B*C*inner*T;
   hipLaunchKernelGGL(cgn_bwd_apply_kernel, flat(total), dim3(256), 0, st, x, dy, (const float2*)stats,
-                     (const float2*)uv_scratch, gain, dx, R, (int)T, (int)groups, (int)inner, total);
+                     (const double2*)scratch, gain, dx, R, (int)T, (int)groups, (int)inner, total);
   hipLaunchKernelGGL(cgn_param_grads_kernel, dim3((unsigned)C), dim3(256), 0, st, x, dy,
                      (const float2*)stats, dgain, dbias, (int)B, (int)C, (int)groups, (int)inner,
                      (int)T);

@@ -42,10 +42,9 @@ class _CausalGroupNormFunction(torch.autograd.Function):
         dgain, dbias = torch.empty_like(gain), torch.empty_like(gain)
         scratch = torch.empty(lib.brv_causal_groupnorm_scratch_bytes(B, groups, T), dtype=torch.uint8,
                               device=x.device)
-        uv = torch.empty(B*groups, T, 2, dtype=torch.float32, device=x.device)
         hip.check(lib.brv_causal_groupnorm_backward(
             hip.ptr(x), hip.ptr(dy), hip.ptr(gain), hip.ptr(stats), hip.ptr(dx), hip.ptr(dgain),
-            hip.ptr(dbias), hip.ptr(scratch), hip.ptr(uv), B, C, inner, T, groups, hip.stream()),
+            hip.ptr(dbias), hip.ptr(scratch), None, B, C, inner, T, groups, hip.stream()),
             'brv_causal_groupnorm_backward')
         return dx, dgain, dbias, None, None
 

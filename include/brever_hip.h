@@ -709,7 +709,8 @@ int brv_cplx_moments_backward(const float* x, const float* gm, float* dx, int64_
  * CausalLayerNorm = 1 group, CausalInstanceNorm = one group per channel): x (B, C, inner, T)
  * with the frames last, every frame normalised with the statistics of its group over all frames
  * up to it. stats (B*groups, T, 2) receives (mean, rstd) for the backward pass; scratch:
- * brv_causal_groupnorm_scratch_bytes(); uv_scratch: B*groups*T*2 floats. */
+ * brv_causal_groupnorm_scratch_bytes(); uv_scratch: not used any more (the suffix sums of the
+ * backward pass stay in fp64 inside scratch), kept in the signature, may be NULL. */
 int64_t brv_causal_groupnorm_scratch_bytes(int64_t B, int64_t groups, int64_t T);
 int brv_causal_groupnorm_forward(const float* x, const float* gain, const float* bias, float* y,
                                  float* stats, void* scratch, int64_t B, int64_t C, int64_t inner,

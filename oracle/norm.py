@@ -2,7 +2,8 @@
 (brever/modules/normalization.py:5-46 CausalGroupNorm; :54-72 the LayerNorm / InstanceNorm
 shorthands, groups = 1 / groups = channels). Pinned by tests/golden/norms.npz (generated from
 the imported reference by tests/golden/make_golden.py). Nothing on the product path imports
-this file.
+this file. `cumulative_norm` is the FFNN's CumulativeNormalizer
+(brever/models/ffnn/ffnn.py:190-203) for float64 use, pinned by `cumnorm_out` of tests/golden/ffnn.npz.
 
 Restated as running moments: with the input viewed as (batch, group, rest, frame), frame t is
 normalised by the mean and the biased variance of everything its group holds in frames 0..t
@@ -31,3 +32,18 @@ def causal_group_norm(x, gain, bias, groups, time_dim=-1, eps=1e-10):
     z = z.reshape(moved).movedim(-1, t_ax)
     per_channel = [1, C] + [1]*(x.ndim - 2)
     return z*gain.view(per_channel) + bias.view(per_channel)
+
+
+def cumulative_norm(x, eps=1e-4, parts=False):
+    """The FFNN's CumulativeNormalizer (brever/models/ffnn/ffnn.py:190-203) in the dtype of `x`:
+    every row of (..., T) is normalised at frame t by its own mean and biased variance over
+    frames 0..t. Meant to be called on `.double()` inputs as the yardstick of the fp32 kernel.
+    The variance is clamped at 0, which it cannot go below in exact arithmetic; the reference
+    does not clamp, and in fp32 returns NaN on constant rows. parts=True also returns the
+    running mean and 1/sqrt(var + eps), from which the tests form their rounding bound."""
+    count = torch.arange(1, x.shape[-1] + 1, dtype=x.dtype)
+    mean = x.cumsum(-1)/count
+    var = ((x*x).cumsum(-1)/count - mean*mean).clamp_min(0)
+    spread = (var + eps).sqrt()
+    y = (x - mean)/spread
+    return (y, mean, 1/spread) if parts else y

@@ -454,6 +454,27 @@ def test_causal_norm_oracle_matches_reference(golden_dir):
             assert ((got - ref).norm()/ref.norm()).item() <= 1e-5, (tag, key)
 
 
+def test_cumulative_norm_oracle_matches_reference(golden_dir):
+    """oracle.norm.cumulative_norm in float64 vs the reference's CumulativeNormalizer output
+    `cumnorm_out` of ffnn.npz. The golden is an fp32 cumsum and sits 1.4e-4 rel-L2 / 0.015 at the
+    worst element from the float64 value (measured on the CPU): bounds 2e-4 / 0.02. On constant
+    rows, where the reference's fp32 arithmetic is not finite, the oracle is finite and zero."""
+    from oracle.norm import cumulative_norm
+    g = np.load(os.path.join(golden_dir, 'ffnn.npz'))
+    x, ref = torch.from_numpy(g['batch'])[:, :384].double(), torch.from_numpy(g['cumnorm_out']).double()
+    y = cumulative_norm(x, 1e-4)
+    assert y.dtype == torch.float64 and y.shape == ref.shape
+    assert ((y - ref).norm()/ref.norm()).item() <= 2e-4
+    assert (y - ref).abs().max().item() <= 0.02
+    y2, mean, rstd = cumulative_norm(x, 1e-4, parts=True)
+    assert torch.equal(y2, y) and (y - (x - mean)*rstd).abs().max().item() <= 1e-12
+    for value in (-18.420681, -9.21, 0.0):
+        const = torch.full((2, 3, 2000), value, dtype=torch.float32).double()
+        yc = cumulative_norm(const, 1e-4)
+        assert torch.isfinite(yc).all()
+        assert yc.abs().max().item() <= 1e-9
+
+
 @pytest.mark.parametrize('tag', ['a', 'b', 'c'])
 def test_tfgridnet_oracle_matches_reference(golden_dir, tag):
     """oracle.tfgridnet vs the reference TF-GridNet at seeded weights (two narrow configurations:
