@@ -51,9 +51,7 @@ class _SnrFunction(torch.autograd.Function):
         x2, y2, lengths, B, S, L = _rows(x, y, lengths)
         scratch = _scratch(B, S, x.device)
         loss = torch.empty(B, dtype=torch.float32, device=x.device)
-        hip.check(hip.lib().brv_snr_forward(
-            hip.ptr(x2), hip.ptr(y2), hip.ptr(lengths), B, S, L, L,
-            hip.ptr(scratch), hip.ptr(loss), hip.stream()), 'brv_snr_forward')
+        hip.call('brv_snr_forward', x2, y2, lengths, B, S, L, L, scratch, loss, hip.stream())
         ctx.save_for_backward(x2, y2, lengths, scratch)
         ctx.shape = x.shape
         ctx.in_dtype = x.dtype
@@ -65,10 +63,7 @@ class _SnrFunction(torch.autograd.Function):
         B, S, L = x2.shape
         dx = torch.empty_like(x2)
         g = grad.float().contiguous()
-        hip.check(hip.lib().brv_snr_backward(
-            hip.ptr(x2), hip.ptr(y2), hip.ptr(lengths), B, S, L, L,
-            hip.ptr(scratch), hip.ptr(g), hip.ptr(dx), hip.stream()),
-            'brv_snr_backward')
+        hip.call('brv_snr_backward', x2, y2, lengths, B, S, L, L, scratch, g, dx, hip.stream())
         return dx.view(ctx.shape).to(ctx.in_dtype), None, None
 
 
@@ -80,9 +75,7 @@ class _SisnrFunction(torch.autograd.Function):
             raise ValueError('sisnr supports at most 4 sources on the HIP path')
         scratch = _scratch(B, S, x.device)
         loss = torch.empty(B, dtype=torch.float32, device=x.device)
-        hip.check(hip.lib().brv_sisnr_forward(
-            hip.ptr(x2), hip.ptr(y2), hip.ptr(lengths), B, S, L, L,
-            hip.ptr(scratch), hip.ptr(loss), hip.stream()), 'brv_sisnr_forward')
+        hip.call('brv_sisnr_forward', x2, y2, lengths, B, S, L, L, scratch, loss, hip.stream())
         ctx.save_for_backward(x2, y2, lengths, scratch)
         ctx.shape = x.shape
         ctx.in_dtype = x.dtype
@@ -94,10 +87,7 @@ class _SisnrFunction(torch.autograd.Function):
         B, S, L = x2.shape
         dx = torch.empty_like(x2)
         g = grad.float().contiguous()
-        hip.check(hip.lib().brv_sisnr_backward(
-            hip.ptr(x2), hip.ptr(y2), hip.ptr(lengths), B, S, L, L,
-            hip.ptr(scratch), hip.ptr(g), hip.ptr(dx), hip.stream()),
-            'brv_sisnr_backward')
+        hip.call('brv_sisnr_backward', x2, y2, lengths, B, S, L, L, scratch, g, dx, hip.stream())
         return dx.view(ctx.shape).to(ctx.in_dtype), None, None
 
 
@@ -111,9 +101,7 @@ class _MseFunction(torch.autograd.Function):
         if weight is not None:
             hip.require_device(weight)
             w = weight.float().contiguous()
-        hip.check(hip.lib().brv_mse_forward(
-            hip.ptr(x2), hip.ptr(y2), hip.ptr(lengths), hip.ptr(w), B, S, L, L,
-            hip.ptr(scratch), hip.ptr(loss), hip.stream()), 'brv_mse_forward')
+        hip.call('brv_mse_forward', x2, y2, lengths, w, B, S, L, L, scratch, loss, hip.stream())
         ctx.save_for_backward(x2, y2, lengths)
         ctx.weight = w
         ctx.shape = x.shape
@@ -126,9 +114,7 @@ class _MseFunction(torch.autograd.Function):
         B, S, L = x2.shape
         dx = torch.empty_like(x2)
         g = grad.float().contiguous()
-        hip.check(hip.lib().brv_mse_backward(
-            hip.ptr(x2), hip.ptr(y2), hip.ptr(lengths), hip.ptr(ctx.weight), B, S,
-            L, L, hip.ptr(g), hip.ptr(dx), hip.stream()), 'brv_mse_backward')
+        hip.call('brv_mse_backward', x2, y2, lengths, ctx.weight, B, S, L, L, g, dx, hip.stream())
         return dx.view(ctx.shape).to(ctx.in_dtype), None, None, None
 
 
@@ -138,16 +124,13 @@ class _MultiResYuFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, y, lengths, stfts, time_w, spec_w):
-        lib = hip.lib()
         x2, y2, lengths, B, S, L = _rows(x, y, lengths)
         rows = B*S
         xm, ym = torch.empty_like(x2), torch.empty_like(y2)
         for src, dst in ((x2, xm), (y2, ym)):
-            hip.check(lib.brv_apply_mask(hip.ptr(src), hip.ptr(lengths), hip.ptr(dst), B, S, L,
-                                         hip.stream()), 'brv_apply_mask')
+            hip.call('brv_apply_mask', src, lengths, dst, B, S, L, hip.stream())
         sums = torch.empty(rows, dtype=torch.float64, device=x.device)
-        hip.check(lib.brv_l1_forward(hip.ptr(xm), hip.ptr(ym), hip.ptr(sums), rows, L,
-                                     hip.stream()), 'brv_l1_forward')
+        hip.call('brv_l1_forward', xm, ym, sums, rows, L, hip.stream())
         total = time_w*sums
         specs = []
         for stft in stfts:
@@ -157,9 +140,7 @@ class _MultiResYuFunction(torch.autograd.Function):
                 Y = stft._dft_forward(ym.view(rows, L), basis, 1.0, stft.scale_factor)
             n = X.shape[-2]*X.shape[-1]
             ssum = torch.empty(rows, dtype=torch.float64, device=x.device)
-            hip.check(lib.brv_mag_l1_forward(
-                hip.ptr(torch.view_as_real(X)), hip.ptr(torch.view_as_real(Y)), hip.ptr(ssum),
-                rows, n, hip.stream()), 'brv_mag_l1_forward')
+            hip.call('brv_mag_l1_forward', torch.view_as_real(X), torch.view_as_real(Y), ssum, rows, n, hip.stream())
             total = total + (spec_w/len(stfts))*ssum
             specs.append((X, Y))
         total = total.view(B, S)/lengths.view(B, 1).double()
@@ -169,7 +150,6 @@ class _MultiResYuFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad):
-        lib = hip.lib()
         xm, ym, lengths, *flat = ctx.saved_tensors
         stfts, time_w, spec_w, shape, in_dtype = ctx.meta
         B, S, L = xm.shape
@@ -178,21 +158,18 @@ class _MultiResYuFunction(torch.autograd.Function):
         grow = (grad.float()/(S*lengths.float())).repeat_interleave(S).contiguous()
         dx = torch.empty_like(xm)
         g_t = (time_w*grow).contiguous()
-        hip.check(lib.brv_l1_backward(hip.ptr(xm), hip.ptr(ym), hip.ptr(g_t), hip.ptr(dx), rows,
-                                      L, 0, hip.stream()), 'brv_l1_backward')
+        hip.call('brv_l1_backward', xm, ym, g_t, dx, rows, L, 0, hip.stream())
         for k, stft in enumerate(stfts):
             X, Y = flat[2*k], flat[2*k + 1]
             n = X.shape[-2]*X.shape[-1]
             g_s = (spec_w/len(stfts)*grow).contiguous()
             dX = torch.empty(*X.shape, 2, dtype=torch.float32, device=X.device)
-            hip.check(lib.brv_mag_l1_backward(
-                hip.ptr(torch.view_as_real(X)), hip.ptr(torch.view_as_real(Y)), hip.ptr(g_s),
-                hip.ptr(dX), rows, n, hip.stream()), 'brv_mag_l1_backward')
+            hip.call('brv_mag_l1_backward', torch.view_as_real(X), torch.view_as_real(Y), g_s, dX, rows, n,
+                     hip.stream())
             # adjoint of X = scale * DFT(x): scale * DFT^T
             dx += stft._dft_adjoint(dX, L, stft.scale_factor).view(B, S, L)
         out = torch.empty_like(dx)
-        hip.check(lib.brv_apply_mask(hip.ptr(dx), hip.ptr(lengths), hip.ptr(out), B, S, L,
-                                     hip.stream()), 'brv_apply_mask')
+        hip.call('brv_apply_mask', dx, lengths, out, B, S, L, hip.stream())
         return out.view(shape).to(in_dtype), None, None, None, None, None
 
 
@@ -205,9 +182,7 @@ class _ScaleInvariantFunction(torch.autograd.Function):
         x2, y2, lengths, B, S, L = _rows(x, y, lengths)
         out = torch.empty_like(x2)
         stats = torch.empty(B*S, 2, dtype=torch.float64, device=x2.device)
-        hip.check(hip.lib().brv_si_scale_forward(
-            hip.ptr(x2), hip.ptr(y2), hip.ptr(lengths), hip.ptr(out), hip.ptr(stats), B, S, L,
-            float(eps), hip.stream()), 'brv_si_scale_forward')
+        hip.call('brv_si_scale_forward', x2, y2, lengths, out, stats, B, S, L, float(eps), hip.stream())
         ctx.save_for_backward(x2, y2, lengths, stats)
         ctx.shape = x.shape
         return out.view(x.shape)
@@ -218,9 +193,7 @@ class _ScaleInvariantFunction(torch.autograd.Function):
         B, S, L = x2.shape
         g2 = g.reshape(B, S, L).float().contiguous()
         dx = torch.empty_like(x2)
-        hip.check(hip.lib().brv_si_scale_backward(
-            hip.ptr(g2), hip.ptr(x2), hip.ptr(y2), hip.ptr(lengths), hip.ptr(stats), hip.ptr(dx), B,
-            S, L, hip.stream()), 'brv_si_scale_backward')
+        hip.call('brv_si_scale_backward', g2, x2, y2, lengths, stats, dx, B, S, L, hip.stream())
         return dx.view(ctx.shape), None, None
 
 

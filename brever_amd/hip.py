@@ -1,4 +1,8 @@
-"""ctypes binding of ``libbrever_hip.so`` (C ABI: ``include/brever_hip.h``).
+"""ctypes binding of ``libbrever_hip.so``, derived from its C header.
+
+``include/brever_hip.h`` is the single declaration of the C ABI: ``SIGNATURES`` is parsed from it at import
+(``parse_header``), so an entry point is added or changed there and nowhere else. ``call`` / ``query`` invoke an
+entry point by name and raise with the library's own message; pointer arguments take tensors directly.
 
 The HIP library is the product; there is no CPU or PyTorch fallback. Every
 helper here raises ``RuntimeError`` when the shared library is missing or when
@@ -6,16 +10,33 @@ it is handed a tensor that is not on a ROCm device.
 """
 import ctypes
 import os
+import re
 
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # BRV_LIB_PATH: load another build of the same library (tools/: diagnostic builds)
 LIB_PATH = os.environ.get('BRV_LIB_PATH') or os.path.join(_HERE, 'csrc', 'libbrever_hip.so')
+# the header sits next to the package (there is no install layout); diagnostic builds share it
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'brever_hip.h')
 
 _c_i64 = ctypes.c_int64
-_c_f32 = ctypes.c_float
-_c_ptr = ctypes.c_void_p
+
+
+class _c_ptr(ctypes.c_void_p):
+    """Pointer argument: a tensor passes its ``data_ptr()``; None, ints, ``bytes``, ctypes buffers and ``byref``
+    go through as for ``c_void_p``. No device check here -- the header does not say which pointers are host
+    pointers (``require_device``)."""
+
+    @staticmethod           # (called once per pointer argument of every call: the lookups are bound here)
+    def from_param(obj, _tensor=torch.Tensor, _void_p=ctypes.c_void_p, _other=ctypes.c_void_p.from_param):
+        if isinstance(obj, _tensor):
+            return _void_p(obj.data_ptr())
+        return _other(obj)
+
+
+_SCALARS = {'int64_t': ctypes.c_int64, 'int32_t': ctypes.c_int32, 'int': ctypes.c_int,
+            'uint32_t': ctypes.c_uint32, 'float': ctypes.c_float}
 
 
 class CtnConfig(ctypes.Structure):
@@ -43,7 +64,7 @@ class DccrnStreamConfig(ctypes.Structure):
         'n_fft', 'hop', 'levels', 'kf', 'kt', 'sf', 'pf', 'opf', 'st', 'pt', 'opt', 'complex_bn')] + [
         ('channels', ctypes.c_int32*_M), ('lstm_hidden', ctypes.c_int32), ('lstm_layers', ctypes.c_int32),
         ('eps', ctypes.c_float*(2*_M)), ('off_block', (_c_i64*7)*(2*_M)), ('off_lstm', ((_c_i64*4)*2)*4),
-        ('off_linear', _c_i64*4), ('run_mean', _c_ptr*(2*_M)), ('run_var', _c_ptr*(2*_M))]
+        ('off_linear', _c_i64*4), ('run_mean', ctypes.c_void_p*(2*_M)), ('run_var', ctypes.c_void_p*(2*_M))]
 
 
 OPT_NO_FWD_FUSE, OPT_NO_BWD_FUSE, OPT_NO_WS, OPT_DWPW2_WS = 0x001, 0x002, 0x004, 0x008
@@ -84,291 +105,50 @@ def opts_ptr(opts):
     return ctypes.byref(opts)
 
 
-# name -> (restype, argtypes); the export test checks every name resolves.
-SIGNATURES = {
-    'brv_version': (ctypes.c_int, []),
-    'brv_last_error': (ctypes.c_char_p, []),
-    'brv_prof_create': (_c_ptr, [ctypes.c_int]),
-    'brv_prof_collect': (_c_i64, [_c_ptr, ctypes.c_char_p, _c_i64]),
-    'brv_prof_destroy': (None, [_c_ptr]),
-    'brv_ctn_param_count': (_c_i64, [_c_ptr]),
-    'brv_ctn_param_tensors': (_c_i64, [_c_ptr]),
-    'brv_ctn_param_offset': (_c_i64, [_c_ptr, _c_i64]),
-    'brv_ctn_frames': (_c_i64, [_c_ptr, _c_i64]),
-    'brv_ctn_prepared_bytes': (_c_i64, [_c_ptr]),
-    'brv_ctn_workspace_bytes': (_c_i64, [_c_ptr, _c_i64, _c_i64]),
-    'brv_ctn_workspace_offset': (_c_i64, [_c_ptr, _c_i64, _c_i64,
-                                          ctypes.c_char_p, _c_i64]),
-    'brv_ctn_prepare': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr]),
-    'brv_ctn_forward': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_i64,
-                                       _c_ptr, _c_i64, _c_i64, _c_ptr, _c_ptr]),
-    'brv_ctn_backward': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_i64,
-                                        _c_ptr, _c_ptr, _c_i64, _c_i64,
-                                        _c_ptr, _c_ptr]),
-    'brv_ctn_backward_part': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_i64,
-                                             _c_ptr, _c_ptr, _c_i64, _c_i64,
-                                             ctypes.c_int32, ctypes.c_int32, _c_ptr, _c_ptr]),
-    'brv_ctn_grad_bucket': (ctypes.c_int, [_c_ptr, ctypes.c_int32, ctypes.c_int32,
-                                           _c_ptr, _c_ptr]),
-    'brv_ctn_f32_backward_part': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr,
-                                                 _c_ptr, _c_i64, _c_i64, ctypes.c_int32,
-                                                 ctypes.c_int32, _c_ptr]),
-    'brv_ctn_f32_workspace_bytes': (_c_i64, [_c_ptr, _c_i64, _c_i64]),
-    'brv_ctn_f32_forward': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr,
-                                           _c_i64, _c_i64, _c_ptr]),
-    'brv_ctn_f32_backward': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr,
-                                            _c_ptr, _c_i64, _c_i64, _c_ptr]),
-    'brv_ctn_stream_state_bytes': (_c_i64, [_c_ptr]),
-    'brv_ctn_stream_workspace_bytes': (_c_i64, [_c_ptr, _c_i64, _c_i64, ctypes.c_int32]),
-    'brv_ctn_stream_reset': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_i64, _c_ptr]),
-    'brv_ctn_stream_step': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_ptr,
-                                           ctypes.c_int32, _c_ptr, _c_i64, _c_ptr, _c_ptr]),
-    'brv_ctn_stream_tail': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_i64, _c_ptr, _c_ptr]),
-    'brv_dccrn_stream_state_bytes': (_c_i64, [_c_ptr]),
-    'brv_dccrn_stream_workspace_bytes': (_c_i64, [_c_ptr, _c_i64, _c_i64, ctypes.c_int32]),
-    'brv_dccrn_stream_reset': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_i64, _c_ptr]),
-    'brv_dccrn_stream_step': (ctypes.c_int, [_c_ptr]*7 + [_c_i64, _c_ptr, _c_i64, _c_ptr, ctypes.c_int32, _c_ptr,
-                                                         _c_i64, _c_ptr, _c_ptr]),
-    'brv_dccrn_stream_tail': (ctypes.c_int, [_c_ptr]*7 + [_c_i64, _c_ptr, _c_i64, _c_ptr, ctypes.c_int32, _c_ptr,
-                                                         _c_i64, _c_ptr, _c_ptr]),
-    'brv_resample_poly': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_ptr] + [_c_i64]*7 + [_c_ptr]),
-    'brv_stoi_frames': (_c_i64, [_c_i64]),
-    'brv_stoi_compact': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64, _c_ptr, _c_ptr,
-                                        _c_i64, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_f32, _c_ptr]),
-    'brv_stoi_bands': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64, _c_i64, _c_i64,
-                                      _c_ptr]),
-    'brv_stoi_correlate': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64,
-                                          ctypes.c_int, _c_f32, _c_ptr]),
-    'brv_flac_info': (ctypes.c_int, [_c_ptr, _c_i64, _c_ptr, _c_ptr, _c_ptr, _c_ptr]),
-    'brv_flac_decode': (_c_i64, [_c_ptr, _c_i64, _c_ptr, _c_i64]),
-    'brv_flac_encode16': (_c_i64, [_c_ptr, _c_i64, ctypes.c_int32, _c_ptr, _c_i64]),
-    'brv_loss_scratch_bytes': (_c_i64, [_c_i64, _c_i64]),
-    'brv_snr_forward_strided': (ctypes.c_int, [_c_ptr, _c_ptr, _c_i64, _c_i64, _c_ptr, _c_i64, _c_i64,
-                                                _c_i64, _c_i64, _c_ptr, _c_ptr, _c_ptr]),
-    'brv_snr_backward_strided': (ctypes.c_int, [_c_ptr, _c_ptr, _c_i64, _c_i64, _c_ptr, _c_i64, _c_i64,
-                                                 _c_i64, _c_i64, _c_ptr, _c_ptr, _c_ptr, _c_ptr]),
-    'brv_snr_forward': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64,
-                                       _c_i64, _c_i64, _c_ptr, _c_ptr, _c_ptr]),
-    'brv_snr_backward': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64,
-                                        _c_i64, _c_i64, _c_ptr, _c_ptr, _c_ptr,
-                                        _c_ptr]),
-    'brv_sisnr_forward': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_i64,
-                                         _c_i64, _c_i64, _c_i64, _c_ptr,
-                                         _c_ptr, _c_ptr]),
-    'brv_sisnr_backward': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64,
-                                          _c_i64, _c_i64, _c_ptr, _c_ptr, _c_ptr,
-                                          _c_ptr]),
-    'brv_mse_backward': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_i64,
-                                        _c_i64, _c_i64, _c_i64, _c_ptr, _c_ptr,
-                                        _c_ptr]),
-    'brv_mse_forward': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_i64,
-                                       _c_i64, _c_i64, _c_i64, _c_ptr, _c_ptr,
-                                       _c_ptr]),
-    'brv_stft_frames': (_c_i64, [_c_i64, _c_i64, _c_i64]),
-    'brv_stft_forward': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64,
-                                        _c_i64, _c_i64, _c_f32, _c_f32, _c_ptr]),
-    'brv_istft_backward': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr,
-                                          _c_i64, _c_i64, _c_i64, _c_i64, _c_f32,
-                                          _c_f32, _c_ptr]),
-    'brv_dft64_forward': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr] + [_c_i64]*7 + [_c_f32, _c_f32, _c_ptr]),
-    'brv_dft64_synthesis': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr] + [_c_i64]*4 + [_c_f32, _c_f32, _c_ptr]),
-    'brv_overlap_add': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr] + [_c_i64]*6 + [_c_ptr]),
-    'brv_pad_signal': (ctypes.c_int, [_c_ptr, _c_ptr, _c_i64, _c_i64, _c_i64, _c_i64, ctypes.c_int, _c_ptr]),
-    'brv_polar': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_i64, _c_ptr]),
-    'brv_mag_phase': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_i64, _c_ptr]),
-    'brv_spec_compress': (ctypes.c_int, [_c_ptr, _c_ptr, _c_i64, _c_f32, _c_f32, _c_ptr]),
-    'brv_spec_compress_backward': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_i64, _c_f32, _c_f32, _c_ptr]),
-    'brv_matmul_f32': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64,
-                                      _c_i64, _c_i64, _c_i64, _c_ptr]),
-    'brv_stft_adjoint': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64,
-                                        _c_i64, _c_i64, _c_f32, _c_ptr]),
-    'brv_apply_mask': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64, _c_i64, _c_ptr]),
-    'brv_l1_forward': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64, _c_ptr]),
-    'brv_l1_backward': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64,
-                                       ctypes.c_int, _c_ptr]),
-    'brv_mag_l1_forward': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64, _c_ptr]),
-    'brv_mag_l1_backward': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64,
-                                           _c_ptr]),
-    'brv_framed_dft_forward': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr] + [_c_i64]*6
-                               + [_c_f32, _c_f32, _c_ptr]),
-    'brv_framed_dft_transpose': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_ptr] + [_c_i64]*6
-                                 + [_c_f32, _c_f32, _c_ptr]),
-    'brv_gemm_f32': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr] + [_c_i64]*10
-                     + [ctypes.c_int, ctypes.c_int, _c_i64, _c_i64, _c_i64, _c_ptr,
-                        ctypes.c_int, _c_ptr]),
-    'brv_gemm_f32_workspace_bytes': (ctypes.c_int64, [_c_i64]*4 + [ctypes.c_int, ctypes.c_int, _c_i64]),
-    'brv_gemm_f32_ws': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr] + [_c_i64]*10
-                        + [ctypes.c_int, ctypes.c_int, _c_i64, _c_i64, _c_i64, _c_ptr,
-                           ctypes.c_int, _c_ptr, _c_i64, _c_ptr]),
-    'brv_gemm_bf16': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr] + [_c_i64]*10
-                      + [ctypes.c_int, ctypes.c_int, _c_i64, _c_i64, _c_i64, _c_ptr,
-                         ctypes.c_int, _c_ptr]),
-    'brv_gemm_bf16_mixed': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr] + [_c_i64]*10
-                            + [ctypes.c_int, ctypes.c_int, _c_i64, _c_i64, _c_i64, _c_ptr,
-                               ctypes.c_int, ctypes.c_int, _c_ptr]),
-    'brv_fbe_power': (ctypes.c_int, [_c_ptr, _c_ptr, _c_i64, _c_i64, _c_i64, _c_ptr]),
-    'brv_compress': (ctypes.c_int, [_c_ptr, _c_ptr, _c_i64, ctypes.c_int, _c_f32, _c_ptr]),
-    'brv_interaural_coherence': (ctypes.c_int, [_c_ptr, _c_ptr, _c_i64, _c_i64, _c_i64, _c_f32, _c_ptr]),
-    'brv_binaural': (ctypes.c_int, [_c_ptr, _c_ptr, _c_i64, _c_i64, ctypes.c_int, _c_f32, _c_ptr]),
-    'brv_col_normalize': (ctypes.c_int, [_c_ptr, _c_i64, _c_i64, _c_i64, _c_f32, _c_ptr]),
-    'brv_deltas': (ctypes.c_int, [_c_ptr, _c_ptr, _c_i64, _c_i64, _c_i64, _c_ptr]),
-    'brv_irm': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_i64, _c_f32, _c_ptr]),
-    'brv_stack_frames': (ctypes.c_int, [_c_ptr, _c_ptr, _c_i64, _c_i64, _c_i64, _c_i64, _c_ptr]),
-    'brv_static_norm': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64, _c_i64,
-                                       _c_ptr]),
-    'brv_cumulative_norm': (ctypes.c_int, [_c_ptr, _c_ptr, _c_i64, _c_i64, _c_f32, _c_ptr]),
-    'brv_relu_dropout_forward': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_i64, _c_f32, _c_ptr]),
-    'brv_relu_dropout_backward': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_f32,
-                                                 _c_ptr]),
-    'brv_dropout_apply': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_i64, _c_f32, _c_ptr]),
-    'brv_sigmoid_forward': (ctypes.c_int, [_c_ptr, _c_ptr, _c_i64, _c_ptr]),
-    'brv_sigmoid_backward': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_i64, _c_ptr]),
-    'brv_row_sum': (ctypes.c_int, [_c_ptr, _c_ptr, _c_i64, _c_i64, _c_i64, _c_ptr]),
-    'brv_masked_mean_spec': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64, _c_i64,
-                                            _c_ptr]),
-    'brv_conv2d_forward': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_ptr] + [_c_i64]*13
-                           + [ctypes.c_int, _c_f32, _c_ptr]),
-    'brv_conv_transpose2d_forward': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_ptr] + [_c_i64]*15
-                                     + [ctypes.c_int, _c_f32, _c_ptr]),
-    'brv_batchnorm2d_forward': (ctypes.c_int, [_c_ptr]*9 + [_c_i64]*3
-                                + [_c_f32, _c_f32, ctypes.c_int, _c_ptr]),
-    'brv_lstm_recurrent_forward': (ctypes.c_int, [_c_ptr]*6 + [_c_i64]*4 + [_c_ptr]),
-    'brv_conv2d_wgrad': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_ptr] + [_c_i64]*15
-                         + [ctypes.c_int, _c_f32, _c_ptr]),
-    'brv_batchnorm2d_backward': (ctypes.c_int, [_c_ptr]*11 + [_c_i64, _c_i64, _c_i64, _c_ptr]),
-    'brv_lstm_recurrent_backward': (ctypes.c_int, [_c_ptr]*5 + [_c_i64]*4 + [_c_ptr]),
-    'brv_lstm_recurrent_bf16_supported': (ctypes.c_int, [_c_i64]),
-    'brv_lstm_recurrent_forward_bf16': (ctypes.c_int, [_c_ptr]*6 + [_c_i64]*4 + [_c_ptr]),
-    'brv_lstm_recurrent_backward_bf16': (ctypes.c_int, [_c_ptr]*5 + [_c_i64]*4 + [_c_ptr]),
-    'brv_lstm_tile_supported': (ctypes.c_int, [_c_i64]),
-    'brv_lstm_tile_forward': (ctypes.c_int, [_c_ptr]*6 + [_c_i64]*7 + [ctypes.c_int, _c_ptr]),
-    'brv_lstm_tile_backward': (ctypes.c_int, [_c_ptr]*5 + [_c_i64]*7 + [ctypes.c_int, _c_ptr]),
-    'brv_dccrn_apply_mask_backward': (ctypes.c_int, [_c_ptr]*7 + [_c_i64, _c_ptr]),
-    'brv_istft_env_divide': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr] + [_c_i64]*5 + [_c_ptr]),
-    'brv_combine': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_i64, _c_f32, _c_ptr]),
-    'brv_dccrn_apply_mask': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_i64,
-                                            _c_ptr]),
-    'brv_causal_groupnorm_scratch_bytes': (_c_i64, [_c_i64, _c_i64, _c_i64]),
-    'brv_causal_groupnorm_forward': (ctypes.c_int, [_c_ptr]*6 + [_c_i64]*5 + [_c_f32, _c_ptr]),
-    'brv_causal_groupnorm_backward': (ctypes.c_int, [_c_ptr]*9 + [_c_i64]*5 + [_c_ptr]),
-    'brv_rownorm_forward': (ctypes.c_int, [_c_ptr]*6 + [_c_i64]*4 + [_c_f32, _c_ptr]),
-    'brv_rownorm_scratch_bytes': (_c_i64, [_c_i64, _c_i64]),
-    'brv_rownorm_backward': (ctypes.c_int, [_c_ptr]*10 + [_c_i64]*4 + [_c_ptr]),
-    'brv_col_sum_scratch_bytes': (_c_i64, [_c_i64, _c_i64]),
-    'brv_linear_small_supported': (ctypes.c_int, [_c_i64, _c_i64, _c_i64]),
-    'brv_linear_small': (ctypes.c_int, [_c_ptr]*4 + [_c_i64]*6 + [ctypes.c_int, ctypes.c_int, _c_ptr]),
-    'brv_linear_small_wgrad_supported': (ctypes.c_int, [_c_i64, _c_i64, _c_i64]),
-    'brv_linear_small_wgrad_scratch_bytes': (_c_i64, [_c_i64, _c_i64]),
-    'brv_linear_small_wgrad': (ctypes.c_int, [_c_ptr]*4 + [_c_i64]*6 + [_c_ptr]),
-    'brv_col_sum': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64, _c_i64, _c_ptr]),
-    'brv_col_sum_bf16': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64, _c_i64, _c_ptr]),
-    'brv_row_std': (ctypes.c_int, [_c_ptr, _c_ptr, _c_i64, _c_i64, _c_ptr]),
-    'brv_row_scale': (ctypes.c_int, [_c_ptr]*3 + [_c_i64, _c_i64, ctypes.c_int, _c_ptr]),
-    'brv_head_permute_supported': (ctypes.c_int, [_c_i64]*3),
-    'brv_head_permute': (ctypes.c_int, [_c_ptr]*2 + [_c_i64]*5 + [ctypes.c_int, _c_ptr]),
-    'brv_cplx_moments': (ctypes.c_int, [_c_ptr, _c_ptr, _c_i64, _c_i64, _c_i64, _c_ptr]),
-    'brv_cplx_affine_forward': (ctypes.c_int, [_c_ptr]*5 + [_c_i64]*3 + [_c_ptr]),
-    'brv_cplx_affine_backward': (ctypes.c_int, [_c_ptr]*9 + [_c_i64]*3 + [_c_ptr]),
-    'brv_cplx_moments_backward': (ctypes.c_int, [_c_ptr]*3 + [_c_i64]*3 + [_c_ptr]),
-    'brv_im2col': (ctypes.c_int, [_c_ptr, _c_ptr] + [_c_i64]*12 + [_c_ptr]),
-    'brv_col2im': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr] + [_c_i64]*12 + [_c_ptr]),
-    'brv_im2col_bf16': (ctypes.c_int, [_c_ptr, _c_ptr] + [_c_i64]*12 + [_c_ptr]),
-    'brv_col2im_bf16': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr] + [_c_i64]*12 + [_c_ptr]),
-    'brv_complex_weight_pack': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64, _c_f32, _c_ptr]),
-    'brv_complex_weight_unpack': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64, _c_f32, _c_ptr]),
-    'brv_groupnorm_scratch_bytes': (_c_i64, [_c_i64, _c_i64]),
-    'brv_groupnorm_fold': (ctypes.c_int, [_c_ptr]*11 + [_c_i64]*4 + [_c_f32, _c_ptr]),
-    'brv_groupnorm_backward': (ctypes.c_int, [_c_ptr]*12 + [_c_i64]*4 + [ctypes.c_int, _c_ptr]),
-    'brv_affine_act_backward': (ctypes.c_int, [_c_ptr]*9 + [_c_i64]*3 + [ctypes.c_int, _c_ptr]),
-    'brv_silu_backward': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_i64, _c_ptr]),
-    'brv_softmax_rows_backward': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64, _c_ptr]),
-    'brv_affine_act': (ctypes.c_int, [_c_ptr]*4 + [_c_i64]*3 + [ctypes.c_int, _c_ptr]),
-    'brv_silu': (ctypes.c_int, [_c_ptr, _c_ptr, _c_i64, _c_ptr]),
-    'brv_softmax_rows': (ctypes.c_int, [_c_ptr, _c_ptr, _c_i64, _c_i64, _c_ptr]),
-    'brv_fir_resample2d': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr] + [_c_i64]*8
-                           + [ctypes.c_int, _c_f32, _c_ptr]),
-    'brv_axpby': (ctypes.c_int, [_c_ptr, _c_f32, _c_ptr, _c_f32, _c_ptr, _c_i64, _c_ptr]),
-    'brv_fourier_features': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64, _c_ptr]),
-    'brv_conv2d_packed_size': (_c_i64, [_c_i64, _c_i64, _c_i64]),
-    'brv_conv2d_pack_f16': (ctypes.c_int, [_c_ptr, _c_ptr, _c_i64, _c_i64, _c_i64, _c_ptr]),
-    'brv_conv2d_mfma_forward': (ctypes.c_int, [_c_ptr]*6 + [ctypes.c_int, _c_ptr] + [_c_i64]*8
-                                + [_c_f32, _c_ptr]),
-    'brv_gemm_bf16_conv': (ctypes.c_int, [_c_ptr]*3 + [_c_i64]*9 + [ctypes.c_int, ctypes.c_int]
-                           + [_c_i64]*3 + [_c_ptr, ctypes.c_int, ctypes.c_int] + [_c_i64]*11 + [_c_ptr]),
-    'brv_dccrn_apply_mask_batched': (ctypes.c_int, [_c_ptr]*3 + [_c_i64, _c_i64, _c_ptr]),
-    'brv_dccrn_apply_mask_backward_batched': (ctypes.c_int, [_c_ptr]*4 + [_c_i64, _c_i64, _c_ptr]),
-    'brv_complex_bias_pack': (ctypes.c_int, [_c_ptr]*3 + [_c_i64, _c_ptr]),
-    'brv_complex_bias_unpack': (ctypes.c_int, [_c_ptr]*3 + [_c_i64, _c_ptr]),
-    'brv_cconv_packed_bytes': (_c_i64, [_c_i64, _c_i64]),
-    'brv_cconv_pack': (ctypes.c_int, [_c_ptr, _c_ptr] + [_c_i64]*4 + [_c_ptr]),
-    'brv_cconv_pack_complex': (ctypes.c_int, [_c_ptr]*4 + [_c_i64]*3 + [_c_f32] + [_c_ptr]*3 + [_c_i64]*4 + [_c_ptr]
-                               + [_c_i64]*4 + [_c_ptr]),
-    'brv_cconv_rows': (ctypes.c_int, [_c_ptr, _c_ptr, _c_i64, _c_ptr, _c_ptr, _c_ptr, _c_ptr] + [_c_i64]*6
-                       + [ctypes.c_int32, _c_ptr]),
-    'brv_cconv_wgrad_workspace_bytes': (_c_i64, [_c_i64]*4),
-    'brv_cconv_wgrad': (ctypes.c_int, [_c_ptr]*5 + [_c_i64]*6 + [_c_ptr]),
-    'brv_cconv_rows_bf16': (ctypes.c_int, [_c_ptr, _c_ptr, _c_i64, _c_ptr, _c_ptr, _c_ptr, _c_ptr] + [_c_i64]*6
-                            + [ctypes.c_int32, _c_ptr]),
-    'brv_cconv_wgrad_bf16': (ctypes.c_int, [_c_ptr]*5 + [_c_i64]*6 + [_c_ptr]),
-    'brv_cconv_rows_ex': (ctypes.c_int, [_c_ptr, _c_ptr, _c_i64, _c_ptr, _c_ptr, _c_ptr, _c_ptr] + [_c_i64]*6
-                          + [ctypes.c_int32]*3 + [_c_ptr]),
-    'brv_batchnorm2d_forward_bf16io': (ctypes.c_int, [_c_ptr]*9 + [_c_i64]*3
-                                       + [_c_f32, _c_f32, ctypes.c_int, _c_ptr]),
-    'brv_batchnorm2d_backward_bf16io': (ctypes.c_int, [_c_ptr]*12 + [_c_i64, _c_i64, _c_i64, _c_ptr]),
-    'brv_complex_mix_forward': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_i64, _c_ptr]),
-    'brv_complex_mix_backward': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_i64, _c_ptr]),
-    'brv_batchnorm2d_backward_ex': (ctypes.c_int, [_c_ptr, ctypes.c_int32, _c_ptr, _c_ptr, ctypes.c_int32] + [_c_ptr]*6
-                                    + [ctypes.c_int32] + [_c_ptr]*4 + [_c_i64, _c_i64, _c_i64, _c_ptr]),
-    'brv_batchnorm2d_forward_bf16': (ctypes.c_int, [_c_ptr]*9 + [_c_i64]*3
-                                     + [_c_f32, _c_f32, ctypes.c_int, _c_ptr]),
-    'brv_batchnorm2d_backward_bf16': (ctypes.c_int, [_c_ptr]*12 + [_c_i64, _c_i64, _c_i64, _c_ptr]),
-    'brv_conv_nhwc_packed_size': (_c_i64, [_c_i64, _c_i64, _c_i64]),
-    'brv_conv_nhwc_pack': (ctypes.c_int, [_c_ptr, _c_ptr, _c_i64, _c_i64, _c_i64, _c_ptr]),
-    'brv_conv_nhwc_forward': (ctypes.c_int, [_c_ptr, _c_i64, _c_i64, _c_ptr, _c_i64, _c_i64, _c_ptr,
-                                             _c_ptr, _c_ptr, _c_i64, _c_ptr, _c_ptr, ctypes.c_int,
-                                             _c_ptr] + [_c_i64]*6 + [_c_f32, _c_ptr, _c_ptr]),
-    'brv_conv_nhwc_forward_gn': (ctypes.c_int, [_c_ptr, _c_i64, _c_i64, _c_ptr, _c_i64, _c_i64, _c_ptr,
-                                                _c_ptr, _c_ptr, _c_i64] + [_c_ptr]*7 + [_c_i64, _c_f32, _c_ptr,
-                                                ctypes.c_int, _c_ptr] + [_c_i64]*6 + [_c_f32, _c_ptr, _c_ptr]),
-    'brv_conv_nhwc_split_ws_bytes': (_c_i64, [_c_i64]*6),
-    'brv_conv_nhwc_forward_ws': (ctypes.c_int, [_c_ptr, _c_i64, _c_i64, _c_ptr, _c_i64, _c_i64, _c_ptr,
-                                                _c_ptr, _c_ptr, _c_i64, _c_ptr, _c_ptr, ctypes.c_int,
-                                                _c_ptr] + [_c_i64]*6 + [_c_f32, _c_ptr, _c_ptr, _c_i64, _c_ptr]),
-    'brv_conv_nhwc_forward_gn_ws': (ctypes.c_int, [_c_ptr, _c_i64, _c_i64, _c_ptr, _c_i64, _c_i64, _c_ptr,
-                                                   _c_ptr, _c_ptr, _c_i64] + [_c_ptr]*7 + [_c_i64, _c_f32, _c_ptr,
-                                                   ctypes.c_int, _c_ptr] + [_c_i64]*6
-                                    + [_c_f32, _c_ptr, _c_ptr, _c_i64, _c_ptr]),
-    'brv_groupnorm_fold_chan2': (ctypes.c_int, [_c_ptr, _c_i64, _c_ptr, _c_i64] + [_c_ptr]*7
-                                 + [_c_i64]*3 + [_c_f32, _c_ptr]),
-    'brv_nchw_to_nhwc_f16': (ctypes.c_int, [_c_ptr, _c_ptr] + [_c_i64]*4 + [_c_ptr]),
-    'brv_nhwc_f16_to_nchw': (ctypes.c_int, [_c_ptr, _c_ptr] + [_c_i64]*4 + [_c_ptr]),
-    'brv_nhwc_chan_stats': (ctypes.c_int, [_c_ptr, _c_ptr] + [_c_i64]*6 + [_c_ptr]),
-    'brv_groupnorm_fold_chan': (ctypes.c_int, [_c_ptr]*8 + [_c_i64]*4 + [_c_f32, _c_ptr]),
-    'brv_nhwc_affine_act': (ctypes.c_int, [_c_ptr]*4 + [_c_i64]*4 + [ctypes.c_int, _c_ptr]),
-    'brv_nhwc_fir_resample2d': (ctypes.c_int, [_c_ptr]*3 + [_c_i64]*9 + [ctypes.c_int, _c_f32, _c_ptr]),
-    'brv_nhwc_fir_resample2d_dual': (ctypes.c_int, [_c_ptr]*3 + [ctypes.c_int] + [_c_ptr]*3 + [_c_i64]*10
-                                     + [ctypes.c_int, _c_f32, _c_ptr]),
-    'brv_nhwc_axpby': (ctypes.c_int, [_c_ptr, _c_f32, _c_ptr, _c_f32, _c_ptr, _c_i64, _c_ptr]),
-    'brv_nhwc_conv1x1_packed_size': (_c_i64, [_c_i64, _c_i64, _c_i64]),
-    'brv_nhwc_conv1x1_pack': (ctypes.c_int, [_c_ptr, _c_ptr, _c_i64, _c_i64, _c_i64, _c_ptr]),
-    'brv_nhwc_conv1x1_forward': (ctypes.c_int, [_c_ptr, _c_i64, _c_i64, _c_ptr, _c_i64, _c_i64,
-                                                _c_ptr, _c_ptr, _c_ptr] + [_c_i64]*3 + [_c_f32, _c_ptr]),
-    'brv_nhwc_conv3x3_small_pack': (ctypes.c_int, [_c_ptr, _c_ptr, _c_i64, _c_i64, _c_ptr]),
-    'brv_nhwc_conv3x3_small': (ctypes.c_int, [_c_ptr]*5 + [ctypes.c_int, _c_ptr, _c_ptr] + [_c_i64]*6
-                               + [_c_ptr]),
-    'brv_nhwc_add_pointwise': (ctypes.c_int, [_c_ptr]*5 + [_c_i64]*5 + [_c_f32, _c_ptr]),
-    'brv_si_scale_forward': (ctypes.c_int, [_c_ptr]*5 + [_c_i64]*3 + [_c_f32, _c_ptr]),
-    'brv_si_scale_backward': (ctypes.c_int, [_c_ptr]*6 + [_c_i64]*3 + [_c_ptr]),
-    'brv_ema_update': (ctypes.c_int, [_c_ptr, _c_ptr, _c_f32, _c_i64, _c_ptr]),
-    'brv_clip_adam_step2': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_i64] + [_c_f32]*6
-                            + [_c_i64, _c_ptr, ctypes.c_int32, _c_ptr, _c_ptr]),
-    'brv_memset_zero': (ctypes.c_int, [_c_ptr, _c_i64, _c_ptr]),
-    'brv_mean_f32': (ctypes.c_int, [_c_ptr, _c_i64, _c_ptr, _c_ptr]),
-    'brv_clip_adam_step': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_ptr,
-                                          _c_i64, _c_f32, _c_f32, _c_f32,
-                                          _c_f32, _c_f32, _c_f32, _c_i64,
-                                          _c_ptr, _c_ptr, _c_ptr]),
-}
+def _ctype(decl, proto, ret=False):
+    """ctypes type of one declaration of the header (``const float* x``, ``int64_t n``, a result type). The map
+    is closed: anything else raises, naming the prototype."""
+    m = re.fullmatch(r'\s*(?:const\s+)?(\w+)\s*(\*?)\s*(\w*)\s*', decl)
+    base, star, name = m.groups() if m else ('', '', '')
+    if star:
+        t = ctypes.c_char_p if base == 'char' else ctypes.c_void_p if ret else _c_ptr
+        known = not ret or base in ('char', 'void')
+    else:
+        t = None if base == 'void' else _c_ptr if base == 'brv_stream_t' else _SCALARS.get(base)
+        known = base in _SCALARS or base == ('void' if ret else 'brv_stream_t')
+    if not known or (ret and name):
+        raise RuntimeError(f'{proto}: no ctypes type for {decl.strip()!r}')
+    return t
+
+
+def parse_header(text):
+    """``{name: (restype, argtypes)}`` of every ``ret brv_name(args);`` of a C header."""
+    text = re.sub(r'/\*.*?\*/', ' ', text, flags=re.S)
+    text = re.sub(r'//[^\n]*', ' ', text)
+    text = re.sub(r'^[ \t]*#(?:.*\\\n)*.*$', ' ', text, flags=re.M)
+    table = {}
+    for ret, name, args in re.findall(r'([^;{}()]*)\b(brv_\w+)\s*\(([^;{}]*);', text):
+        args = args.rstrip()
+        if not args.endswith(')') or '(' in args or ')' in args[:-1]:
+            raise RuntimeError(f'{name}: cannot split the argument list ({args!r}')
+        args = args[:-1].strip()
+        argtypes = [] if args in ('', 'void') else [_ctype(a, name) for a in args.split(',')]
+        table[name] = (_ctype(ret, name, ret=True), argtypes)
+    for name in re.findall(r'\b(brv_\w+)\s*\(', text):
+        if name not in table:
+            raise RuntimeError(f'{name}: not a prototype the parser can read')
+    return table
+
+
+def _header_signatures():
+    if not os.path.exists(HEADER_PATH):
+        raise RuntimeError(f'{HEADER_PATH} is missing: the binding is derived from the C header')
+    with open(HEADER_PATH) as f:
+        return parse_header(f.read())
+
+
+# name -> (restype, argtypes), read from the header; the export test checks every name resolves.
+SIGNATURES = _header_signatures()
 
 _lib = None
 
@@ -400,6 +180,21 @@ def check(status, what):
                            f'{msg.decode() if msg else ""}')
 
 
+def call(name, *args):
+    """Call the entry point ``name``, which returns an int status; anything but 0 raises with the library's message."""
+    status = getattr(_lib or lib(), name)(*args)
+    if status:
+        check(status, name)
+
+
+def query(name, *args):
+    """Value of the int64_t size / count query ``name``; a negative one raises like ``call``."""
+    n = getattr(_lib or lib(), name)(*args)
+    if n < 0:
+        check(int(n), name)
+    return n
+
+
 def require_device(*tensors):
     for t in tensors:
         if t is not None and not t.is_cuda:
@@ -426,13 +221,11 @@ def gemm_f32(a, b, d, batch, M, N, K, lda, ldb, ldd, a_bs, b_bs, d_bs, trans_a, 
         nbytes = lib().brv_gemm_f32_workspace_bytes(batch, M, N, K, trans_a, trans_b, kbatch)
         if nbytes > 0:
             ws = torch.empty(nbytes//4, dtype=torch.float32, device=d.device)
-            check(lib().brv_gemm_f32_ws(
-                ptr(a), ptr(b), ptr(d), batch, M, N, K, lda, ldb, ldd, a_bs, b_bs, d_bs, trans_a, trans_b,
-                kbatch, a_kbs, b_kbs, ptr(bias), mode, ptr(ws), nbytes, stream()), 'brv_gemm_f32_ws')
+            call('brv_gemm_f32_ws', a, b, d, batch, M, N, K, lda, ldb, ldd, a_bs, b_bs, d_bs, trans_a, trans_b,
+                 kbatch, a_kbs, b_kbs, bias, mode, ws, nbytes, stream())
             return
-    check(lib().brv_gemm_f32(
-        ptr(a), ptr(b), ptr(d), batch, M, N, K, lda, ldb, ldd, a_bs, b_bs, d_bs, trans_a, trans_b,
-        kbatch, a_kbs, b_kbs, ptr(bias), mode, stream()), 'brv_gemm_f32')
+    call('brv_gemm_f32', a, b, d, batch, M, N, K, lda, ldb, ldd, a_bs, b_bs, d_bs, trans_a, trans_b,
+         kbatch, a_kbs, b_kbs, bias, mode, stream())
 
 
 def prof_enable(mode):

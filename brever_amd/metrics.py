@@ -96,9 +96,8 @@ def _stoi_hip(x, y, fs, extended, lengths):
         n10 = -(-L*c['up']//c['down'])
         res = torch.empty(2*B, n10, dtype=torch.float32, device=dev)
         len2 = torch.cat([lengths, lengths])
-        hip.check(lib.brv_resample_poly(
-            hip.ptr(sig), hip.ptr(c['hpad']), hip.ptr(res), hip.ptr(len2), 2*B, L, n10,
-            c['up'], c['down'], c['hpad'].numel(), c['n_pre_remove'], st), 'brv_resample_poly')
+        hip.call('brv_resample_poly', sig, c['hpad'], res, len2, 2*B, L, n10, c['up'], c['down'], c['hpad'].numel(),
+                 c['n_pre_remove'], st)
         sig, L = res, n10
         lengths = -(-lengths*c['up']//c['down'])
     nf_max = max(int(lib.brv_stoi_frames(L)), 1)
@@ -107,25 +106,19 @@ def _stoi_hip(x, y, fs, extended, lengths):
     geom = torch.empty(B, 4, dtype=torch.int32, device=dev)
     energy = torch.empty(B, nf_max, dtype=torch.float32, device=dev)
     kept = torch.empty(B, nf_max, dtype=torch.int32, device=dev)
-    hip.check(lib.brv_stoi_compact(
-        hip.ptr(sig[:B]), hip.ptr(sig[B:]), hip.ptr(lengths), B, L, hip.ptr(comp[:B]),
-        hip.ptr(comp[B:]), out_stride, hip.ptr(geom), hip.ptr(energy), hip.ptr(kept), nf_max,
-        40.0, st), 'brv_stoi_compact')
+    hip.call('brv_stoi_compact', sig[:B], sig[B:], lengths, B, L, comp[:B], comp[B:], out_stride, geom, energy, kept,
+             nf_max, 40.0, st)
     ncols = c['basis'].shape[1]
     spec = torch.empty(2*B, nf_max, ncols, dtype=torch.float32, device=dev)
     # frames are rows of the compacted signals 128 samples apart: one product for all items
-    hip.check(lib.brv_gemm_f32(
-        hip.ptr(comp), hip.ptr(c['basis']), hip.ptr(spec), 2*B, nf_max, ncols, _STOI_FRAME,
-        _STOI_FRAME//2, ncols, ncols, out_stride, 0, nf_max*ncols, 0, 0, 1, 0, 0, None, 0, st),
-        'brv_gemm_f32')
+    hip.call('brv_gemm_f32', comp, c['basis'], spec, 2*B, nf_max, ncols, _STOI_FRAME, _STOI_FRAME//2, ncols, ncols,
+             out_stride, 0, nf_max*ncols, 0, 0, 1, 0, 0, None, 0, st)
     tob = torch.empty(2*B, _STOI_BANDS, nf_max, dtype=torch.float32, device=dev)
-    hip.check(lib.brv_stoi_bands(hip.ptr(spec), hip.ptr(c['edges']), hip.ptr(tob), 2*B, nf_max,
-                                 ncols, c['bin0'], st), 'brv_stoi_bands')
+    hip.call('brv_stoi_bands', spec, c['edges'], tob, 2*B, nf_max, ncols, c['bin0'], st)
     partial = torch.empty(B, max(nf_max - 29, 1), dtype=torch.float32, device=dev)
     out = torch.empty(B, dtype=torch.float32, device=dev)
-    hip.check(lib.brv_stoi_correlate(
-        hip.ptr(tob[:B]), hip.ptr(tob[B:]), hip.ptr(geom), hip.ptr(partial), hip.ptr(out), B,
-        nf_max, int(bool(extended)), 10.0**(15.0/20.0), st), 'brv_stoi_correlate')
+    hip.call('brv_stoi_correlate', tob[:B], tob[B:], geom, partial, out, B, nf_max, int(bool(extended)),
+             10.0**(15.0/20.0), st)
     return out.double().cpu().numpy()
 
 

@@ -299,20 +299,16 @@ class ConvTasNet(BreverBaseModel):
         return hip.lib().brv_ctn_workspace_bytes(self._cfg_ptr(), 1, fs)
 
     def _check_layout(self):
-        lib = hip.lib()
-        n = lib.brv_ctn_param_count(self._cfg_ptr())
-        if n < 0:
-            hip.check(int(n), 'brv_ctn_param_count')
+        n = hip.query('brv_ctn_param_count', self._cfg_ptr())
         if n != self._flat.numel():
             raise RuntimeError(f'parameter layout mismatch: library expects {n} '
                                f'floats, module holds {self._flat.numel()}')
 
     def _prepare(self):
-        lib = hip.lib()
         hip.require_device(self._flat)
         if self._prepared is None:
             self._check_layout()
-            nbytes = lib.brv_ctn_prepared_bytes(self._cfg_ptr())
+            nbytes = hip.query('brv_ctn_prepared_bytes', self._cfg_ptr())
             self._prepared = torch.empty(nbytes, dtype=torch.uint8,
                                          device=self._flat.device)
             self._prepared_dirty = True
@@ -320,9 +316,7 @@ class ConvTasNet(BreverBaseModel):
         # [res | skip] weights, else the plain ones): a switch toggled on a live model prepares again
         opts = hip.launch_opts()
         if self._prepared_dirty or getattr(self, '_prepared_flags', None) != opts.flags:
-            hip.check(lib.brv_ctn_prepare(
-                self._cfg_ptr(), hip.ptr(self._flat), hip.ptr(self._prepared),
-                hip.opts_ptr(opts), hip.stream()), 'brv_ctn_prepare')
+            hip.call('brv_ctn_prepare', self._cfg_ptr(), self._flat, self._prepared, hip.opts_ptr(opts), hip.stream())
             self._prepared_dirty = False
             self._prepared_flags = opts.flags
 
@@ -331,11 +325,8 @@ class ConvTasNet(BreverBaseModel):
         amp = bool(amp)
         key = (B, L, self._flat.device)
         if self._ws_key.get(amp) != key:
-            fn = hip.lib().brv_ctn_workspace_bytes if amp \
-                else hip.lib().brv_ctn_f32_workspace_bytes
-            nbytes = fn(self._cfg_ptr(), B, L)
-            if nbytes < 0:
-                hip.check(int(nbytes), 'brv_ctn_workspace_bytes')
+            nbytes = hip.query('brv_ctn_workspace_bytes' if amp else 'brv_ctn_f32_workspace_bytes',
+                               self._cfg_ptr(), B, L)
             ws = self._workspace.get(amp)
             if ws is None or ws.numel() < nbytes \
                     or ws.device != self._flat.device:
@@ -386,16 +377,11 @@ class ConvTasNet(BreverBaseModel):
         if amp:
             self._prepare()
             opts = hip.launch_opts()
-            hip.check(hip.lib().brv_ctn_forward(
-                self._cfg_ptr(), hip.ptr(self._flat), hip.ptr(self._prepared),
-                hip.ptr(ws), hip.ptr(wave), wstride, hip.ptr(out), B, L, hip.opts_ptr(opts),
-                hip.stream()), 'brv_ctn_forward')
+            hip.call('brv_ctn_forward', self._cfg_ptr(), self._flat, self._prepared, ws, wave, wstride, out, B, L,
+                     hip.opts_ptr(opts), hip.stream())
         else:
             self._check_layout()
-            hip.check(hip.lib().brv_ctn_f32_forward(
-                self._cfg_ptr(), hip.ptr(self._flat), hip.ptr(ws),
-                hip.ptr(wave), hip.ptr(out), B, L, hip.stream()),
-                'brv_ctn_f32_forward')
+            hip.call('brv_ctn_f32_forward', self._cfg_ptr(), self._flat, ws, wave, out, B, L, hip.stream())
         self._ws_version[amp] += 1
         return out
 
@@ -406,9 +392,7 @@ class ConvTasNet(BreverBaseModel):
         out = []
         for part in range(nparts):
             off, cnt = ctypes.c_int64(0), ctypes.c_int64(0)
-            hip.check(hip.lib().brv_ctn_grad_bucket(
-                self._cfg_ptr(), part, nparts, ctypes.byref(off), ctypes.byref(cnt)),
-                'brv_ctn_grad_bucket')
+            hip.call('brv_ctn_grad_bucket', self._cfg_ptr(), part, nparts, ctypes.byref(off), ctypes.byref(cnt))
             out.append((off.value, cnt.value))
         return out
 
@@ -422,19 +406,14 @@ class ConvTasNet(BreverBaseModel):
         B, L = wave.shape
         ws = self._get_workspace(B, L, amp)
         buckets = self.grad_buckets(nparts) if after_part is not None else None
-        lib = hip.lib()
         opts = hip.launch_opts()
         for part in range(nparts):
             if amp:
-                hip.check(lib.brv_ctn_backward_part(
-                    self._cfg_ptr(), hip.ptr(self._flat), hip.ptr(self._prepared),
-                    hip.ptr(ws), hip.ptr(wave), wstride, hip.ptr(d_out), hip.ptr(flat_grad),
-                    B, L, part, nparts, hip.opts_ptr(opts), hip.stream()), 'brv_ctn_backward_part')
+                hip.call('brv_ctn_backward_part', self._cfg_ptr(), self._flat, self._prepared, ws, wave, wstride, d_out,
+                         flat_grad, B, L, part, nparts, hip.opts_ptr(opts), hip.stream())
             else:
-                hip.check(lib.brv_ctn_f32_backward_part(
-                    self._cfg_ptr(), hip.ptr(self._flat), hip.ptr(ws),
-                    hip.ptr(wave), hip.ptr(d_out), hip.ptr(flat_grad), B, L,
-                    part, nparts, hip.stream()), 'brv_ctn_f32_backward_part')
+                hip.call('brv_ctn_f32_backward_part', self._cfg_ptr(), self._flat, ws, wave, d_out, flat_grad, B, L,
+                         part, nparts, hip.stream())
             if after_part is not None:
                 off, cnt = buckets[part]
                 if cnt:
@@ -442,10 +421,7 @@ class ConvTasNet(BreverBaseModel):
 
     def workspace_tensor(self, name, index, B, L, shape, dtype):
         """View of a saved activation of the bf16 path (tests / profiling)."""
-        off = hip.lib().brv_ctn_workspace_offset(
-            self._cfg_ptr(), B, L, name.encode(), index)
-        if off < 0:
-            hip.check(int(off), 'brv_ctn_workspace_offset')
+        off = hip.query('brv_ctn_workspace_offset', self._cfg_ptr(), B, L, name.encode(), index)
         n = 1
         for s in shape:
             n *= s
@@ -518,7 +494,6 @@ class ConvTasNet(BreverBaseModel):
         if not fused:
             return super().train_step(batch, lengths, use_amp, scaler)
         # neither bf16 nor fp32 needs loss scaling: the GradScaler is left untouched
-        lib = hip.lib()
         inputs, labels = batch[:, 0], batch[:, 1:]
         hip.require_device(inputs, lengths)
         B, L = inputs.shape
@@ -532,16 +507,12 @@ class ConvTasNet(BreverBaseModel):
             labels, ybs, yss = self._label_rows(labels)
             lengths = lengths.to(torch.int64).contiguous()
             scratch, loss_b, gscale, d_out = self._step_buffers(B, S, L, out.device)
-            hip.check(lib.brv_snr_forward_strided(
-                hip.ptr(out), hip.ptr(labels), ybs, yss, hip.ptr(lengths), B, S, L, L,
-                hip.ptr(scratch), hip.ptr(loss_b), hip.stream()),
-                'brv_snr_forward_strided')
-            hip.check(lib.brv_snr_backward_strided(
-                hip.ptr(out), hip.ptr(labels), ybs, yss, hip.ptr(lengths), B, S, L, L,
-                hip.ptr(scratch), hip.ptr(gscale), hip.ptr(d_out), hip.stream()),
-                'brv_snr_backward_strided')
+            hip.call('brv_snr_forward_strided', out, labels, ybs, yss, lengths, B, S, L, L, scratch, loss_b,
+                     hip.stream())
+            hip.call('brv_snr_backward_strided', out, labels, ybs, yss, lengths, B, S, L, L, scratch, gscale, d_out,
+                     hip.stream())
             grads = self.flat_grads()
-            hip.check(lib.brv_memset_zero(hip.ptr(grads), 4*grads.numel(), hip.stream()), 'brv_memset_zero')
+            hip.call('brv_memset_zero', grads, 4*grads.numel(), hip.stream())
             sync = self._grad_sync
             grad_scale = 1.0
             if sync is not None and getattr(sync, 'nparts', 1) > 1:
@@ -555,7 +526,7 @@ class ConvTasNet(BreverBaseModel):
                     grad_scale = sync(grads)
             self.optimizer.step(max_norm=self.grad_clip, grad_scale=grad_scale)
             loss = torch.empty((), dtype=torch.float32, device=out.device)
-            hip.check(lib.brv_mean_f32(hip.ptr(loss_b), B, hip.ptr(loss), hip.stream()), 'brv_mean_f32')
+            hip.call('brv_mean_f32', loss_b, B, loss, hip.stream())
             return loss
 
     @staticmethod
@@ -579,7 +550,6 @@ class ConvTasNet(BreverBaseModel):
         arithmetic per item; the weight gradient is g(first half) + g(second half). Measured
         7.97 -> 7.65 ms per step (16 x 4 s), 7.45 ms with the persistent kernels at 7/8 of the CUs
         meanwhile; four chains: 10.4 ms. ``BRV_CTN_STREAMS=1``: one chain."""
-        lib = hip.lib()
         B, L = inputs.shape
         S = self.output_sources
         nB = self._chain_split(B)                 # items per chain (odd batches: the first takes one more)
@@ -600,7 +570,7 @@ class ConvTasNet(BreverBaseModel):
             opts = hip.launch_opts(cu_eighths=int(os.environ.get('BRV_CTN_CU_EIGHTHS', '7')))
             po = hip.opts_ptr(opts)
             streams = (main, side)
-            flat, prep, cfg = hip.ptr(self._flat), hip.ptr(self._prepared), self._cfg_ptr()
+            flat, prep, cfg = self._flat, self._prepared, self._cfg_ptr()
 
             def half(h):
                 sl = slice(0, nB[0]) if h == 0 else slice(nB[0], B)
@@ -612,22 +582,17 @@ class ConvTasNet(BreverBaseModel):
                     st = hip.stream()
                     if h == 1:
                         if not t['grad2_zero']:
-                            hip.check(lib.brv_memset_zero(hip.ptr(t['grad2']), 4*t['grad2'].numel(), st),
-                                      'brv_memset_zero')
+                            hip.call('brv_memset_zero', t['grad2'], 4*t['grad2'].numel(), st)
                         t['grad2_zero'] = False        # (until this step's sum pass has re-zeroed it)
-                    hip.check(lib.brv_ctn_forward(cfg, flat, prep, hip.ptr(t['ws'][h]), hip.ptr(x), wstride,
-                                                  hip.ptr(out), nB[h], L, po, st), 'brv_ctn_forward')
-                    hip.check(lib.brv_snr_forward_strided(
-                        hip.ptr(out), hip.ptr(y), ybs, yss, hip.ptr(ln), nB[h], S, L, L,
-                        hip.ptr(t['scratch'][h]), hip.ptr(loss_b), st), 'brv_snr_forward_strided')
-                    hip.check(lib.brv_snr_backward_strided(
-                        hip.ptr(out), hip.ptr(y), ybs, yss, hip.ptr(ln), nB[h], S, L, L,
-                        hip.ptr(t['scratch'][h]), hip.ptr(gscale), hip.ptr(d_out), st),
-                        'brv_snr_backward_strided')
+                    hip.call('brv_ctn_forward', cfg, flat, prep, t['ws'][h], x, wstride, out, nB[h], L, po, st)
+                    hip.call('brv_snr_forward_strided', out, y, ybs, yss, ln, nB[h], S, L, L, t['scratch'][h], loss_b,
+                             st)
+                    hip.call('brv_snr_backward_strided', out, y, ybs, yss, ln, nB[h], S, L, L, t['scratch'][h], gscale,
+                             d_out, st)
                     if h == 0:
                         # the first chain's gradient buffer, zeroed behind ITS forward (the other chain's kernels
                         # fill the chip meanwhile) instead of in the serial section in front of both chains
-                        hip.check(lib.brv_memset_zero(hip.ptr(grads), 4*grads.numel(), st), 'brv_memset_zero')
+                        hip.call('brv_memset_zero', grads, 4*grads.numel(), st)
             sync = self._grad_sync
             nparts = getattr(sync, 'nparts', 1) if sync is not None else 1
             buckets = self.grad_buckets(nparts) if nparts > 1 else [(0, grads.numel())]
@@ -635,18 +600,15 @@ class ConvTasNet(BreverBaseModel):
                 for h in (0, 1):
                     x, y, ln, out, d_out, loss_b, gscale = half(h)
                     with torch.cuda.stream(streams[h]):
-                        hip.check(lib.brv_ctn_backward_part(
-                            cfg, flat, prep, hip.ptr(t['ws'][h]), hip.ptr(x), wstride, hip.ptr(d_out),
-                            hip.ptr(grads if h == 0 else t['grad2']), nB[h], L, part, nparts, po, hip.stream()),
-                            'brv_ctn_backward_part')
+                        hip.call('brv_ctn_backward_part', cfg, flat, prep, t['ws'][h], x, wstride, d_out,
+                                 grads if h == 0 else t['grad2'], nB[h], L, part, nparts, po, hip.stream())
                 # this part's slice of the gradient is final in both halves
                 main.wait_stream(side)
                 off, cnt = buckets[part]
                 if cnt and nparts > 1:
                     # bucketed all-reduce: sum the slice now and hand it over while the next part's
                     # chains run (the second buffer is re-zeroed at the next step's start)
-                    hip.check(lib.brv_axpby(hip.ptr(grads[off:]), 1.0, hip.ptr(t['grad2'][off:]), 1.0,
-                                            hip.ptr(grads[off:]), cnt, hip.stream()), 'brv_axpby')
+                    hip.call('brv_axpby', grads[off:], 1.0, t['grad2'][off:], 1.0, grads[off:], cnt, hip.stream())
                     sync.bucket(part, grads[off:off + cnt])
             if nparts > 1:
                 grad_scale, second = sync.finish(), None
@@ -657,16 +619,14 @@ class ConvTasNet(BreverBaseModel):
                 if sync is None:
                     grad_scale = 1.0
                 else:
-                    hip.check(lib.brv_axpby(hip.ptr(grads), 1.0, hip.ptr(second), 1.0, hip.ptr(grads),
-                                            grads.numel(), hip.stream()), 'brv_axpby')
-                    hip.check(lib.brv_memset_zero(hip.ptr(second), 4*second.numel(), hip.stream()),
-                              'brv_memset_zero')
+                    hip.call('brv_axpby', grads, 1.0, second, 1.0, grads, grads.numel(), hip.stream())
+                    hip.call('brv_memset_zero', second, 4*second.numel(), hip.stream())
                     grad_scale, second = sync(grads), None
             self.optimizer.step(max_norm=self.grad_clip, grad_scale=grad_scale, grads2=second)
             # (only now: a failed launch above must not leave the buffer marked as zeroed)
             t['grad2_zero'] = nparts == 1
             loss = torch.empty((), dtype=torch.float32, device=dev)
-            hip.check(lib.brv_mean_f32(hip.ptr(t['loss']), B, hip.ptr(loss), hip.stream()), 'brv_mean_f32')
+            hip.call('brv_mean_f32', t['loss'], B, loss, hip.stream())
             return loss
 
     @staticmethod
@@ -684,13 +644,9 @@ class ConvTasNet(BreverBaseModel):
         workspace -- the buffer validation / ``enhance`` / odd batches use as a whole -- and the
         output / loss buffers are views of flat allocations that are replaced only by larger ones (the
         old reference is dropped first: no 2x peak). The side stream is created once."""
-        lib = hip.lib()
         Bh = max(self._chain_split(B))             # the larger part sizes both workspaces
-        nws = lib.brv_ctn_workspace_bytes(self._cfg_ptr(), Bh, L)
-        if nws < 0:
-            hip.check(int(nws), 'brv_ctn_workspace_bytes')
-        nws = (int(nws) + 255)//256*256
-        nscr = (int(lib.brv_loss_scratch_bytes(Bh, S)) + 255)//256*256
+        nws = (int(hip.query('brv_ctn_workspace_bytes', self._cfg_ptr(), Bh, L)) + 255)//256*256
+        nscr = (int(hip.lib().brv_loss_scratch_bytes(Bh, S)) + 255)//256*256
         t = self._two
         if t is None or t['dev'] != dev:
             t = self._two = dict(dev=dev, side=torch.cuda.Stream(device=dev), cap_out=0, cap_scr=0, cap_b=0,

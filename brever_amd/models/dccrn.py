@@ -138,18 +138,15 @@ def _gemm(a, b, d, batch, M, N, K, lda, ldb, ldd, a_bs, b_bs, d_bs, trans_a=0, t
     flags = int(b.dtype == torch.bfloat16) | int(d.dtype == torch.bfloat16) << 1
     if flags:
         assert lowp
-        hip.check(hip.lib().brv_gemm_bf16_mixed(
-            hip.ptr(a), hip.ptr(b), hip.ptr(d), batch, M, N, K, lda, ldb, ldd, a_bs, b_bs, d_bs,
-            trans_a, trans_b, kbatch, a_kbs, b_kbs, hip.ptr(bias), 0, flags, hip.stream()),
-            'brv_gemm_bf16_mixed')
+        hip.call('brv_gemm_bf16_mixed', a, b, d, batch, M, N, K, lda, ldb, ldd, a_bs, b_bs, d_bs, trans_a, trans_b,
+                 kbatch, a_kbs, b_kbs, bias, 0, flags, hip.stream())
         return
     if not lowp:
         hip.gemm_f32(a, b, d, batch, M, N, K, lda, ldb, ldd, a_bs, b_bs, d_bs, trans_a, trans_b, kbatch, a_kbs,
                      b_kbs, bias, 0)
         return
-    hip.check(hip.lib().brv_gemm_bf16(
-        hip.ptr(a), hip.ptr(b), hip.ptr(d), batch, M, N, K, lda, ldb, ldd, a_bs, b_bs, d_bs,
-        trans_a, trans_b, kbatch, a_kbs, b_kbs, hip.ptr(bias), 0, hip.stream()), 'brv_gemm_bf16')
+    hip.call('brv_gemm_bf16', a, b, d, batch, M, N, K, lda, ldb, ldd, a_bs, b_bs, d_bs, trans_a, trans_b, kbatch, a_kbs,
+             b_kbs, bias, 0, hip.stream())
 
 
 def _gemm_conv(a, img, d, batch, M, N, K, lda, ldd, a_bs, img_bs, d_bs, mode, image, geom, grid,
@@ -158,10 +155,9 @@ def _gemm_conv(a, img, d, batch, M, N, K, lda, ldd, a_bs, img_bs, d_bs, mode, im
     (``brv_gemm_bf16_conv``): ``image`` = (C, H, W) of ``img``, ``grid`` = the pixel grid of the
     columns; mode 1 = im2col, mode 2 = the gather form of col2im."""
     (kh, kw), (sh, sw), (ph, pw) = geom
-    hip.check(hip.lib().brv_gemm_bf16_conv(
-        hip.ptr(a), hip.ptr(img), hip.ptr(d), batch, M, N, K, lda, ldd, a_bs, img_bs, d_bs, 0, trans_b,
-        kbatch, a_kbs, img_kbs, hip.ptr(bias), 0, mode, image[0], image[1], image[2], kh, kw, sh, sw,
-        ph, pw, grid[0], grid[1], hip.stream()), 'brv_gemm_bf16_conv')
+    hip.call('brv_gemm_bf16_conv', a, img, d, batch, M, N, K, lda, ldd, a_bs, img_bs, d_bs, 0, trans_b, kbatch, a_kbs,
+             img_kbs, bias, 0, mode, image[0], image[1], image[2], kh, kw, sh, sw, ph, pw, grid[0], grid[1],
+             hip.stream())
 
 
 _IMPLICIT = os.environ.get('BRV_DCCRN_IM2COL', '0') != '1'     # use_amp: implicit GEMM convolutions
@@ -185,14 +181,12 @@ def _cconv_rows(x, wc, bias, M, m_stride, c_stride, transposed, x2=None, split_o
         seg, C = C//2, 2*C
     if wp is None:       # (``wp``: the fragments of this reading of ``wc``, packed already -- _pack_complex_layer)
         wp = torch.empty(lib.brv_cconv_packed_bytes(M, C), dtype=torch.uint8, device=x.device)
-        hip.check(lib.brv_cconv_pack(hip.ptr(wc), hip.ptr(wp), M, C, m_stride, c_stride, hip.stream()),
-                  'brv_cconv_pack')
+        hip.call('brv_cconv_pack', wc, wp, M, C, m_stride, c_stride, hip.stream())
     shape = (B, M//2 if split_out else M) + ((2*H, W + 1) if transposed else (H//2, W - 1))
     out = torch.empty(shape, dtype=torch.float32, device=x.device)
     out2 = torch.empty_like(out) if split_out else None
-    hip.check(lib.brv_cconv_rows(hip.ptr(x), hip.ptr(x2), seg, hip.ptr(wp), hip.ptr(bias), hip.ptr(out),
-                                 hip.ptr(out2), M//4 if split_out else 0, B, C, M, H, W, int(transposed),
-                                 hip.stream()), 'brv_cconv_rows')
+    hip.call('brv_cconv_rows', x, x2, seg, wp, bias, out, out2, M//4 if split_out else 0, B, C, M, H, W,
+             int(transposed), hip.stream())
     return (out, out2) if split_out else out
 
 
@@ -207,10 +201,8 @@ def _pack_complex_layer(wr, wi, br, bi, sign, fwd, bwd):
     wp1 = torch.empty(lib.brv_cconv_packed_bytes(fwd[0], fwd[1]), dtype=torch.uint8, device=dev)
     wp2 = torch.empty(lib.brv_cconv_packed_bytes(bwd[0], bwd[1]), dtype=torch.uint8, device=dev) if bwd else None
     wr_c, wi_c, br_c, bi_c = wr.contiguous(), wi.contiguous(), br.contiguous(), bi.contiguous()
-    hip.check(lib.brv_cconv_pack_complex(
-        hip.ptr(wr_c), hip.ptr(wi_c), hip.ptr(br_c), hip.ptr(bi_c), R, Cw, br.numel(), float(sign), hip.ptr(wc),
-        hip.ptr(bias), hip.ptr(wp1), *fwd, hip.ptr(wp2), *(bwd or (0, 0, 0, 0)), hip.stream()),
-        'brv_cconv_pack_complex')
+    hip.call('brv_cconv_pack_complex', wr_c, wi_c, br_c, bi_c, R, Cw, br.numel(), float(sign), wc, bias, wp1, *fwd, wp2,
+             *(bwd or (0, 0, 0, 0)), hip.stream())
     return wc, bias, wp1, wp2
 
 
@@ -228,10 +220,8 @@ def _cconv_wgrad(small, big, small2=None):
     assert small.dtype == big.dtype and (small2 is None or small2.dtype == big.dtype)
     # (the LDS-DMA kernel fetches whole 16-byte pieces around the images' ends: include/brever_hip.h)
     assert not lowp or all(_has_slack(t) for t in (small, small2, big) if t is not None), 'bf16 image without slack'
-    fn, name = (hip.lib().brv_cconv_wgrad_bf16, 'brv_cconv_wgrad_bf16') if lowp else \
-        (hip.lib().brv_cconv_wgrad, 'brv_cconv_wgrad')
-    hip.check(fn(hip.ptr(small), hip.ptr(small2), hip.ptr(big), hip.ptr(out), hip.ptr(ws),
-                 B, A, C, Hs, Ws, seg, hip.stream()), name)
+    hip.call('brv_cconv_wgrad_bf16' if lowp else 'brv_cconv_wgrad', small, small2, big, out, ws,
+             B, A, C, Hs, Ws, seg, hip.stream())
     return out
 
 
@@ -277,10 +267,8 @@ def _im2col(x, geom, grid, lowp=False):
     B, C, H, W = x.shape
     col = torch.empty(B, C*kh*kw, grid[0]*grid[1], dtype=torch.bfloat16 if lowp else torch.float32,
                       device=x.device)
-    fn, name = (hip.lib().brv_im2col_bf16, 'brv_im2col_bf16') if lowp else \
-        (hip.lib().brv_im2col, 'brv_im2col')
-    hip.check(fn(hip.ptr(x), hip.ptr(col), B, C, H, W, kh, kw, sh, sw, ph, pw, grid[0], grid[1],
-                 hip.stream()), name)
+    hip.call('brv_im2col_bf16' if lowp else 'brv_im2col', x, col, B, C, H, W, kh, kw, sh, sw, ph, pw,
+             grid[0], grid[1], hip.stream())
     return col
 
 
@@ -288,17 +276,14 @@ def _col2im(col, bias, C, image, geom, grid):
     (kh, kw), (sh, sw), (ph, pw) = geom
     B = col.shape[0]
     y = torch.empty(B, C, image[0], image[1], dtype=torch.float32, device=col.device)
-    fn, name = (hip.lib().brv_col2im_bf16, 'brv_col2im_bf16') if col.dtype == torch.bfloat16 else \
-        (hip.lib().brv_col2im, 'brv_col2im')
-    hip.check(fn(hip.ptr(col), hip.ptr(bias), hip.ptr(y), B, C, image[0], image[1], kh, kw, sh, sw,
-                 ph, pw, grid[0], grid[1], hip.stream()), name)
+    hip.call('brv_col2im_bf16' if col.dtype == torch.bfloat16 else 'brv_col2im', col, bias, y, B, C,
+             image[0], image[1], kh, kw, sh, sw, ph, pw, grid[0], grid[1], hip.stream())
     return y
 
 
 def _combine(a, b, sign):
     out = torch.empty_like(a)
-    hip.check(hip.lib().brv_combine(hip.ptr(a), hip.ptr(b), hip.ptr(out), a.numel(), float(sign),
-                                    hip.stream()), 'brv_combine')
+    hip.call('brv_combine', a, b, out, a.numel(), float(sign), hip.stream())
     return out
 
 
@@ -319,7 +304,6 @@ class _ComplexConvFunction(torch.autograd.Function):
         (dccrn.py:213-217); the row kernels read the two tensors in place."""
         (kh, kw), (sh, sw), (ph, pw), (oph, opw) = geom4
         geom = geom4[:3]
-        lib = hip.lib()
         lowp = ctx.lowp = _AMP['on']
         ctx.side_ok = _side_allowed((wr, br, wi, bi))
         kept_col = None
@@ -352,13 +336,10 @@ class _ComplexConvFunction(torch.autograd.Function):
         else:
             wc = torch.empty(2*R, 2*Cw, dtype=torch.float32, device=x.device)
             wr_c, wi_c = wr.contiguous(), wi.contiguous()      # alive until the launch is queued
-            hip.check(lib.brv_complex_weight_pack(hip.ptr(wr_c), hip.ptr(wi_c),
-                                                  hip.ptr(wc), R, Cw, -1.0 if transpose else 1.0,
-                                                  hip.stream()), 'brv_complex_weight_pack')
+            hip.call('brv_complex_weight_pack', wr_c, wi_c, wc, R, Cw, -1.0 if transpose else 1.0, hip.stream())
             bias = torch.empty(2*br.numel(), dtype=torch.float32, device=x.device)
             br_c, bi_c = br.contiguous(), bi.contiguous()
-            hip.check(lib.brv_complex_bias_pack(hip.ptr(br_c), hip.ptr(bi_c), hip.ptr(bias), br.numel(),
-                                                hip.stream()), 'brv_complex_bias_pack')
+            hip.call('brv_complex_bias_pack', br_c, bi_c, bias, br.numel(), hip.stream())
         if rows and not transpose:
             Ho, Wo = H//2, W - 1
             y = _cconv_rows(x, wc, bias, 2*Cout, 2*Cw, khw, 0, wp=wp_fwd)
@@ -400,24 +381,18 @@ class _ComplexConvFunction(torch.autograd.Function):
     @staticmethod
     def _unpack_param_grads(dwc, dy, wshape, R, Cw, Cout, B, HoWo, transpose):
         """dwc (2R, 2Cw) -> (d Wr, d Wi); channel sums of dy -> (d br, d bi) (bias = [br - bi | br + bi])."""
-        lib = hip.lib()
         dwr = torch.empty(wshape, dtype=torch.float32, device=dy.device)
         dwi = torch.empty_like(dwr)
-        hip.check(lib.brv_complex_weight_unpack(hip.ptr(dwc), hip.ptr(dwr), hip.ptr(dwi), R, Cw,
-                                                -1.0 if transpose else 1.0, hip.stream()),
-                  'brv_complex_weight_unpack')
+        hip.call('brv_complex_weight_unpack', dwc, dwr, dwi, R, Cw, -1.0 if transpose else 1.0, hip.stream())
         sums = torch.empty(2*Cout, dtype=torch.float32, device=dy.device)
-        hip.check(lib.brv_row_sum(hip.ptr(dy), hip.ptr(sums), B, 2*Cout, HoWo, hip.stream()),
-                  'brv_row_sum')
+        hip.call('brv_row_sum', dy, sums, B, 2*Cout, HoWo, hip.stream())
         dbr = torch.empty(Cout, dtype=torch.float32, device=dy.device)
         dbi = torch.empty_like(dbr)
-        hip.check(lib.brv_complex_bias_unpack(hip.ptr(sums), hip.ptr(dbr), hip.ptr(dbi), Cout, hip.stream()),
-                  'brv_complex_bias_unpack')
+        hip.call('brv_complex_bias_unpack', sums, dbr, dbi, Cout, hip.stream())
         return dwr, dwi, dbr, dbi
 
     @staticmethod
     def backward(ctx, dy):
-        lib = hip.lib()
         x, wc = ctx.saved_tensors[:2]
         skip = ctx.saved_tensors[2] if ctx.two else None
         geom, transpose, (H, W), (Ho, Wo), Cin, Cout, R, Cw, wshape = ctx.cfg
@@ -518,8 +493,7 @@ class _CombineFunction(torch.autograd.Function):
     def forward(ctx, a, b, sign):
         a, b = a.contiguous(), b.contiguous()
         out = torch.empty_like(a)
-        hip.check(hip.lib().brv_combine(hip.ptr(a), hip.ptr(b), hip.ptr(out), a.numel(),
-                                        float(sign), hip.stream()), 'brv_combine')
+        hip.call('brv_combine', a, b, out, a.numel(), float(sign), hip.stream())
         ctx.sign = float(sign)
         return out
 
@@ -539,8 +513,7 @@ class _ComplexMixFunction(torch.autograd.Function):
         assert G == 2 and B2 % 2 == 0
         real = torch.empty(B2//2, T, H, dtype=torch.float32, device=out.device)
         imag = torch.empty_like(real)
-        hip.check(hip.lib().brv_complex_mix_forward(hip.ptr(out), hip.ptr(real), hip.ptr(imag), real.numel(),
-                                                    hip.stream()), 'brv_complex_mix_forward')
+        hip.call('brv_complex_mix_forward', out, real, imag, real.numel(), hip.stream())
         ctx.shape = out.shape
         return real, imag
 
@@ -548,8 +521,7 @@ class _ComplexMixFunction(torch.autograd.Function):
     def backward(ctx, greal, gimag):
         greal, gimag = greal.contiguous(), gimag.contiguous()
         dout = torch.empty(ctx.shape, dtype=torch.float32, device=greal.device)
-        hip.check(hip.lib().brv_complex_mix_backward(hip.ptr(greal), hip.ptr(gimag), hip.ptr(dout), greal.numel(),
-                                                     hip.stream()), 'brv_complex_mix_backward')
+        hip.call('brv_complex_mix_backward', greal, gimag, dout, greal.numel(), hip.stream())
         return dout
 
 
@@ -591,11 +563,8 @@ class _BatchNormActFunction(torch.autograd.Function):
         y = torch.empty_like(x)
         mean = torch.empty(C, dtype=torch.float32, device=x.device)
         invstd = torch.empty_like(mean)
-        hip.check(hip.lib().brv_batchnorm2d_forward(
-            hip.ptr(x), hip.ptr(gamma), hip.ptr(beta), hip.ptr(norm.running_mean),
-            hip.ptr(norm.running_var), hip.ptr(slope), hip.ptr(y), hip.ptr(mean), hip.ptr(invstd),
-            B, C, H*W, float(norm.eps), float(norm.momentum), int(training), hip.stream()),
-            'brv_batchnorm2d_forward')
+        hip.call('brv_batchnorm2d_forward', x, gamma, beta, norm.running_mean, norm.running_var, slope, y, mean, invstd,
+                 B, C, H*W, float(norm.eps), float(norm.momentum), int(training), hip.stream())
         if training:
             _BN_COUNTERS.append(norm.num_batches_tracked)      # (+= 1 for all layers in one launch: _flush_bn_counters)
         ctx.save_for_backward(x, gamma, beta, slope if slope is not None else gamma.new_zeros(0),
@@ -615,15 +584,12 @@ class _BatchNormActFunction(torch.autograd.Function):
         dx = torch.empty_like(x)
         dgamma, dbeta, dsl = (torch.empty(C, dtype=torch.float32, device=x.device)
                               for _ in range(3))
-        hip.check(hip.lib().brv_batchnorm2d_backward(
-            hip.ptr(x), hip.ptr(dy), hip.ptr(mean), hip.ptr(invstd), hip.ptr(gamma), hip.ptr(beta),
-            hip.ptr(slope) if has_slope else None, hip.ptr(dx), hip.ptr(dgamma), hip.ptr(dbeta),
-            hip.ptr(dsl), B, C, H*W, hip.stream()), 'brv_batchnorm2d_backward')
+        hip.call('brv_batchnorm2d_backward', x, dy, mean, invstd, gamma, beta, slope if has_slope else None, dx, dgamma,
+                 dbeta, dsl, B, C, H*W, hip.stream())
         dslope = None
         if has_slope:
             tot = torch.empty(1, dtype=torch.float32, device=x.device)
-            hip.check(hip.lib().brv_row_sum(hip.ptr(dsl), hip.ptr(tot), 1, 1, C, hip.stream()),
-                      'brv_row_sum')
+            hip.call('brv_row_sum', dsl, tot, 1, 1, C, hip.stream())
             dslope = tot
         return dx, dgamma, dbeta, dslope, None, None
 
@@ -689,7 +655,6 @@ class _BlockFunction(torch.autograd.Function):
         """``two_out``: a second token for the block's second consumer (an encoder output feeds the next block AND the
         decoder's skip input, dccrn.py:205-217): the two gradients arrive separately and the norm's backward pass adds
         them on the fly (``brv_batchnorm2d_backward_ex``: no pass that sums them)."""
-        lib = hip.lib()
         (kh, kw) = geom4[0]
         khw = kh*kw
         dev = x.device
@@ -720,9 +685,8 @@ class _BlockFunction(torch.autograd.Function):
         Ho, Wo = (2*H, W + 1) if transpose else (H//2, W - 1)
         y16 = ctx.y16 = bool(_BF16_Y and norm is not None and out_bf16 and not first)
         y = torch.empty(B, 2*Cout, Ho, Wo, dtype=torch.bfloat16 if y16 else torch.float32, device=dev)
-        hip.check(lib.brv_cconv_rows_ex(hip.ptr(x16), hip.ptr(skip16), seg, hip.ptr(wp_fwd), hip.ptr(bias),
-                                        hip.ptr(y), None, 0, B, Cin2, 2*Cout, H, W, int(transpose), int(not first),
-                                        int(y16), hip.stream()), 'brv_cconv_rows_ex')
+        hip.call('brv_cconv_rows_ex', x16, skip16, seg, wp_fwd, bias, y, None, 0, B, Cin2, 2*Cout, H, W, int(transpose),
+                 int(not first), int(y16), hip.stream())
         assert first or (_has_slack(x16) and (skip16 is None or _has_slack(skip16))), 'bf16 image without slack'
         ctx.dx_bf16 = x.dtype == torch.bfloat16          # (the input is the bf16 token of a block: its gradient is bf16)
         assert not two or skip.dtype == x.dtype
@@ -735,14 +699,11 @@ class _BlockFunction(torch.autograd.Function):
             return y, None
         mean = torch.empty(2*Cout, dtype=torch.float32, device=dev)
         invstd = torch.empty_like(mean)
-        args = (hip.ptr(y), hip.ptr(gamma), hip.ptr(beta), hip.ptr(norm.running_mean), hip.ptr(norm.running_var),
-                hip.ptr(slope))
-        tail = (hip.ptr(mean), hip.ptr(invstd), B, 2*Cout, Ho*Wo, float(norm.eps), float(norm.momentum),
-                int(training), hip.stream())
+        args = (y, gamma, beta, norm.running_mean, norm.running_var, slope)
+        tail = (mean, invstd, B, 2*Cout, Ho*Wo, float(norm.eps), float(norm.momentum), int(training), hip.stream())
         if out_bf16:
             a16 = _bf16_empty((B, 2*Cout, Ho, Wo), dev)
-            fwd_fn = lib.brv_batchnorm2d_forward_bf16io if y16 else lib.brv_batchnorm2d_forward_bf16
-            hip.check(fwd_fn(*args, hip.ptr(a16), *tail), 'brv_batchnorm2d_forward_bf16[io]')
+            hip.call('brv_batchnorm2d_forward_bf16io' if y16 else 'brv_batchnorm2d_forward_bf16', *args, a16, *tail)
             # (bf16 gradients need every encoder output to hand out one token per consumer: a forked token's two
             # gradients are summed by an fp32 pass)
             tdt = torch.bfloat16 if (_BF16_GRAD and _TWO_TOKENS) else torch.float32
@@ -750,7 +711,7 @@ class _BlockFunction(torch.autograd.Function):
             ctx.mark_non_differentiable(a16)
         else:
             a = torch.empty_like(y)
-            hip.check(lib.brv_batchnorm2d_forward(*args, hip.ptr(a), *tail), 'brv_batchnorm2d_forward')
+            hip.call('brv_batchnorm2d_forward', *args, a, *tail)
             out = (a, None)
         if training:
             _BN_COUNTERS.append(norm.num_batches_tracked)
@@ -761,7 +722,6 @@ class _BlockFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g, _g16=None, g2=None):
-        lib = hip.lib()
         if g is None:
             g, g2 = g2, None
         if g is None:                       # nothing downstream asked for a gradient
@@ -788,15 +748,12 @@ class _BlockFunction(torch.autograd.Function):
             dy = torch.empty_like(y) if small_cin else None
             dy16 = None if small_cin else _bf16_empty(y.shape, dev)
             assert g2 is None or g2.dtype == g.dtype
-            hip.check(lib.brv_batchnorm2d_backward_ex(
-                hip.ptr(y), int(ctx.y16), hip.ptr(g), hip.ptr(g2), int(g.dtype == torch.bfloat16), hip.ptr(mean),
-                hip.ptr(invstd), hip.ptr(gamma),
-                hip.ptr(beta), hip.ptr(slope), hip.ptr(dy if small_cin else dy16), int(not small_cin), hip.ptr(dgamma),
-                hip.ptr(dbeta), hip.ptr(dsl), None if small_cin else hip.ptr(sums), B, 2*Cout, Ho*Wo, hip.stream()),
-                'brv_batchnorm2d_backward_ex')
+            hip.call('brv_batchnorm2d_backward_ex', y, int(ctx.y16), g, g2, int(g.dtype == torch.bfloat16), mean,
+                     invstd, gamma, beta, slope, dy if small_cin else dy16, int(not small_cin), dgamma, dbeta, dsl,
+                     None if small_cin else sums, B, 2*Cout, Ho*Wo, hip.stream())
             if ctx.has_slope:
                 dslope = torch.empty(1, dtype=torch.float32, device=dev)
-                hip.check(lib.brv_row_sum(hip.ptr(dsl), hip.ptr(dslope), 1, 1, 2*Cout, hip.stream()), 'brv_row_sum')
+                hip.call('brv_row_sum', dsl, dslope, 1, 1, 2*Cout, hip.stream())
         else:
             dy, dy16 = g, _as_bf16(g)
 
@@ -813,16 +770,13 @@ class _BlockFunction(torch.autograd.Function):
             else:
                 dwc = _cconv_wgrad(dy16, x16)
             if dy is not None:          # (no norm behind the convolution: the sums of the fp32 gradient)
-                hip.check(lib.brv_row_sum(hip.ptr(dy), hip.ptr(sums), B, 2*Cout, Ho*Wo, hip.stream()), 'brv_row_sum')
+                hip.call('brv_row_sum', dy, sums, B, 2*Cout, Ho*Wo, hip.stream())
             dwr = torch.empty(wshape, dtype=torch.float32, device=dev)
             dwi = torch.empty_like(dwr)
-            hip.check(lib.brv_complex_weight_unpack(hip.ptr(dwc), hip.ptr(dwr), hip.ptr(dwi), R, Cw,
-                                                    -1.0 if transpose else 1.0, hip.stream()),
-                      'brv_complex_weight_unpack')
+            hip.call('brv_complex_weight_unpack', dwc, dwr, dwi, R, Cw, -1.0 if transpose else 1.0, hip.stream())
             dbr = torch.empty(Cout, dtype=torch.float32, device=dev)
             dbi = torch.empty_like(dbr)
-            hip.check(lib.brv_complex_bias_unpack(hip.ptr(sums), hip.ptr(dbr), hip.ptr(dbi), Cout, hip.stream()),
-                      'brv_complex_bias_unpack')
+            hip.call('brv_complex_bias_unpack', sums, dbr, dbi, Cout, hip.stream())
             return dwr, dwi, dbr, dbi
 
         side = _side_stream(dev) if ctx.side_ok else None
@@ -838,9 +792,8 @@ class _BlockFunction(torch.autograd.Function):
             dx = torch.empty(shape, dtype=torch.bfloat16 if ctx.dx_bf16 else torch.float32, device=dev)
             dskip = torch.empty_like(dx) if two else None
             # the data gradient of a (transposed) convolution is the other form with the same weights
-            hip.check(lib.brv_cconv_rows_ex(hip.ptr(src), None, 0, hip.ptr(ctx.wp_bwd), None, hip.ptr(dx),
-                                            hip.ptr(dskip), M//4 if two else 0, B, 2*Cout, M, Ho, Wo,
-                                            int(not transpose), 1, int(ctx.dx_bf16), hip.stream()), 'brv_cconv_rows_ex')
+            hip.call('brv_cconv_rows_ex', src, None, 0, ctx.wp_bwd, None, dx, dskip, M//4 if two else 0, B, 2*Cout, M,
+                     Ho, Wo, int(not transpose), 1, int(ctx.dx_bf16), hip.stream())
         if side is None:
             dwr, dwi, dbr, dbi = param_grads()
         else:
@@ -863,8 +816,7 @@ class _CplxMomentsFunction(torch.autograd.Function):
         x = x.contiguous()
         B, C2, H, W = x.shape
         m = torch.empty(5, C2//2, dtype=torch.float32, device=x.device)
-        hip.check(hip.lib().brv_cplx_moments(hip.ptr(x), hip.ptr(m), B, C2//2, H*W, hip.stream()),
-                  'brv_cplx_moments')
+        hip.call('brv_cplx_moments', x, m, B, C2//2, H*W, hip.stream())
         ctx.save_for_backward(x)
         return m
 
@@ -874,8 +826,7 @@ class _CplxMomentsFunction(torch.autograd.Function):
         B, C2, H, W = x.shape
         gm = (gm.float()/(B*H*W)).contiguous()
         dx = torch.empty_like(x)
-        hip.check(hip.lib().brv_cplx_moments_backward(hip.ptr(x), hip.ptr(gm), hip.ptr(dx), B, C2//2,
-                                                      H*W, hip.stream()), 'brv_cplx_moments_backward')
+        hip.call('brv_cplx_moments_backward', x, gm, dx, B, C2//2, H*W, hip.stream())
         return dx
 
 
@@ -887,9 +838,7 @@ class _CplxAffineFunction(torch.autograd.Function):
         x, A, o = x.contiguous(), A.contiguous(), o.contiguous()
         B, C2, H, W = x.shape
         y = torch.empty_like(x)
-        hip.check(hip.lib().brv_cplx_affine_forward(hip.ptr(x), hip.ptr(A), hip.ptr(o), hip.ptr(slope),
-                                                    hip.ptr(y), B, C2//2, H*W, hip.stream()),
-                  'brv_cplx_affine_forward')
+        hip.call('brv_cplx_affine_forward', x, A, o, slope, y, B, C2//2, H*W, hip.stream())
         ctx.save_for_backward(x, A, o, slope if slope is not None else A.new_zeros(0))
         return y
 
@@ -903,15 +852,12 @@ class _CplxAffineFunction(torch.autograd.Function):
         dx = torch.empty_like(x)
         dA, do = torch.empty_like(A), torch.empty_like(o)
         dsl = torch.empty(C, dtype=torch.float32, device=x.device)
-        hip.check(hip.lib().brv_cplx_affine_backward(
-            hip.ptr(x), hip.ptr(dy), hip.ptr(A), hip.ptr(o), hip.ptr(slope) if has_slope else None,
-            hip.ptr(dx), hip.ptr(dA), hip.ptr(do), hip.ptr(dsl), B, C, H*W, hip.stream()),
-            'brv_cplx_affine_backward')
+        hip.call('brv_cplx_affine_backward', x, dy, A, o, slope if has_slope else None, dx, dA, do, dsl, B, C, H*W,
+                 hip.stream())
         dslope = None
         if has_slope:
             dslope = torch.empty(1, dtype=torch.float32, device=x.device)
-            hip.check(hip.lib().brv_row_sum(hip.ptr(dsl), hip.ptr(dslope), 1, 1, C, hip.stream()),
-                      'brv_row_sum')
+            hip.call('brv_row_sum', dsl, dslope, 1, 1, C, hip.stream())
         return dx, dA, do, dslope
 
 
@@ -997,12 +943,10 @@ class _LSTMFunction(torch.autograd.Function):
         cs = torch.empty(G, B, T, H, dtype=torch.float32, device=x.device)
         # use_amp, few long chains: the step's matrix-vector product on the bf16 MFMA (csrc/dccrn.hip lstm_*_mv_kernel)
         mv = ctx.mv = bool(lowp and not tiled and _LSTM_MV and lib.brv_lstm_recurrent_bf16_supported(H))
-        fn, name = (lib.brv_lstm_tile_forward, 'brv_lstm_tile_forward') if tiled else \
-            (lib.brv_lstm_recurrent_forward_bf16, 'brv_lstm_recurrent_forward_bf16') if mv else \
-            (lib.brv_lstm_recurrent_forward, 'brv_lstm_recurrent_forward')
+        name = 'brv_lstm_tile_forward' if tiled else \
+            'brv_lstm_recurrent_forward_bf16' if mv else 'brv_lstm_recurrent_forward'
         extra = (0, H, B*T*H, int(lowp)) if tiled else ()   # no reversed group, (G, B, T, H) output
-        hip.check(fn(hip.ptr(gates), hip.ptr(w_hh), hip.ptr(bias), hip.ptr(y), hip.ptr(act),
-                     hip.ptr(cs), G*B, T, H, G, *extra, hip.stream()), name)
+        hip.call(name, gates, w_hh, bias, y, act, cs, G*B, T, H, G, *extra, hip.stream())
         ctx.save_for_backward(x, w_ih, w_hh, y, act, cs)
         return y
 
@@ -1018,12 +962,10 @@ class _LSTMFunction(torch.autograd.Function):
         lowp = ctx.lowp
         dy = dy.contiguous()
         dg = torch.empty(G, B, T, 4*H, dtype=torch.float32, device=x.device)
-        fn, name = (lib.brv_lstm_tile_backward, 'brv_lstm_tile_backward') if ctx.tiled else \
-            (lib.brv_lstm_recurrent_backward_bf16, 'brv_lstm_recurrent_backward_bf16') if ctx.mv else \
-            (lib.brv_lstm_recurrent_backward, 'brv_lstm_recurrent_backward')
+        name = 'brv_lstm_tile_backward' if ctx.tiled else \
+            'brv_lstm_recurrent_backward_bf16' if ctx.mv else 'brv_lstm_recurrent_backward'
         extra = (0, H, B*T*H, int(lowp)) if ctx.tiled else ()
-        hip.check(fn(hip.ptr(act), hip.ptr(cs), hip.ptr(w_hh), hip.ptr(dy), hip.ptr(dg), G*B, T, H,
-                     G, *extra, hip.stream()), name)
+        hip.call(name, act, cs, w_hh, dy, dg, G*B, T, H, G, *extra, hip.stream())
         BT = B*T
         dx = torch.empty_like(x)                                   # dg (BT, 4H) @ W_ih (4H, I)
         if shared:                                                 # (summed over the groups: they are the k-batches)
@@ -1043,8 +985,7 @@ class _LSTMFunction(torch.autograd.Function):
         # bias gradients: column sums of dg (BT, 4H) per group, in a fixed order (no transposed copy)
         db = torch.empty(G, 4*H, dtype=torch.float32, device=x.device)
         scratch = torch.empty(lib.brv_col_sum_scratch_bytes(G, 4*H), dtype=torch.uint8, device=x.device)
-        hip.check(lib.brv_col_sum(hip.ptr(dg), hip.ptr(db), hip.ptr(scratch), G, BT, 4*H, hip.stream()),
-                  'brv_col_sum')
+        hip.call('brv_col_sum', dg, db, scratch, G, BT, 4*H, hip.stream())
         if ctx.tiled:
             dw_ih, dw_hh, db = (_LSTMFunction._deinterleave(t, H) for t in (dw_ih, dw_hh, db))
         return dx, dw_ih, dw_hh, db, db.clone()
@@ -1078,7 +1019,7 @@ class _LinearLowpFunction(torch.autograd.Function):
         dw = torch.empty_like(weight)                      # sum_b dy[b] (O, T) @ x[b]^T (T, I)
         _gemm(dy, x, dw, 1, O, I, T, T, T, I, 0, 0, 0, trans_b=1, kbatch=B, a_kbs=O*T, b_kbs=I*T, lowp=True)
         db = torch.empty(O, dtype=torch.float32, device=x.device)
-        hip.check(hip.lib().brv_row_sum(hip.ptr(dy), hip.ptr(db), B, O, T, hip.stream()), 'brv_row_sum')
+        hip.call('brv_row_sum', dy, db, B, O, T, hip.stream())
         return dx, dw, db
 
 
@@ -1116,7 +1057,7 @@ class _ComplexLinearFunction(torch.autograd.Function):
             _gemm(d, x, dw, 1, F_, H, T, T, H, H, 0, 0, 0, kbatch=B, a_kbs=2*F_*T, b_kbs=T*H, lowp=lowp)
             grads.append((dx, dw))
         sums = torch.empty(2*F_, dtype=torch.float32, device=dy.device)
-        hip.check(hip.lib().brv_row_sum(hip.ptr(dy), hip.ptr(sums), B, 2*F_, T, hip.stream()), 'brv_row_sum')
+        hip.call('brv_row_sum', dy, sums, B, 2*F_, T, hip.stream())
         return grads[0][0], grads[1][0], grads[0][1], sums[:F_], grads[1][1], sums[F_:], None
 
 
@@ -1129,8 +1070,7 @@ class _ApplyMaskFunction(torch.autograd.Function):
         B, _, Fq, T = x.shape
         n = Fq*T
         out = torch.empty(B, n, 2, dtype=torch.float32, device=x.device)
-        hip.check(hip.lib().brv_dccrn_apply_mask_batched(hip.ptr(x), hip.ptr(mask), hip.ptr(out), B, n,
-                                                         hip.stream()), 'brv_dccrn_apply_mask_batched')
+        hip.call('brv_dccrn_apply_mask_batched', x, mask, out, B, n, hip.stream())
         ctx.save_for_backward(x, mask)
         return torch.view_as_complex(out.view(B, 1, Fq, T, 2))
 
@@ -1141,9 +1081,7 @@ class _ApplyMaskFunction(torch.autograd.Function):
         n = Fq*T
         gr = torch.view_as_real(g.to(torch.complex64).contiguous()).view(B, n, 2)
         dm = torch.empty_like(mask)
-        hip.check(hip.lib().brv_dccrn_apply_mask_backward_batched(
-            hip.ptr(x), hip.ptr(mask), hip.ptr(gr), hip.ptr(dm), B, n, hip.stream()),
-            'brv_dccrn_apply_mask_backward_batched')
+        hip.call('brv_dccrn_apply_mask_backward_batched', x, mask, gr, dm, B, n, hip.stream())
         return None, dm
 
 

@@ -30,10 +30,8 @@ eps = np.finfo(float).eps        # ffnn.py:12
 
 def _gemm(a, b, d, batch, M, N, K, lda, ldb, ldd, a_bs, b_bs, d_bs, trans_a=0, trans_b=0,
           kbatch=1, a_kbs=0, b_kbs=0, bias=None, accumulate=0):
-    hip.check(hip.lib().brv_gemm_f32(
-        hip.ptr(a), hip.ptr(b), hip.ptr(d), batch, M, N, K, lda, ldb, ldd, a_bs, b_bs, d_bs,
-        trans_a, trans_b, kbatch, a_kbs, b_kbs, hip.ptr(bias), accumulate, hip.stream()),
-        'brv_gemm_f32')
+    hip.call('brv_gemm_f32', a, b, d, batch, M, N, K, lda, ldb, ldd, a_bs, b_bs, d_bs, trans_a, trans_b, kbatch, a_kbs,
+             b_kbs, bias, accumulate, hip.stream())
 
 
 class _LinearFunction(torch.autograd.Function):
@@ -63,8 +61,7 @@ class _LinearFunction(torch.autograd.Function):
         dw = torch.empty_like(weight)                      # sum_b dy[b] (O, T) @ x[b]^T (T, I)
         _gemm(dy, x, dw, 1, O, I, T, T, T, I, 0, 0, 0, trans_b=1, kbatch=B, a_kbs=O*T, b_kbs=I*T)
         db = torch.empty(O, dtype=torch.float32, device=x.device)
-        hip.check(hip.lib().brv_row_sum(hip.ptr(dy), hip.ptr(db), B, O, T, hip.stream()),
-                  'brv_row_sum')
+        hip.call('brv_row_sum', dy, db, B, O, T, hip.stream())
         return dx, dw, db
 
 
@@ -73,9 +70,7 @@ class _ReluDropoutFunction(torch.autograd.Function):
     def forward(ctx, x, mask, scale):
         x = x.contiguous()
         out = torch.empty_like(x)
-        hip.check(hip.lib().brv_relu_dropout_forward(hip.ptr(x), hip.ptr(mask), hip.ptr(out),
-                                                     x.numel(), float(scale), hip.stream()),
-                  'brv_relu_dropout_forward')
+        hip.call('brv_relu_dropout_forward', x, mask, out, x.numel(), float(scale), hip.stream())
         ctx.save_for_backward(x, mask)
         ctx.scale = float(scale)
         return out
@@ -85,9 +80,7 @@ class _ReluDropoutFunction(torch.autograd.Function):
         x, mask = ctx.saved_tensors
         dy = dy.contiguous()
         dx = torch.empty_like(x)
-        hip.check(hip.lib().brv_relu_dropout_backward(hip.ptr(x), hip.ptr(mask), hip.ptr(dy),
-                                                      hip.ptr(dx), x.numel(), ctx.scale,
-                                                      hip.stream()), 'brv_relu_dropout_backward')
+        hip.call('brv_relu_dropout_backward', x, mask, dy, dx, x.numel(), ctx.scale, hip.stream())
         return dx, None, None
 
 
@@ -96,8 +89,7 @@ class _SigmoidFunction(torch.autograd.Function):
     def forward(ctx, x):
         x = x.contiguous()
         y = torch.empty_like(x)
-        hip.check(hip.lib().brv_sigmoid_forward(hip.ptr(x), hip.ptr(y), x.numel(), hip.stream()),
-                  'brv_sigmoid_forward')
+        hip.call('brv_sigmoid_forward', x, y, x.numel(), hip.stream())
         ctx.save_for_backward(y)
         return y
 
@@ -106,8 +98,7 @@ class _SigmoidFunction(torch.autograd.Function):
         y, = ctx.saved_tensors
         dy = dy.contiguous()
         dx = torch.empty_like(y)
-        hip.check(hip.lib().brv_sigmoid_backward(hip.ptr(y), hip.ptr(dy), hip.ptr(dx), y.numel(),
-                                                 hip.stream()), 'brv_sigmoid_backward')
+        hip.call('brv_sigmoid_backward', y, dy, dx, y.numel(), hip.stream())
         return dx
 
 
@@ -164,8 +155,7 @@ class StaticNormalizer(nn.Module):
         out = torch.empty_like(x3)
         # locals keep both (possibly converted) tensors alive until the launch is queued
         mean, std = self.mean.float().contiguous(), self.std.float().contiguous()
-        hip.check(hip.lib().brv_static_norm(hip.ptr(x3), hip.ptr(mean), hip.ptr(std), hip.ptr(out), B,
-                                            R, T, hip.stream()), 'brv_static_norm')
+        hip.call('brv_static_norm', x3, mean, std, out, B, R, T, hip.stream())
         return out.squeeze(0) if unbatched else out
 
 
@@ -179,9 +169,7 @@ class CumulativeNormalizer(nn.Module):
         x3 = x.float().contiguous()
         out = torch.empty_like(x3)
         T = x3.shape[-1]
-        hip.check(hip.lib().brv_cumulative_norm(hip.ptr(x3), hip.ptr(out), x3.numel()//T, T,
-                                                float(self.eps), hip.stream()),
-                  'brv_cumulative_norm')
+        hip.call('brv_cumulative_norm', x3, out, x3.numel()//T, T, float(self.eps), hip.stream())
         return out
 
 
@@ -265,27 +253,22 @@ class FFNN(BreverBaseModel):
         B, C, bins, F = x.shape
         spec = torch.view_as_real(x.to(torch.complex64).contiguous())
         out = torch.empty(B, bins, F, 2, dtype=torch.float32, device=x.device)
-        hip.check(hip.lib().brv_masked_mean_spec(
-            hip.ptr(spec), hip.ptr(mask_extrapolated.float().contiguous()), hip.ptr(out), B, C,
-            bins*F, hip.stream()), 'brv_masked_mean_spec')
+        hip.call('brv_masked_mean_spec', spec, mask_extrapolated.float().contiguous(), out, B, C, bins*F, hip.stream())
         y = self.stft.backward(torch.view_as_complex(out))
         return y[..., :length]
 
     def irm(self, foreground, background):
         """(channels, bins, frames) complex spectra -> (mel_filters, frames) ideal ratio mask
         (ffnn.py:121-128)."""
-        lib = hip.lib()
         C, bins, F = foreground.shape
         powers = []
         for s in (foreground, background):
             spec = torch.view_as_real(s.to(torch.complex64).contiguous())
             p = torch.empty(1, bins, F, dtype=torch.float32, device=s.device)
-            hip.check(lib.brv_fbe_power(hip.ptr(spec), hip.ptr(p), 1, C, bins*F, hip.stream()),
-                      'brv_fbe_power')
+            hip.call('brv_fbe_power', spec, p, 1, C, bins*F, hip.stream())
             powers.append(self.mel_fb(p[0]))
         out = torch.empty_like(powers[0])
-        hip.check(lib.brv_irm(hip.ptr(powers[0]), hip.ptr(powers[1]), hip.ptr(out), out.numel(),
-                              float(eps), hip.stream()), 'brv_irm')
+        hip.call('brv_irm', powers[0], powers[1], out, out.numel(), float(eps), hip.stream())
         return out
 
     def stack(self, data):
@@ -294,8 +277,7 @@ class FFNN(BreverBaseModel):
         d3 = (data.unsqueeze(0) if unbatched else data).float().contiguous()
         B, nf, T = d3.shape
         out = torch.empty(B, (self.stacks + 1)*nf, T, dtype=torch.float32, device=data.device)
-        hip.check(hip.lib().brv_stack_frames(hip.ptr(d3), hip.ptr(out), B, nf, T, self.stacks,
-                                             hip.stream()), 'brv_stack_frames')
+        hip.call('brv_stack_frames', d3, out, B, nf, T, self.stacks, hip.stream())
         return out.squeeze(0) if unbatched else out
 
     def decimate(self, data):

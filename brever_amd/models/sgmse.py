@@ -69,8 +69,7 @@ def _packed_weight(mod):
         Cout, Cin, k, _ = w.shape
         n = hip.lib().brv_conv2d_packed_size(Cout, Cin, k)
         wp = torch.empty(n, dtype=torch.float16, device=w.device)
-        hip.check(hip.lib().brv_conv2d_pack_f16(hip.ptr(w.detach().contiguous()), hip.ptr(wp), Cout,
-                                                Cin, k, hip.stream()), 'brv_conv2d_pack_f16')
+        hip.call('brv_conv2d_pack_f16', w.detach().contiguous(), wp, Cout, Cin, k, hip.stream())
         mod._brv_wp, mod._brv_wp_key = wp, key
     return mod._brv_wp
 
@@ -90,17 +89,14 @@ def _conv(x, mod, fold=None, silu=False, res=None, out_scale=1.0):
             and ph == pw == kh//2:
         y = torch.empty(B, Cout, H, W, dtype=torch.float32, device=x.device)
         sc, sf = fold if fold is not None else (None, None)
-        hip.check(hip.lib().brv_conv2d_mfma_forward(
-            hip.ptr(x), hip.ptr(_packed_weight(mod)), hip.ptr(mod.bias),
-            hip.ptr(res.contiguous()) if res is not None else None, hip.ptr(sc), hip.ptr(sf),
-            int(silu), hip.ptr(y), B, Cin, H, W, Cout, kh, Cin*H*W, Cout*H*W, float(out_scale),
-            hip.stream()), 'brv_conv2d_mfma_forward')
+        hip.call('brv_conv2d_mfma_forward', x, _packed_weight(mod), mod.bias,
+                 res.contiguous() if res is not None else None, sc, sf, int(silu), y, B, Cin, H, W, Cout, kh, Cin*H*W,
+                 Cout*H*W, float(out_scale), hip.stream())
         return y
     if fold is not None:
         x = _affine_act(x, fold, silu)
     Ho, Wo = (H + 2*ph - kh)//sh + 1, (W + 2*pw - kw)//sw + 1
     y = torch.empty(B, Cout, Ho, Wo, dtype=torch.float32, device=x.device)
-    lib = hip.lib()
     K = Cin*kh*kw
     if Cout >= 16 and K >= 16:
         # fp32 path: column matrix + one exact-fp32 MFMA product per item (a 1x1 convolution
@@ -109,15 +105,12 @@ def _conv(x, mod, fold=None, silu=False, res=None, out_scale=1.0):
             col = x
         else:
             col = torch.empty(B, K, Ho*Wo, dtype=torch.float32, device=x.device)
-            hip.check(lib.brv_im2col(hip.ptr(x), hip.ptr(col), B, Cin, H, W, kh, kw, sh, sw, ph, pw,
-                                     Ho, Wo, hip.stream()), 'brv_im2col')
-        hip.check(lib.brv_gemm_f32(
-            hip.ptr(mod.weight), hip.ptr(col), hip.ptr(y), B, Cout, Ho*Wo, K, K, Ho*Wo, Ho*Wo, 0,
-            K*Ho*Wo, Cout*Ho*Wo, 0, 0, 1, 0, 0, hip.ptr(mod.bias), 0, hip.stream()), 'brv_gemm_f32')
+            hip.call('brv_im2col', x, col, B, Cin, H, W, kh, kw, sh, sw, ph, pw, Ho, Wo, hip.stream())
+        hip.call('brv_gemm_f32', mod.weight, col, y, B, Cout, Ho*Wo, K, K, Ho*Wo, Ho*Wo, 0, K*Ho*Wo, Cout*Ho*Wo, 0, 0,
+                 1, 0, 0, mod.bias, 0, hip.stream())
     else:
-        hip.check(lib.brv_conv2d_forward(
-            hip.ptr(x), hip.ptr(mod.weight), hip.ptr(mod.bias), hip.ptr(y), B, Cin, H, W, Cout, kh,
-            kw, sh, sw, ph, pw, Cin*H*W, Cout*Ho*Wo, 0, 1.0, hip.stream()), 'brv_conv2d_forward')
+        hip.call('brv_conv2d_forward', x, mod.weight, mod.bias, y, B, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, Cin*H*W,
+                 Cout*Ho*Wo, 0, 1.0, hip.stream())
     if res is not None or out_scale != 1.0:
         y = _axpby(y, out_scale, res, out_scale)
     return y
@@ -138,11 +131,8 @@ def _gn_fold(x, mod, add=None, adm=None):
     scale = torch.empty(B, C, dtype=torch.float32, device=x.device)
     shift = torch.empty_like(scale)
     a0, a1 = (adm[0].contiguous(), adm[1].contiguous()) if adm is not None else (None, None)
-    hip.check(lib.brv_groupnorm_fold(
-        hip.ptr(x), hip.ptr(add.contiguous()) if add is not None else None, hip.ptr(mod.weight),
-        hip.ptr(mod.bias), hip.ptr(a0), hip.ptr(a1), hip.ptr(scratch), hip.ptr(scale),
-        hip.ptr(shift), None, None, B, C, H*W, mod.num_groups, float(mod.eps), hip.stream()),
-        'brv_groupnorm_fold')
+    hip.call('brv_groupnorm_fold', x, add.contiguous() if add is not None else None, mod.weight, mod.bias, a0, a1,
+             scratch, scale, shift, None, None, B, C, H*W, mod.num_groups, float(mod.eps), hip.stream())
     return scale, shift
 
 
@@ -150,8 +140,7 @@ def _affine_act(x, fold, silu=False):
     x = x.contiguous()
     B, C, H, W = x.shape
     y = torch.empty_like(x)
-    hip.check(hip.lib().brv_affine_act(hip.ptr(x), hip.ptr(fold[0]), hip.ptr(fold[1]), hip.ptr(y),
-                                       B, C, H*W, int(silu), hip.stream()), 'brv_affine_act')
+    hip.call('brv_affine_act', x, fold[0], fold[1], y, B, C, H*W, int(silu), hip.stream())
     return y
 
 
@@ -162,7 +151,7 @@ def _group_norm(x, mod, add=None, silu=False):
 def _silu(x):
     x = x.contiguous()
     y = torch.empty_like(x)
-    hip.check(hip.lib().brv_silu(hip.ptr(x), hip.ptr(y), x.numel(), hip.stream()), 'brv_silu')
+    hip.call('brv_silu', x, y, x.numel(), hip.stream())
     return y
 
 
@@ -172,9 +161,7 @@ def _linear(x, mod):
     N, K = x.shape
     O = mod.out_features
     d = torch.empty(O, N, dtype=torch.float32, device=x.device)
-    hip.check(hip.lib().brv_gemm_f32(
-        hip.ptr(mod.weight), hip.ptr(x), hip.ptr(d), 1, O, N, K, K, K, N, 0, 0, 0, 0, 1, 1, 0, 0,
-        hip.ptr(mod.bias), 0, hip.stream()), 'brv_gemm_f32')
+    hip.call('brv_gemm_f32', mod.weight, x, d, 1, O, N, K, K, K, N, 0, 0, 0, 0, 1, 1, 0, 0, mod.bias, 0, hip.stream())
     return d.t().contiguous()
 
 
@@ -189,8 +176,7 @@ def _axpby(a, alpha, b=None, beta=0.0):
         if a.is_complex() and not b.is_complex():
             b = torch.complex(b, torch.zeros_like(b))        # real noise added to a complex state
         br = torch.view_as_real(b) if b.is_complex() else b
-    hip.check(hip.lib().brv_axpby(hip.ptr(ar), float(alpha), hip.ptr(br), float(beta),
-                                  hip.ptr(orr), ar.numel(), hip.stream()), 'brv_axpby')
+    hip.call('brv_axpby', ar, float(alpha), br, float(beta), orr, ar.numel(), hip.stream())
     return out
 
 
@@ -227,8 +213,7 @@ def _h_from_nchw(x):
     x = x.contiguous()
     B, C, H, W = x.shape
     a = _h_new(B, H, W, C, x.device)
-    hip.check(hip.lib().brv_nchw_to_nhwc_f16(hip.ptr(x), hip.ptr(a.t), B, C, a.Cs, H*W, hip.stream()),
-              'brv_nchw_to_nhwc_f16')
+    hip.call('brv_nchw_to_nhwc_f16', x, a.t, B, C, a.Cs, H*W, hip.stream())
     return a
 
 
@@ -237,8 +222,7 @@ def _h_to_nchw(a):
         return torch.cat([_h_to_nchw(_Act(a.t, a.C)), _h_to_nchw(a.second)], dim=1)
     B, H, W, Cs = a.t.shape
     y = torch.empty(B, a.C, H, W, dtype=torch.float32, device=a.t.device)
-    hip.check(hip.lib().brv_nhwc_f16_to_nchw(hip.ptr(a.t), hip.ptr(y), B, a.C, Cs, H*W, hip.stream()),
-              'brv_nhwc_f16_to_nchw')
+    hip.call('brv_nhwc_f16_to_nchw', a.t, y, B, a.C, Cs, H*W, hip.stream())
     return y
 
 
@@ -274,8 +258,7 @@ def _h_sums(a):
     if a.sums is None:
         B, H, W, Cs = a.t.shape
         a.sums = _zeros_f64(B*a.C*2, a.t.device).view(B, a.C, 2)
-        hip.check(hip.lib().brv_nhwc_chan_stats(hip.ptr(a.t), hip.ptr(a.sums), B, a.C, Cs, H*W, 0, a.C,
-                                                hip.stream()), 'brv_nhwc_chan_stats')
+        hip.call('brv_nhwc_chan_stats', a.t, a.sums, B, a.C, Cs, H*W, 0, a.C, hip.stream())
     return a.sums
 
 
@@ -289,10 +272,8 @@ def _h_gn_fold(a, mod, add=None, adm=None):
     scale = torch.empty(B, C, dtype=torch.float32, device=a.t.device)
     shift = torch.empty_like(scale)
     a0, a1 = (adm[0].contiguous(), adm[1].contiguous()) if adm is not None else (None, None)
-    hip.check(hip.lib().brv_groupnorm_fold_chan(
-        hip.ptr(sums), hip.ptr(add.contiguous()) if add is not None else None, hip.ptr(mod.weight),
-        hip.ptr(mod.bias), hip.ptr(a0), hip.ptr(a1), hip.ptr(scale), hip.ptr(shift), B, C, H*W,
-        mod.num_groups, float(mod.eps), hip.stream()), 'brv_groupnorm_fold_chan')
+    hip.call('brv_groupnorm_fold_chan', sums, add.contiguous() if add is not None else None, mod.weight, mod.bias, a0,
+             a1, scale, shift, B, C, H*W, mod.num_groups, float(mod.eps), hip.stream())
     return scale, shift
 
 
@@ -303,8 +284,7 @@ def _h_packed3(mod):
         Cout, Cin, k, _ = w.shape
         n = hip.lib().brv_conv_nhwc_packed_size(Cout, Cin, k)
         wp = torch.empty(n, dtype=torch.float16, device=w.device)
-        hip.check(hip.lib().brv_conv_nhwc_pack(hip.ptr(w.detach().contiguous()), hip.ptr(wp), Cout, Cin,
-                                               k, hip.stream()), 'brv_conv_nhwc_pack')
+        hip.call('brv_conv_nhwc_pack', w.detach().contiguous(), wp, Cout, Cin, k, hip.stream())
         mod._brv_hp, mod._brv_hp_key = wp, key
     return mod._brv_hp
 
@@ -322,28 +302,25 @@ def _h_conv3(a, mod, fold=None, silu=False, res=None, out_scale=1.0, norm=None, 
     if res is not None:
         res = _h_single(res)
     b = a.second
-    common = (hip.ptr(a.t), a.C, a.Cs, hip.ptr(b.t) if b is not None else None, b.C if b is not None else 0,
-              b.Cs if b is not None else 0, hip.ptr(_h_packed3(mod)), hip.ptr(mod.bias),
-              hip.ptr(res.t) if res is not None else None, res.Cs if res is not None else 0)
+    common = (a.t, a.C, a.Cs, b.t if b is not None else None, b.C if b is not None else 0,
+              b.Cs if b is not None else 0, _h_packed3(mod), mod.bias,
+              res.t if res is not None else None, res.Cs if res is not None else 0)
     # scratch of the launches that split their reduction over workgroups (the inner U-Net levels: csrc/conv_nhwc_splitk.cuh);
     # BRV_CONV_SPLIT=0: the pixel-parallel kernel for every launch (rounds 2 - 5)
     nsplit = hip.lib().brv_conv_nhwc_split_ws_bytes(B, H, W, a.C, b.C if b is not None else 0, mod.out_channels) \
         if _CONV_SPLIT else 0
     split_ws = torch.empty(nsplit, dtype=torch.uint8, device=a.t.device) if nsplit > 0 else None
-    tail = (int(silu), hip.ptr(y.t), y.Cs, B, H, W, mod.out_channels, 3, float(out_scale), hip.ptr(y.sums),
-            hip.ptr(split_ws), nsplit, hip.stream())
+    tail = (int(silu), y.t, y.Cs, B, H, W, mod.out_channels, 3, float(out_scale), y.sums, split_ws, nsplit,
+            hip.stream())
     if norm is not None:
         ws = torch.empty(2*B*a.channels, dtype=torch.float32, device=a.t.device)
         a0, a1 = (adm[0].contiguous(), adm[1].contiguous()) if adm is not None else (None, None)
-        hip.check(hip.lib().brv_conv_nhwc_forward_gn_ws(
-            *common, hip.ptr(_h_sums(a)), hip.ptr(_h_sums(b)) if b is not None else None,
-            hip.ptr(add.contiguous()) if add is not None else None, hip.ptr(norm.weight),
-            hip.ptr(norm.bias), hip.ptr(a0), hip.ptr(a1), norm.num_groups, float(norm.eps), hip.ptr(ws),
-            *tail), 'brv_conv_nhwc_forward_gn_ws')
+        hip.call('brv_conv_nhwc_forward_gn_ws', *common, _h_sums(a), _h_sums(b) if b is not None else None,
+                 add.contiguous() if add is not None else None, norm.weight, norm.bias, a0, a1, norm.num_groups,
+                 float(norm.eps), ws, *tail)
         return y
     sc, sf = fold if fold is not None else (None, None)
-    hip.check(hip.lib().brv_conv_nhwc_forward_ws(*common, hip.ptr(sc), hip.ptr(sf), *tail),
-              'brv_conv_nhwc_forward_ws')
+    hip.call('brv_conv_nhwc_forward_ws', *common, sc, sf, *tail)
     return y
 
 
@@ -356,16 +333,13 @@ def _h_conv1(a, mod, out_scale=1.0):
     if getattr(mod, '_brv_h1_key', None) != key:
         n = hip.lib().brv_nhwc_conv1x1_packed_size(mod.out_channels, a.C, C2)
         wp = torch.empty(n, dtype=torch.float16, device=w.device)
-        hip.check(hip.lib().brv_nhwc_conv1x1_pack(hip.ptr(w.detach().contiguous()), hip.ptr(wp),
-                                                  mod.out_channels, a.C, C2, hip.stream()),
-                  'brv_nhwc_conv1x1_pack')
+        hip.call('brv_nhwc_conv1x1_pack', w.detach().contiguous(), wp, mod.out_channels, a.C, C2, hip.stream())
         mod._brv_h1, mod._brv_h1_key = wp, key
     B, (H, W) = a.t.shape[0], a.hw
     y = _h_new(B, H, W, mod.out_channels, a.t.device)
-    hip.check(hip.lib().brv_nhwc_conv1x1_forward(
-        hip.ptr(a.t), a.C, a.Cs, hip.ptr(b.t) if b is not None else None, C2,
-        b.Cs if b is not None else 0, hip.ptr(mod._brv_h1), hip.ptr(mod.bias), hip.ptr(y.t), y.Cs,
-        B*H*W, mod.out_channels, float(out_scale), hip.stream()), 'brv_nhwc_conv1x1_forward')
+    hip.call('brv_nhwc_conv1x1_forward', a.t, a.C, a.Cs, b.t if b is not None else None, C2,
+             b.Cs if b is not None else 0, mod._brv_h1, mod.bias, y.t, y.Cs, B*H*W, mod.out_channels, float(out_scale),
+             hip.stream())
     return y
 
 
@@ -373,9 +347,7 @@ def _h_affine_act(a, fold, silu=False):
     a = _h_single(a)
     B, H, W, Cs = a.t.shape
     y = _Act(torch.empty_like(a.t), a.C)
-    hip.check(hip.lib().brv_nhwc_affine_act(hip.ptr(a.t), hip.ptr(fold[0]), hip.ptr(fold[1]),
-                                            hip.ptr(y.t), B, a.C, Cs, H*W, int(silu), hip.stream()),
-              'brv_nhwc_affine_act')
+    hip.call('brv_nhwc_affine_act', a.t, fold[0], fold[1], y.t, B, a.C, Cs, H*W, int(silu), hip.stream())
     return y
 
 
@@ -385,9 +357,8 @@ def _h_resample(a, resampler, up_or_down):
     K = resampler.kernel.shape[-1]
     padding, (Ho, Wo), up = resampler.plan((H, W), up_or_down)
     y = _Act(torch.empty(B, Ho, Wo, Cs, dtype=torch.float16, device=a.t.device), a.C)
-    hip.check(hip.lib().brv_nhwc_fir_resample2d(
-        hip.ptr(a.t), hip.ptr(resampler.kernel.float().contiguous()), hip.ptr(y.t), B, Cs, H, W, Ho, Wo,
-        K, padding[0], padding[1], int(up), 4.0 if up else 1.0, hip.stream()), 'brv_nhwc_fir_resample2d')
+    hip.call('brv_nhwc_fir_resample2d', a.t, resampler.kernel.float().contiguous(), y.t, B, Cs, H, W, Ho, Wo, K,
+             padding[0], padding[1], int(up), 4.0 if up else 1.0, hip.stream())
     return y
 
 
@@ -403,11 +374,8 @@ def _h_resample_pair(a, fold, resampler, up_or_down, silu=True):
     padding, (Ho, Wo), up = resampler.plan((H, W), up_or_down)
     y = _Act(torch.empty(B, Ho, Wo, Cs, dtype=torch.float16, device=a.t.device), a.C)
     h = _Act(torch.empty_like(y.t), a.C)
-    hip.check(hip.lib().brv_nhwc_fir_resample2d_dual(
-        hip.ptr(a.t), hip.ptr(fold[0]), hip.ptr(fold[1]), int(silu),
-        hip.ptr(resampler.kernel.float().contiguous()), hip.ptr(y.t), hip.ptr(h.t), B, a.C, Cs, H, W,
-        Ho, Wo, K, padding[0], padding[1], int(up), 4.0 if up else 1.0, hip.stream()),
-        'brv_nhwc_fir_resample2d_dual')
+    hip.call('brv_nhwc_fir_resample2d_dual', a.t, fold[0], fold[1], int(silu), resampler.kernel.float().contiguous(),
+             y.t, h.t, B, a.C, Cs, H, W, Ho, Wo, K, padding[0], padding[1], int(up), 4.0 if up else 1.0, hip.stream())
     return y, h
 
 
@@ -419,16 +387,12 @@ def _h_small_conv(a, mod, fold=None, silu=False, y_in=None):
     key = (w.data_ptr(), w._version, _PARAM_EPOCH[0])
     if getattr(mod, '_brv_hs_key', None) != key:
         w16 = torch.empty(9*w.shape[0]*w.shape[1], dtype=torch.float16, device=w.device)
-        hip.check(hip.lib().brv_nhwc_conv3x3_small_pack(hip.ptr(w.detach().contiguous()), hip.ptr(w16),
-                                                        w.shape[0], w.shape[1], hip.stream()),
-                  'brv_nhwc_conv3x3_small_pack')
+        hip.call('brv_nhwc_conv3x3_small_pack', w.detach().contiguous(), w16, w.shape[0], w.shape[1], hip.stream())
         mod._brv_hs, mod._brv_hs_key = w16, key
     y = torch.empty(B, mod.out_channels, H, W, dtype=torch.float32, device=a.t.device)
     sc, sf = fold if fold is not None else (None, None)
-    hip.check(hip.lib().brv_nhwc_conv3x3_small(
-        hip.ptr(a.t), hip.ptr(mod._brv_hs), hip.ptr(mod.bias), hip.ptr(sc), hip.ptr(sf), int(silu),
-        hip.ptr(y_in.contiguous()) if y_in is not None else None, hip.ptr(y), B, a.C, Cs, H, W,
-        mod.out_channels, hip.stream()), 'brv_nhwc_conv3x3_small')
+    hip.call('brv_nhwc_conv3x3_small', a.t, mod._brv_hs, mod.bias, sc, sf, int(silu),
+             y_in.contiguous() if y_in is not None else None, y, B, a.C, Cs, H, W, mod.out_channels, hip.stream())
     return y
 
 
@@ -437,9 +401,8 @@ def _h_add_pointwise(a, aux, mod, out_scale=1.0):
     a = _h_single(a)
     B, H, W, Cs = a.t.shape
     y = _Act(torch.empty_like(a.t), a.C)
-    hip.check(hip.lib().brv_nhwc_add_pointwise(
-        hip.ptr(a.t), hip.ptr(aux.contiguous()), hip.ptr(mod.weight), hip.ptr(mod.bias), hip.ptr(y.t),
-        B, a.C, Cs, mod.in_channels, H*W, float(out_scale), hip.stream()), 'brv_nhwc_add_pointwise')
+    hip.call('brv_nhwc_add_pointwise', a.t, aux.contiguous(), mod.weight, mod.bias, y.t, B, a.C, Cs, mod.in_channels,
+             H*W, float(out_scale), hip.stream())
     return y
 
 
@@ -460,9 +423,7 @@ class GaussianFourierProjection(nn.Module):
     def forward(self, x):
         x = x.float().contiguous()
         out = torch.empty(x.numel(), 2*self.b.numel(), dtype=torch.float32, device=x.device)
-        hip.check(hip.lib().brv_fourier_features(hip.ptr(x), hip.ptr(self.b), hip.ptr(out),
-                                                 x.numel(), self.b.numel(), hip.stream()),
-                  'brv_fourier_features')
+        hip.call('brv_fourier_features', x, self.b, out, x.numel(), self.b.numel(), hip.stream())
         return out
 
 
@@ -489,7 +450,6 @@ class AttentionBlock(nn.Module):
         self.conv_out = nn.Conv2d(num_channels, num_channels, 1)
 
     def forward(self, x, out_scale=1.0):
-        lib = hip.lib()
         N, C, H, W = x.shape
         L = H*W
         fold = _gn_fold(x, self.norm)
@@ -504,8 +464,7 @@ class AttentionBlock(nn.Module):
         hip.gemm_f32(q, k, w, N, L, L, C, L, L, L, 3*C*L, 3*C*L, L*L, 1, 0, 1, 0, 0, None, 0)
         w = _axpby(w, 1.0/C**0.5)
         p = torch.empty_like(w)
-        hip.check(lib.brv_softmax_rows(hip.ptr(w), hip.ptr(p), N*L, L, hip.stream()),
-                  'brv_softmax_rows')
+        hip.call('brv_softmax_rows', w, p, N*L, L, hip.stream())
         # attention^T (C, L) = v (C, L) @ weights^T (L, L)
         a = torch.empty(N, C, L, dtype=torch.float32, device=x.device)
         hip.gemm_f32(v, p, a, N, C, L, L, L, L, L, 3*C*L, L*L, C*L, 0, 1, 1, 0, 0, None, 0)
@@ -780,9 +739,8 @@ class DiffusionUNet(nn.Module):
         N, K = emb.shape
         O = self._emb_w.shape[0]
         d = torch.empty(O, N, dtype=torch.float32, device=emb.device)
-        hip.check(hip.lib().brv_gemm_f32(
-            hip.ptr(self._emb_w), hip.ptr(emb.contiguous()), hip.ptr(d), 1, O, N, K, K, K, N, 0, 0,
-            0, 0, 1, 1, 0, 0, hip.ptr(self._emb_b), 0, hip.stream()), 'brv_gemm_f32')
+        hip.call('brv_gemm_f32', self._emb_w, emb.contiguous(), d, 1, O, N, K, K, K, N, 0, 0, 0, 0, 1, 1, 0, 0,
+                 self._emb_b, 0, hip.stream())
         gidx = self._emb_gidx.get((N, batch)) if batch is not None else None
         if gidx is None and batch is not None and batch % N == 0 and not torch.cuda.is_current_stream_capturing():
             # source index of every element of the blocks' (batch, out_features) slices laid out back to back: built on

@@ -25,17 +25,15 @@ def _gemm(a, b, d, batch, M, N, K, lda, ldb, ldd, a_bs, b_bs, d_bs, trans_a=0, t
     flags = int(b.dtype == torch.bfloat16) | int(d.dtype == torch.bfloat16) << 1
     if flags:
         assert lowp
-        hip.check(hip.lib().brv_gemm_bf16_mixed(
-            hip.ptr(a), hip.ptr(b), hip.ptr(d), batch, M, N, K, lda, ldb, ldd, a_bs, b_bs, d_bs,
-            trans_a, trans_b, kbatch, a_kbs, b_kbs, hip.ptr(bias), 0, flags, hip.stream()), 'brv_gemm_bf16_mixed')
+        hip.call('brv_gemm_bf16_mixed', a, b, d, batch, M, N, K, lda, ldb, ldd, a_bs, b_bs, d_bs, trans_a, trans_b,
+                 kbatch, a_kbs, b_kbs, bias, 0, flags, hip.stream())
         return
     if not lowp:
         hip.gemm_f32(a, b, d, batch, M, N, K, lda, ldb, ldd, a_bs, b_bs, d_bs, trans_a, trans_b, kbatch, a_kbs,
                      b_kbs, bias, 0)
         return
-    hip.check(hip.lib().brv_gemm_bf16(
-        hip.ptr(a), hip.ptr(b), hip.ptr(d), batch, M, N, K, lda, ldb, ldd, a_bs, b_bs, d_bs,
-        trans_a, trans_b, kbatch, a_kbs, b_kbs, hip.ptr(bias), 0, hip.stream()), 'brv_gemm_bf16')
+    hip.call('brv_gemm_bf16', a, b, d, batch, M, N, K, lda, ldb, ldd, a_bs, b_bs, d_bs, trans_a, trans_b, kbatch, a_kbs,
+             b_kbs, bias, 0, hip.stream())
 
 
 # use_amp: the explicit column matrices (and the column-matrix gradient) in bf16 -- the products round them to bf16
@@ -53,10 +51,8 @@ def _gemm_conv(a, img, d, batch, M, N, K, lda, ldd, a_bs, img_bs, d_bs, C, H, W,
                img_kbs=0, bias=None):
     """``_gemm(lowp=True)`` whose B operand is the im2col matrix of ``img`` (C, H, W per item; k x k window,
     stride 1, padding k//2) -- never written out (``brv_gemm_bf16_conv``)."""
-    hip.check(hip.lib().brv_gemm_bf16_conv(
-        hip.ptr(a), hip.ptr(img), hip.ptr(d), batch, M, N, K, lda, ldd, a_bs, img_bs, d_bs, 0, trans_b,
-        kbatch, a_kbs, img_kbs, hip.ptr(bias), 0, 1, C, H, W, k, k, 1, 1, k//2, k//2, H, W, hip.stream()),
-        'brv_gemm_bf16_conv')
+    hip.call('brv_gemm_bf16_conv', a, img, d, batch, M, N, K, lda, ldd, a_bs, img_bs, d_bs, 0, trans_b, kbatch, a_kbs,
+             img_kbs, bias, 0, 1, C, H, W, k, k, 1, 1, k//2, k//2, H, W, hip.stream())
 
 
 # Column matrices kept from the forward pass for the weight gradient (instead of a second im2col in backward): up to
@@ -102,8 +98,8 @@ class ConvFn(torch.autograd.Function):
         B, Cin, H, W = x.shape
         half = lowp and _COL_BF16
         col = torch.empty(B, Cin*k*k, H*W, dtype=torch.bfloat16 if half else torch.float32, device=x.device)
-        fn, name = (hip.lib().brv_im2col_bf16, 'brv_im2col_bf16') if half else (hip.lib().brv_im2col, 'brv_im2col')
-        hip.check(fn(hip.ptr(x), hip.ptr(col), B, Cin, H, W, k, k, 1, 1, k//2, k//2, H, W, hip.stream()), name)
+        hip.call('brv_im2col_bf16' if half else 'brv_im2col', x, col, B, Cin, H, W, k, k, 1, 1, k//2, k//2, H, W,
+                 hip.stream())
         return col
 
     @staticmethod
@@ -114,8 +110,7 @@ class ConvFn(torch.autograd.Function):
         Cout, _, k, _ = w.shape
         K, HW = Cin*k*k, H*W
         db = _empty(Cout, like=x)
-        hip.check(hip.lib().brv_row_sum(hip.ptr(dy), hip.ptr(db), B, Cout, HW, hip.stream()),
-                  'brv_row_sum')
+        hip.call('brv_row_sum', dy, db, B, Cout, HW, hip.stream())
         if ctx.lowp and k > 1 and _IMPLICIT:
             # both gradients as products with a column matrix read in place: dW = dy @ col(x)^T summed over the
             # batch; dx = the same convolution of dy with the window rotated by 180 degrees and (Cout, Cin) swapped
@@ -145,10 +140,8 @@ class ConvFn(torch.autograd.Function):
                 dx = dcol.view(B, Cin, H, W)
             else:
                 dx = torch.empty_like(x)
-                fn, name = (hip.lib().brv_col2im_bf16, 'brv_col2im_bf16') if dcol.dtype == torch.bfloat16 else \
-                    (hip.lib().brv_col2im, 'brv_col2im')
-                hip.check(fn(hip.ptr(dcol), None, hip.ptr(dx), B, Cin, H, W, k, k, 1, 1, k//2, k//2, H, W,
-                             hip.stream()), name)
+                hip.call('brv_col2im_bf16' if dcol.dtype == torch.bfloat16 else 'brv_col2im', dcol, None, dx,
+                         B, Cin, H, W, k, k, 1, 1, k//2, k//2, H, W, hip.stream())
         return dx, dw, db
 
 
@@ -164,13 +157,10 @@ class GroupNormFn(torch.autograd.Function):
                               device=x.device)
         scale, shift, mu, rstd = (_empty(B, C, like=x) for _ in range(4))
         addc = add.contiguous() if add is not None else None
-        hip.check(lib.brv_groupnorm_fold(
-            hip.ptr(x), hip.ptr(addc), hip.ptr(gamma), hip.ptr(beta), None, None, hip.ptr(scratch),
-            hip.ptr(scale), hip.ptr(shift), hip.ptr(mu), hip.ptr(rstd), B, C, H*W, groups,
-            float(eps), hip.stream()), 'brv_groupnorm_fold')
+        hip.call('brv_groupnorm_fold', x, addc, gamma, beta, None, None, scratch, scale, shift, mu, rstd, B, C, H*W,
+                 groups, float(eps), hip.stream())
         y = torch.empty_like(x)
-        hip.check(lib.brv_affine_act(hip.ptr(x), hip.ptr(scale), hip.ptr(shift), hip.ptr(y), B, C,
-                                     H*W, int(silu), hip.stream()), 'brv_affine_act')
+        hip.call('brv_affine_act', x, scale, shift, y, B, C, H*W, int(silu), hip.stream())
         ctx.save_for_backward(x, gamma, scale, shift, mu, rstd)
         ctx.cfg = (groups, bool(silu), add is not None)
         return y
@@ -184,10 +174,8 @@ class GroupNormFn(torch.autograd.Function):
         dx = torch.empty_like(x)
         s1, s2, dadd = (_empty(B, C, like=x) for _ in range(3))
         coef = _empty(3*B*C, like=x)
-        hip.check(hip.lib().brv_groupnorm_backward(
-            hip.ptr(x), hip.ptr(dy), hip.ptr(scale), hip.ptr(shift), hip.ptr(mu), hip.ptr(rstd),
-            hip.ptr(gamma), hip.ptr(dx), hip.ptr(s1), hip.ptr(s2), hip.ptr(dadd), hip.ptr(coef), B,
-            C, H*W, groups, int(silu), hip.stream()), 'brv_groupnorm_backward')
+        hip.call('brv_groupnorm_backward', x, dy, scale, shift, mu, rstd, gamma, dx, s1, s2, dadd, coef, B, C, H*W,
+                 groups, int(silu), hip.stream())
         # d gamma / d beta: (B, C) -> (C,), a handful of values
         return dx, (dadd if has_add else None), s2.sum(0), s1.sum(0), None, None, None
 
@@ -201,8 +189,7 @@ class AffineActFn(torch.autograd.Function):
         x, scale, shift = x.contiguous(), scale.contiguous(), shift.contiguous()
         B, C, H, W = x.shape
         y = torch.empty_like(x)
-        hip.check(hip.lib().brv_affine_act(hip.ptr(x), hip.ptr(scale), hip.ptr(shift), hip.ptr(y), B,
-                                           C, H*W, int(silu), hip.stream()), 'brv_affine_act')
+        hip.call('brv_affine_act', x, scale, shift, y, B, C, H*W, int(silu), hip.stream())
         ctx.save_for_backward(x, scale, shift)
         ctx.silu = bool(silu)
         return y
@@ -215,10 +202,8 @@ class AffineActFn(torch.autograd.Function):
         dx = torch.empty_like(x)
         dscale, dshift = torch.empty_like(scale), torch.empty_like(shift)
         zeros, ones = torch.zeros_like(scale), torch.ones_like(scale)
-        hip.check(hip.lib().brv_affine_act_backward(
-            hip.ptr(x), hip.ptr(dy), hip.ptr(scale), hip.ptr(shift), hip.ptr(zeros), hip.ptr(ones),
-            hip.ptr(dx), hip.ptr(dscale), hip.ptr(dshift), B, C, H*W, int(ctx.silu), hip.stream()),
-            'brv_affine_act_backward')
+        hip.call('brv_affine_act_backward', x, dy, scale, shift, zeros, ones, dx, dscale, dshift, B, C, H*W,
+                 int(ctx.silu), hip.stream())
         return dx, dscale, dshift, None
 
 
@@ -227,7 +212,7 @@ class SiluFn(torch.autograd.Function):
     def forward(ctx, x):
         x = x.contiguous()
         y = torch.empty_like(x)
-        hip.check(hip.lib().brv_silu(hip.ptr(x), hip.ptr(y), x.numel(), hip.stream()), 'brv_silu')
+        hip.call('brv_silu', x, y, x.numel(), hip.stream())
         ctx.save_for_backward(x)
         return y
 
@@ -236,15 +221,13 @@ class SiluFn(torch.autograd.Function):
         x, = ctx.saved_tensors
         dy = dy.contiguous()
         dx = torch.empty_like(x)
-        hip.check(hip.lib().brv_silu_backward(hip.ptr(x), hip.ptr(dy), hip.ptr(dx), x.numel(),
-                                              hip.stream()), 'brv_silu_backward')
+        hip.call('brv_silu_backward', x, dy, dx, x.numel(), hip.stream())
         return dx
 
 
 def _axpby_raw(a, alpha, b, beta):
     out = torch.empty_like(a)
-    hip.check(hip.lib().brv_axpby(hip.ptr(a), float(alpha), hip.ptr(b), float(beta), hip.ptr(out),
-                                  a.numel(), hip.stream()), 'brv_axpby')
+    hip.call('brv_axpby', a, float(alpha), b, float(beta), out, a.numel(), hip.stream())
     return out
 
 
@@ -274,9 +257,8 @@ class ResampleFn(torch.autograd.Function):
         B, C, H, W = x.shape
         K = kernel.shape[-1]
         y = _empty(B, C, out_hw[0], out_hw[1], like=x)
-        hip.check(hip.lib().brv_fir_resample2d(
-            hip.ptr(x), hip.ptr(kernel), hip.ptr(y), B*C, H, W, out_hw[0], out_hw[1], K, pad[0],
-            pad[1], int(up), 4.0 if up else 1.0, hip.stream()), 'brv_fir_resample2d')
+        hip.call('brv_fir_resample2d', x, kernel, y, B*C, H, W, out_hw[0], out_hw[1], K, pad[0], pad[1], int(up),
+                 4.0 if up else 1.0, hip.stream())
         ctx.save_for_backward(kernel)
         ctx.cfg = (bool(up), pad, (H, W))
         return y
@@ -291,13 +273,9 @@ class ResampleFn(torch.autograd.Function):
         dx = _empty(B, C, H, W, like=dy)
         if up:       # adjoint of the transposed convolution with 4*kernel: strided FIR with 4*kernel
             k4 = (4.0*kernel).contiguous()
-            hip.check(hip.lib().brv_fir_resample2d(
-                hip.ptr(dy), hip.ptr(k4), hip.ptr(dx), B*C, Ho, Wo, H, W, K, pad[0], pad[1], 0, 1.0,
-                hip.stream()), 'brv_fir_resample2d')
+            hip.call('brv_fir_resample2d', dy, k4, dx, B*C, Ho, Wo, H, W, K, pad[0], pad[1], 0, 1.0, hip.stream())
         else:        # adjoint of the strided FIR: transposed convolution onto the input grid
-            hip.check(hip.lib().brv_fir_resample2d(
-                hip.ptr(dy), hip.ptr(kernel), hip.ptr(dx), B*C, Ho, Wo, H, W, K, pad[0], pad[1], 1,
-                1.0, hip.stream()), 'brv_fir_resample2d')
+            hip.call('brv_fir_resample2d', dy, kernel, dx, B*C, Ho, Wo, H, W, K, pad[0], pad[1], 1, 1.0, hip.stream())
         return dx, None, None, None, None
 
 
@@ -334,13 +312,11 @@ class AttentionCoreFn(torch.autograd.Function):
     def forward(ctx, q, k, v):
         q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
         N, C, L = q.shape
-        lib = hip.lib()
         w = _empty(N, L, L, like=q)
         _gemm(q, k, w, N, L, L, C, L, L, L, C*L, C*L, L*L, trans_a=1)
         w = _axpby_raw(w, 1.0/C**0.5, None, 0.0)
         p = torch.empty_like(w)
-        hip.check(lib.brv_softmax_rows(hip.ptr(w), hip.ptr(p), N*L, L, hip.stream()),
-                  'brv_softmax_rows')
+        hip.call('brv_softmax_rows', w, p, N*L, L, hip.stream())
         a = _empty(N, C, L, like=q)
         _gemm(v, p, a, N, C, L, L, L, L, L, C*L, L*L, C*L, trans_b=1)
         ctx.save_for_backward(q, k, v, p)
@@ -356,8 +332,7 @@ class AttentionCoreFn(torch.autograd.Function):
         dp = torch.empty_like(p)                      # da^T (L x C) @ v (C x L)
         _gemm(da, v, dp, N, L, L, C, L, L, L, C*L, C*L, L*L, trans_a=1)
         dw = torch.empty_like(p)
-        hip.check(hip.lib().brv_softmax_rows_backward(hip.ptr(p), hip.ptr(dp), hip.ptr(dw), N*L, L,
-                                                      hip.stream()), 'brv_softmax_rows_backward')
+        hip.call('brv_softmax_rows_backward', p, dp, dw, N*L, L, hip.stream())
         dw = _axpby_raw(dw, 1.0/C**0.5, None, 0.0)
         dq = torch.empty_like(q)                      # k (C x L) @ dW^T
         _gemm(k, dw, dq, N, C, L, L, L, L, L, C*L, L*L, C*L, trans_b=1)
@@ -399,8 +374,7 @@ class DropoutFn(torch.autograd.Function):
         keep = 1.0 - p
         mask = torch.empty_like(x).bernoulli_(keep)
         out = torch.empty_like(x)
-        hip.check(hip.lib().brv_dropout_apply(hip.ptr(x.contiguous()), hip.ptr(mask), hip.ptr(out),
-                                              x.numel(), 1.0/keep, hip.stream()), 'brv_dropout_apply')
+        hip.call('brv_dropout_apply', x.contiguous(), mask, out, x.numel(), 1.0/keep, hip.stream())
         ctx.save_for_backward(mask)
         ctx.scale = 1.0/keep
         return out
@@ -409,9 +383,7 @@ class DropoutFn(torch.autograd.Function):
     def backward(ctx, dy):
         mask, = ctx.saved_tensors
         dx = torch.empty_like(mask)
-        hip.check(hip.lib().brv_dropout_apply(hip.ptr(dy.contiguous()), hip.ptr(mask), hip.ptr(dx),
-                                              mask.numel(), ctx.scale, hip.stream()),
-                  'brv_dropout_apply')
+        hip.call('brv_dropout_apply', dy.contiguous(), mask, dx, mask.numel(), ctx.scale, hip.stream())
         return dx, None
 
 

@@ -112,9 +112,7 @@ class _RowNormFn(torch.autograd.Function):
         y = torch.empty_like(x)
         stats = torch.empty(R, 2, dtype=torch.float32, device=x.device)
         sl = slope.contiguous() if slope is not None else None
-        hip.check(hip.lib().brv_rownorm_forward(hip.ptr(x), hip.ptr(sl), hip.ptr(gain), hip.ptr(bias),
-                                                hip.ptr(y), hip.ptr(stats), R, n, inner, G,
-                                                float(eps), hip.stream()), 'brv_rownorm_forward')
+        hip.call('brv_rownorm_forward', x, sl, gain, bias, y, stats, R, n, inner, G, float(eps), hip.stream())
         ctx.save_for_backward(x, sl, gain, stats)
         ctx.cfg = (inner, G, slope is not None)
         return y
@@ -131,15 +129,12 @@ class _RowNormFn(torch.autograd.Function):
         rows = torch.empty(R, dtype=torch.float32, device=x.device) if has_slope else None
         scratch = torch.empty(lib.brv_rownorm_scratch_bytes(n, G), dtype=torch.uint8,
                               device=x.device)
-        hip.check(lib.brv_rownorm_backward(
-            hip.ptr(x), hip.ptr(dy), hip.ptr(sl), hip.ptr(gain), hip.ptr(stats), hip.ptr(dx),
-            hip.ptr(dgain), hip.ptr(dbias), hip.ptr(rows), hip.ptr(scratch), R, n, inner, G,
-            hip.stream()), 'brv_rownorm_backward')
+        hip.call('brv_rownorm_backward', x, dy, sl, gain, stats, dx, dgain, dbias, rows, scratch, R, n, inner, G,
+                 hip.stream())
         dslope = None
         if has_slope:                                   # rows are (outer, G, inner)
             dslope = torch.empty(G, dtype=torch.float32, device=x.device)
-            hip.check(lib.brv_row_sum(hip.ptr(rows), hip.ptr(dslope), R//(G*inner), G, inner,
-                                      hip.stream()), 'brv_row_sum')
+            hip.call('brv_row_sum', rows, dslope, R//(G*inner), G, inner, hip.stream())
         return dx, dslope, dgain, dbias, None, None
 
 
@@ -150,8 +145,7 @@ class _RowScaleFn(torch.autograd.Function):
     def forward(ctx, x, s, divide):
         x, s = x.contiguous(), s.contiguous()
         y = torch.empty_like(x)
-        hip.check(hip.lib().brv_row_scale(hip.ptr(x), hip.ptr(s), hip.ptr(y), x.shape[0], x.shape[1],
-                                          int(divide), hip.stream()), 'brv_row_scale')
+        hip.call('brv_row_scale', x, s, y, x.shape[0], x.shape[1], int(divide), hip.stream())
         ctx.save_for_backward(s)
         ctx.divide = divide
         return y
@@ -175,8 +169,7 @@ class _AttentionFn(torch.autograd.Function):
         T._gemm(q, k, w, N, L, L, D, D, D, L, L*D, L*D, L*L, trans_b=1, lowp=lowp)
         w = T._axpby_raw(w, 1.0/D**0.5, None, 0.0)
         p = torch.empty_like(w)
-        hip.check(hip.lib().brv_softmax_rows(hip.ptr(w), hip.ptr(p), N*L, L, hip.stream()),
-                  'brv_softmax_rows')
+        hip.call('brv_softmax_rows', w, p, N*L, L, hip.stream())
         a = T._empty(N, L, Dv, like=q)
         T._gemm(p, v, a, N, L, Dv, L, L, Dv, Dv, L*L, L*Dv, L*Dv, lowp=lowp)
         ctx.save_for_backward(q, k, v, p)
@@ -194,8 +187,7 @@ class _AttentionFn(torch.autograd.Function):
         dp = torch.empty_like(p)                       # da (L x Dv) @ v^T
         T._gemm(da, v, dp, N, L, L, Dv, Dv, Dv, L, L*Dv, L*Dv, L*L, trans_b=1, lowp=lowp)
         dw = torch.empty_like(p)
-        hip.check(hip.lib().brv_softmax_rows_backward(hip.ptr(p), hip.ptr(dp), hip.ptr(dw), N*L, L,
-                                                      hip.stream()), 'brv_softmax_rows_backward')
+        hip.call('brv_softmax_rows_backward', p, dp, dw, N*L, L, hip.stream())
         dw = T._axpby_raw(dw, 1.0/D**0.5, None, 0.0)
         dq = torch.empty_like(q)                       # dW (L x L) @ k (L x D)
         T._gemm(dw, k, dq, N, L, D, L, L, D, D, L*L, L*D, L*D, lowp=lowp)
@@ -223,8 +215,7 @@ def _gemm(a, b, d, batch, M, N, K, lda, ldb, ldd, a_bs=0, b_bs=0, d_bs=0, trans_
             and lda % 4 == 0 and ldd % 4 == 0 and (a.data_ptr() | d.data_ptr()) % 16 == 0 \
             and hip.lib().brv_linear_small_supported(M, N, K):
         # narrow layers (K, N <= 64 over ~2.6e5 rows): one thread per row in fp32 instead of a 128 x 128 MFMA tile
-        hip.check(hip.lib().brv_linear_small(hip.ptr(a), hip.ptr(b), hip.ptr(bias), hip.ptr(d), M, N, K, lda, ldb,
-                                             ldd, trans_b, int(mode == 1), hip.stream()), 'brv_linear_small')
+        hip.call('brv_linear_small', a, b, bias, d, M, N, K, lda, ldb, ldd, trans_b, int(mode == 1), hip.stream())
         return
     if _SMALL and not flags and batch == 1 and kbatch == 1 and trans_a and not trans_b and bias is None and mode == 0 \
             and lda % 4 == 0 and ldb % 4 == 0 and (a.data_ptr() | b.data_ptr()) % 16 == 0 \
@@ -238,22 +229,18 @@ def _gemm(a, b, d, batch, M, N, K, lda, ldb, ldd, a_bs=0, b_bs=0, d_bs=0, trans_
         scratch = _SMALL_SCRATCH.get(key)
         if scratch is None or scratch.numel() < nbytes:
             scratch = _SMALL_SCRATCH[key] = torch.empty(nbytes, dtype=torch.uint8, device=d.device)
-        hip.check(lib.brv_linear_small_wgrad(hip.ptr(a), hip.ptr(b), hip.ptr(d), hip.ptr(scratch), K, M, N, lda, ldb,
-                                             ldd, hip.stream()), 'brv_linear_small_wgrad')
+        hip.call('brv_linear_small_wgrad', a, b, d, scratch, K, M, N, lda, ldb, ldd, hip.stream())
         return
     if flags:
-        hip.check(hip.lib().brv_gemm_bf16_mixed(
-            hip.ptr(a), hip.ptr(b), hip.ptr(d), batch, M, N, K, lda, ldb, ldd, a_bs, b_bs, d_bs,
-            trans_a, trans_b, kbatch, a_kbs, b_kbs, hip.ptr(bias), mode, flags, hip.stream()),
-            'brv_gemm_bf16_mixed')
+        hip.call('brv_gemm_bf16_mixed', a, b, d, batch, M, N, K, lda, ldb, ldd, a_bs, b_bs, d_bs, trans_a, trans_b,
+                 kbatch, a_kbs, b_kbs, bias, mode, flags, hip.stream())
         return
     if not lowp:
         hip.gemm_f32(a, b, d, batch, M, N, K, lda, ldb, ldd, a_bs, b_bs, d_bs, trans_a, trans_b, kbatch, a_kbs,
                      b_kbs, bias, mode)
         return
-    hip.check(hip.lib().brv_gemm_bf16(
-        hip.ptr(a), hip.ptr(b), hip.ptr(d), batch, M, N, K, lda, ldb, ldd, a_bs, b_bs, d_bs,
-        trans_a, trans_b, kbatch, a_kbs, b_kbs, hip.ptr(bias), mode, hip.stream()), 'brv_gemm_bf16')
+    hip.call('brv_gemm_bf16', a, b, d, batch, M, N, K, lda, ldb, ldd, a_bs, b_bs, d_bs, trans_a, trans_b, kbatch, a_kbs,
+             b_kbs, bias, mode, hip.stream())
 
 
 def _column_sums(x, rows, cols, batch=1, lowp=False):
@@ -265,15 +252,13 @@ def _column_sums(x, rows, cols, batch=1, lowp=False):
         lib = hip.lib()
         scratch = torch.empty(lib.brv_col_sum_scratch_bytes(batch, cols), dtype=torch.uint8,
                               device=x.device)
-        hip.check(lib.brv_col_sum(hip.ptr(x), hip.ptr(out), hip.ptr(scratch), batch, rows, cols,
-                                  hip.stream()), 'brv_col_sum')
+        hip.call('brv_col_sum', x, out, scratch, batch, rows, cols, hip.stream())
         return out
     if x.dtype == torch.bfloat16 and cols % 8 == 0 and x.data_ptr() % 16 == 0:
         lib = hip.lib()
         scratch = torch.empty(lib.brv_col_sum_scratch_bytes(batch, cols), dtype=torch.uint8,
                               device=x.device)
-        hip.check(lib.brv_col_sum_bf16(hip.ptr(x), hip.ptr(out), hip.ptr(scratch), batch, rows, cols,
-                                       hip.stream()), 'brv_col_sum_bf16')
+        hip.call('brv_col_sum_bf16', x, out, scratch, batch, rows, cols, hip.stream())
         return out
     ones = torch.ones(rows, dtype=torch.float32, device=x.device)
     _gemm(ones, x, out, batch, 1, cols, rows, rows, cols, cols, 0, rows*cols, cols, lowp=True)
@@ -323,7 +308,6 @@ class _BiLSTMFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w_ih, w_hh, b_ih, b_hh):
-        lib = hip.lib()
         x, w_hh = x.contiguous(), w_hh.contiguous()
         N, S, I = x.shape
         H = w_hh.shape[-1]
@@ -337,25 +321,20 @@ class _BiLSTMFn(torch.autograd.Function):
         bias = T._axpby_raw(b_ih.detach().contiguous(), 1.0, b_hh.detach().contiguous(), 1.0)
         y = T._empty(N, S, 2*H, like=x)
         act, cs = torch.empty(2, N, S, 4*H, dtype=io, device=x.device), T._empty(2, N, S, H, like=x)
-        hip.check(lib.brv_lstm_tile_forward(hip.ptr(gates), hip.ptr(w_hh), hip.ptr(bias), hip.ptr(y),
-                                            hip.ptr(act), hip.ptr(cs), 2*N, S, H, 2, 2, 2*H, H,
-                                            2*int(lowp), hip.stream()), 'brv_lstm_tile_forward')
+        hip.call('brv_lstm_tile_forward', gates, w_hh, bias, y, act, cs, 2*N, S, H, 2, 2, 2*H, H, 2*int(lowp),
+                 hip.stream())
         ctx.save_for_backward(x, w_ih, w_hh, y, act, cs)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        lib = hip.lib()
         x, w_ih, w_hh, y, act, cs = ctx.saved_tensors            # w_ih interleaved
         N, S, I = x.shape
         H = w_hh.shape[-1]
         lowp, NS = ctx.lowp, N*S
         dy = dy.contiguous()
         dg = torch.empty(2, N, S, 4*H, dtype=act.dtype, device=x.device)     # bf16 under use_amp
-        hip.check(lib.brv_lstm_tile_backward(hip.ptr(act), hip.ptr(cs), hip.ptr(w_hh), hip.ptr(dy),
-                                             hip.ptr(dg), 2*N, S, H, 2, 2, 2*H, H, 2*int(lowp),
-                                             hip.stream()),
-                  'brv_lstm_tile_backward')
+        hip.call('brv_lstm_tile_backward', act, cs, w_hh, dy, dg, 2*N, S, H, 2, 2, 2*H, H, 2*int(lowp), hip.stream())
         dx = torch.empty_like(x)                      # sum over both directions: dg_g @ W_ih_g
         _gemm(dg, w_ih, dx, 1, NS, I, 4*H, 4*H, I, I, kbatch=2, a_kbs=NS*4*H, b_kbs=4*H*I,
               lowp=lowp)
@@ -388,16 +367,14 @@ class _WindowFn(torch.autograd.Function):
         N = x.shape[0]
         n = (S - ks)//hs + 1
         col = T._empty(N, C*ks, n, like=x)
-        hip.check(hip.lib().brv_im2col(hip.ptr(x), hip.ptr(col), N, *_WindowFn._geom(C, S, ks, hs),
-                                       hip.stream()), 'brv_im2col')
+        hip.call('brv_im2col', x, col, N, *_WindowFn._geom(C, S, ks, hs), hip.stream())
         return col
 
     @staticmethod
     def _fold(col, bias, C, S, ks, hs):
         N = col.shape[0]
         out = T._empty(N, C, S, like=col)
-        hip.check(hip.lib().brv_col2im(hip.ptr(col), hip.ptr(bias), hip.ptr(out), N,
-                                       *_WindowFn._geom(C, S, ks, hs), hip.stream()), 'brv_col2im')
+        hip.call('brv_col2im', col, bias, out, N, *_WindowFn._geom(C, S, ks, hs), hip.stream())
         return out
 
     @staticmethod
@@ -417,8 +394,7 @@ class _WindowFn(torch.autograd.Function):
         db = None
         if has_bias:
             db = T._empty(C, like=g)
-            hip.check(hip.lib().brv_row_sum(hip.ptr(g), hip.ptr(db), g.shape[0], C, S, hip.stream()),
-                      'brv_row_sum')
+            hip.call('brv_row_sum', g, db, g.shape[0], C, S, hip.stream())
         return _WindowFn._unfold(g, C, S, ks, hs), db, None, None, None, None, None
 
 
@@ -438,8 +414,7 @@ class _HeadPermuteFn(torch.autograd.Function):
     def _run(x, B, Tn, Fq, H, E, merge):
         x = x.contiguous()
         out = torch.empty((B, Tn, Fq, H*E) if merge else (B, H, Tn, E, Fq), dtype=torch.float32, device=x.device)
-        hip.check(hip.lib().brv_head_permute(hip.ptr(x), hip.ptr(out), B, Tn, Fq, H, E, int(merge), hip.stream()),
-                  'brv_head_permute')
+        hip.call('brv_head_permute', x, out, B, Tn, Fq, H, E, int(merge), hip.stream())
         return out
 
     @staticmethod
@@ -617,8 +592,7 @@ class TFGridNet(BreverBaseModel):
         with torch.no_grad():                          # the mixture carries no gradient
             x = x.float().contiguous()
             std = torch.empty(B, dtype=torch.float32, device=x.device)
-            hip.check(hip.lib().brv_row_std(hip.ptr(x), hip.ptr(std), B, M*L, hip.stream()),
-                      'brv_row_std')
+            hip.call('brv_row_std', x, std, B, M*L, hip.stream())
             xn = _RowScaleFn.apply(x.view(B, M*L), std, True).view(B, M, L)
             spec = self.stft(xn).transpose(2, 3)                              # (B, M, T, F)
             batch = torch.cat((spec.real, spec.imag), dim=1).contiguous()     # (B, 2M, T, F)

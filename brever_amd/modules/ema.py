@@ -21,8 +21,7 @@ from .. import hip
 def _ema_step(ema_param, param, beta):
     if ema_param.is_cuda and ema_param.dtype == torch.float32 and ema_param.is_contiguous():
         src = param.detach().contiguous()
-        hip.check(hip.lib().brv_ema_update(hip.ptr(ema_param), hip.ptr(src), float(1 - beta),
-                                           ema_param.numel(), hip.stream()), 'brv_ema_update')
+        hip.call('brv_ema_update', ema_param, src, float(1 - beta), ema_param.numel(), hip.stream())
     else:
         ema_param += (1 - beta)*(param.detach() - ema_param)
 

@@ -86,26 +86,22 @@ class FeatureExtractor:
             raise ValueError(f'binaural features need 2 channels, got {C}')
         spec = torch.view_as_real(x.to(torch.complex64).contiguous())
         cue = torch.empty(B, bins, F, dtype=torch.float32, device=x.device)
-        hip.check(hip.lib().brv_binaural(hip.ptr(spec), hip.ptr(cue), B, bins*F, mode, float(eps),
-                                         hip.stream()), 'brv_binaural')
+        hip.call('brv_binaural', spec, cue, B, bins*F, mode, float(eps), hip.stream())
         return self.mel_fb(cue)
 
     def ic(self, x, tau=10e-3):
         """Interaural coherence (features.py:263-293) of (B, 2, bins, frames) complex ->
         (B, n_filters, frames)."""
         hip.require_device(x)
-        lib = hip.lib()
         B, C, bins, F = x.shape
         if C != 2:
             raise ValueError(f'binaural features need 2 channels, got {C}')
         alpha = math.exp(-self.hop_length/(tau*self.fs))
         spec = torch.view_as_real(x.to(torch.complex64).contiguous())
         coh = torch.empty(B, bins, F, dtype=torch.float32, device=x.device)
-        hip.check(lib.brv_interaural_coherence(hip.ptr(spec), hip.ptr(coh), B, bins, F, alpha,
-                                               hip.stream()), 'brv_interaural_coherence')
+        hip.call('brv_interaural_coherence', spec, coh, B, bins, F, alpha, hip.stream())
         out = self.mel_fb(coh).contiguous()
-        hip.check(lib.brv_compress(hip.ptr(out), hip.ptr(out), out.numel(), 3, 0.0, hip.stream()),
-                  'brv_compress')
+        hip.call('brv_compress', out, out, out.numel(), 3, 0.0, hip.stream())
         return out
 
     def _dct_matrix(self, M, device):
@@ -122,27 +118,21 @@ class FeatureExtractor:
         """(B, channels, bins, frames) complex -> (B, n_filters, frames), or (B, 39, frames) with
         the DCT (13 cepstral rows + their first and second differences)."""
         hip.require_device(x)
-        lib = hip.lib()
         B, C, bins, F = x.shape
         spec = torch.view_as_real(x.to(torch.complex64).contiguous())
         power = torch.empty(B, bins, F, dtype=torch.float32, device=x.device)
-        hip.check(lib.brv_fbe_power(hip.ptr(spec), hip.ptr(power), B, C, bins*F, hip.stream()),
-                  'brv_fbe_power')
+        hip.call('brv_fbe_power', spec, power, B, C, bins*F, hip.stream())
         out = self.mel_fb(power).contiguous()
         M = out.shape[1]
         if normalize:
-            hip.check(lib.brv_col_normalize(hip.ptr(out), B, M, F, float(eps), hip.stream()),
-                      'brv_col_normalize')
+            hip.call('brv_col_normalize', out, B, M, F, float(eps), hip.stream())
         if compression:
-            hip.check(lib.brv_compress(hip.ptr(out), hip.ptr(out), out.numel(), compression,
-                                       float(eps), hip.stream()), 'brv_compress')
+            hip.call('brv_compress', out, out, out.numel(), compression, float(eps), hip.stream())
         if dct:
             D = self._dct_matrix(M, x.device)
             K = D.shape[0]
             cep = torch.empty(B, K, F, dtype=torch.float32, device=x.device)
-            hip.check(lib.brv_matmul_f32(hip.ptr(D), hip.ptr(out), hip.ptr(cep), B, K, F, M, 0,
-                                         hip.stream()), 'brv_matmul_f32')
+            hip.call('brv_matmul_f32', D, out, cep, B, K, F, M, 0, hip.stream())
             out = torch.empty(B, 3*K, F, dtype=torch.float32, device=x.device)
-            hip.check(lib.brv_deltas(hip.ptr(cep), hip.ptr(out), B, K, F, hip.stream()),
-                      'brv_deltas')
+            hip.call('brv_deltas', cep, out, B, K, F, hip.stream())
         return out

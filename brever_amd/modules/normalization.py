@@ -24,9 +24,8 @@ class _CausalGroupNormFunction(torch.autograd.Function):
         stats = torch.empty(B*groups, T, 2, dtype=torch.float32, device=x.device)
         scratch = torch.empty(lib.brv_causal_groupnorm_scratch_bytes(B, groups, T), dtype=torch.uint8,
                               device=x.device)
-        hip.check(lib.brv_causal_groupnorm_forward(
-            hip.ptr(x), hip.ptr(gain), hip.ptr(bias), hip.ptr(y), hip.ptr(stats), hip.ptr(scratch),
-            B, C, inner, T, groups, float(eps), hip.stream()), 'brv_causal_groupnorm_forward')
+        hip.call('brv_causal_groupnorm_forward', x, gain, bias, y, stats, scratch, B, C, inner, T, groups, float(eps),
+                 hip.stream())
         ctx.save_for_backward(x, gain, stats)
         ctx.cfg = (groups, inner)
         return y
@@ -42,10 +41,8 @@ class _CausalGroupNormFunction(torch.autograd.Function):
         dgain, dbias = torch.empty_like(gain), torch.empty_like(gain)
         scratch = torch.empty(lib.brv_causal_groupnorm_scratch_bytes(B, groups, T), dtype=torch.uint8,
                               device=x.device)
-        hip.check(lib.brv_causal_groupnorm_backward(
-            hip.ptr(x), hip.ptr(dy), hip.ptr(gain), hip.ptr(stats), hip.ptr(dx), hip.ptr(dgain),
-            hip.ptr(dbias), hip.ptr(scratch), None, B, C, inner, T, groups, hip.stream()),
-            'brv_causal_groupnorm_backward')
+        hip.call('brv_causal_groupnorm_backward', x, dy, gain, stats, dx, dgain, dbias, scratch, None, B, C, inner, T,
+                 groups, hip.stream())
         return dx, dgain, dbias, None, None
 
 

@@ -50,10 +50,8 @@ class Resample(nn.Module):
         K = self.kernel.shape[-1]
         padding, (Ho, Wo), up = self.plan(x.shape, up_or_down)
         y = torch.empty(B, C, Ho, Wo, dtype=torch.float32, device=x.device)
-        hip.check(hip.lib().brv_fir_resample2d(
-            hip.ptr(x), hip.ptr(self.kernel.float().contiguous()), hip.ptr(y), B*C, H, W, Ho, Wo, K,
-            padding[0], padding[1], int(up), 4.0 if up else 1.0, hip.stream()),
-            'brv_fir_resample2d')
+        hip.call('brv_fir_resample2d', x, self.kernel.float().contiguous(), y, B*C, H, W, Ho, Wo, K, padding[0],
+                 padding[1], int(up), 4.0 if up else 1.0, hip.stream())
         return y
 
 

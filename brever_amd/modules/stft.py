@@ -54,9 +54,7 @@ class _SpecCompress(torch.autograd.Function):
     def forward(ctx, x, compression, scale):
         xr = _complex_pairs(x)
         y = torch.empty_like(xr)
-        hip.check(hip.lib().brv_spec_compress(hip.ptr(xr), hip.ptr(y), x.numel(),
-                                              float(compression), float(scale), hip.stream()),
-                  'brv_spec_compress')
+        hip.call('brv_spec_compress', xr, y, x.numel(), float(compression), float(scale), hip.stream())
         ctx.save_for_backward(xr)
         ctx.cs = (float(compression), float(scale))
         return torch.view_as_complex(y)
@@ -66,9 +64,7 @@ class _SpecCompress(torch.autograd.Function):
         xr, = ctx.saved_tensors
         gy = _complex_pairs(grad)
         gx = torch.empty_like(xr)
-        hip.check(hip.lib().brv_spec_compress_backward(
-            hip.ptr(xr), hip.ptr(gy), hip.ptr(gx), xr.numel()//2, *ctx.cs, hip.stream()),
-            'brv_spec_compress_backward')
+        hip.call('brv_spec_compress_backward', xr, gy, gx, xr.numel()//2, *ctx.cs, hip.stream())
         return torch.view_as_complex(gx), None, None
 
 
@@ -111,19 +107,15 @@ class _IstftLinear(torch.autograd.Function):
         F, out_len, scale = ctx.geom
         if not stft.center:
             raise NotImplementedError('gradient of STFT.backward needs center=True')
-        lib = hip.lib()
         dy = dy.float().contiguous()
         rows = dy.shape[0]
         tb = stft._tables(dy.device)
         u = torch.empty_like(dy)
-        hip.check(lib.brv_istft_env_divide(hip.ptr(dy), hip.ptr(tb['window']), hip.ptr(u), rows,
-                                           out_len, stft.n_fft, stft.hop_length, F, hip.stream()),
-                  'brv_istft_env_divide')
+        hip.call('brv_istft_env_divide', dy, tb['window'], u, rows, out_len, stft.n_fft, stft.hop_length, F,
+                 hip.stream())
         dspec = torch.empty(rows, stft.bins, F, 2, dtype=torch.float32, device=dy.device)
-        hip.check(lib.brv_dft64_forward(
-            hip.ptr(u), hip.ptr(tb['synthesis']), hip.ptr(dspec), rows, out_len, stft.n_fft,
-            stft.hop_length, stft.n_fft//2, F, stft.bins, 1.0, 1.0/scale, hip.stream()),
-            'brv_dft64_forward')
+        hip.call('brv_dft64_forward', u, tb['synthesis'], dspec, rows, out_len, stft.n_fft, stft.hop_length,
+                 stft.n_fft//2, F, stft.bins, 1.0, 1.0/scale, hip.stream())
         return torch.view_as_complex(dspec), None, None, None
 
 
@@ -225,7 +217,6 @@ class STFT:
         """pad_mode != 'constant': the right padding of ``STFT.pad`` and torch.stft's centre
         padding are applied one after the other, each in ``pad_mode`` (zeros need no copy: the
         framed product reads them implicitly). Values only (no gradient through the padding)."""
-        lib = hip.lib()
         mode = self._PAD_MODES[self.pad_mode]
         rows, L = x2.shape
         padded = (self.frame_count(L) - 1)*self.hop_length + self.frame_length
@@ -235,12 +226,13 @@ class STFT:
             stages.append((half, padded + 2*half))
         for left, out_len in stages:
             y = torch.empty(rows, out_len, dtype=torch.float32, device=x2.device)
-            status = lib.brv_pad_signal(hip.ptr(x2), hip.ptr(y), rows, x2.shape[-1], left, out_len,
-                                        mode, hip.stream())
-            if status == -2:
+            try:
+                hip.call('brv_pad_signal', x2, y, rows, x2.shape[-1], left, out_len, mode, hip.stream())
+            except RuntimeError as e:
+                if ' status -2:' not in str(e):
+                    raise
                 raise ValueError(f"pad_mode='{self.pad_mode}' needs padding smaller than the "
-                                 f'input ({x2.shape[-1]} samples)')
-            hip.check(status, 'brv_pad_signal')
+                                 f'input ({x2.shape[-1]} samples)') from None
             x2 = y
         return x2
 
@@ -251,44 +243,34 @@ class STFT:
             x2 = self._explicit_padding(x2)
             L, pad_left = x2.shape[-1], 0
         spec = torch.empty(rows, self.bins, F, 2, dtype=torch.float32, device=x2.device)
-        hip.check(hip.lib().brv_dft64_forward(
-            hip.ptr(x2), hip.ptr(basis), hip.ptr(spec), rows, L, self.n_fft, self.hop_length,
-            pad_left, F, self.bins, float(compression), float(scale), hip.stream()),
-            'brv_dft64_forward')
+        hip.call('brv_dft64_forward', x2, basis, spec, rows, L, self.n_fft, self.hop_length, pad_left, F, self.bins,
+                 float(compression), float(scale), hip.stream())
         return torch.view_as_complex(spec)
 
     def _dft_adjoint(self, dspec, L, scale=1.0):
         """dx (rows, L): adjoint of ``scale * _dft_forward`` applied to dspec (rows, bins, F, 2)."""
         if self.pad_mode != 'constant':
             raise NotImplementedError("gradient through pad_mode != 'constant' is not built")
-        lib = hip.lib()
         rows, F = dspec.shape[0], dspec.shape[2]
         _, pad_left = self._geometry(L)
         frames = torch.empty(rows, F, self.n_fft, dtype=torch.float32, device=dspec.device)
-        hip.check(lib.brv_dft64_synthesis(
-            hip.ptr(dspec), hip.ptr(self._tables(dspec.device)['basis']), hip.ptr(frames), rows, F,
-            self.n_fft, self.bins, 1.0, 1.0/float(scale), hip.stream()), 'brv_dft64_synthesis')
+        hip.call('brv_dft64_synthesis', dspec, self._tables(dspec.device)['basis'], frames, rows, F, self.n_fft,
+                 self.bins, 1.0, 1.0/float(scale), hip.stream())
         dx = torch.empty(rows, L, dtype=torch.float32, device=dspec.device)
-        hip.check(lib.brv_overlap_add(hip.ptr(frames), None, hip.ptr(dx), rows, F, self.n_fft,
-                                      self.hop_length, pad_left, L, hip.stream()),
-                  'brv_overlap_add')
+        hip.call('brv_overlap_add', frames, None, dx, rows, F, self.n_fft, self.hop_length, pad_left, L, hip.stream())
         return dx
 
     def _istft(self, spec, compression=1.0, scale=1.0):
-        lib = hip.lib()
         rows, bins, F = spec.shape
         tb = self._tables(spec.device)
         frames = torch.empty(rows, F, self.n_fft, dtype=torch.float32, device=spec.device)
-        hip.check(lib.brv_dft64_synthesis(
-            hip.ptr(_complex_pairs(spec)), hip.ptr(tb['synthesis']), hip.ptr(frames), rows, F,
-            self.n_fft, bins, float(compression), float(scale), hip.stream()),
-            'brv_dft64_synthesis')
+        hip.call('brv_dft64_synthesis', _complex_pairs(spec), tb['synthesis'], frames, rows, F, self.n_fft, bins,
+                 float(compression), float(scale), hip.stream())
         pad_left = self.n_fft//2 if self.center else 0
         out_len = self.n_fft + self.hop_length*(F - 1) - 2*pad_left
         y = torch.empty(rows, out_len, dtype=torch.float32, device=spec.device)
-        hip.check(lib.brv_overlap_add(hip.ptr(frames), hip.ptr(tb['window']), hip.ptr(y), rows, F,
-                                      self.n_fft, self.hop_length, pad_left, out_len, hip.stream()),
-                  'brv_overlap_add')
+        hip.call('brv_overlap_add', frames, tb['window'], y, rows, F, self.n_fft, self.hop_length, pad_left, out_len,
+                 hip.stream())
         return y
 
     # -- public interface --------------------------------------------------------------------
@@ -313,8 +295,7 @@ class STFT:
             pairs = _complex_pairs(out)
             mag = torch.empty(out.shape, dtype=torch.float32, device=out.device)
             phase = torch.empty_like(mag)
-            hip.check(hip.lib().brv_mag_phase(hip.ptr(pairs), hip.ptr(mag), hip.ptr(phase),
-                                              out.numel(), hip.stream()), 'brv_mag_phase')
+            hip.call('brv_mag_phase', pairs, mag, phase, out.numel(), hip.stream())
             return mag, phase
         raise ValueError('return_type must be complex, real_imag or '
                          f'mag_phase, got {return_type}')
@@ -330,8 +311,7 @@ class STFT:
                 hip.require_device(mag, phase)
                 m, ph = mag.float().contiguous(), phase.float().contiguous()
                 pairs = torch.empty(*m.shape, 2, dtype=torch.float32, device=m.device)
-                hip.check(hip.lib().brv_polar(hip.ptr(m), hip.ptr(ph), hip.ptr(pairs), m.numel(),
-                                              hip.stream()), 'brv_polar')
+                hip.call('brv_polar', m, ph, pairs, m.numel(), hip.stream())
                 x = torch.view_as_complex(pairs)
         elif input_type != 'complex':
             raise ValueError('input_type must be complex, real_imag or '
@@ -419,10 +399,8 @@ class ConvSTFT:
         bins = n//2 + 1
         x2 = x.reshape(rows, L).float().contiguous()
         spec = torch.empty(rows, bins, F, 2, dtype=torch.float32, device=x.device)
-        hip.check(hip.lib().brv_framed_dft_forward(
-            hip.ptr(x2), hip.ptr(self._get_basis(x.device)), hip.ptr(spec), rows, L, n, hop,
-            side, F, float(self.compression_factor), float(self.scale_factor), hip.stream()),
-            'brv_framed_dft_forward')
+        hip.call('brv_framed_dft_forward', x2, self._get_basis(x.device), spec, rows, L, n, hop, side, F,
+                 float(self.compression_factor), float(self.scale_factor), hip.stream())
         out = torch.view_as_complex(spec).view(*lead, bins, F)
         if return_type == 'complex':
             return out
@@ -451,10 +429,8 @@ class ConvSTFT:
         spec = torch.view_as_real(x.reshape(rows, bins, F).to(torch.complex64).contiguous())
         scratch = torch.empty(rows, F, n, dtype=torch.float32, device=x.device)
         y = torch.empty(rows, out_len, dtype=torch.float32, device=x.device)
-        hip.check(hip.lib().brv_framed_dft_transpose(
-            hip.ptr(spec), hip.ptr(self._get_basis(x.device)), hip.ptr(scratch), hip.ptr(y), rows,
-            F, n, hop, side, out_len, float(self.compression_factor), float(self.scale_factor),
-            hip.stream()), 'brv_framed_dft_transpose')
+        hip.call('brv_framed_dft_transpose', spec, self._get_basis(x.device), scratch, y, rows, F, n, hop, side,
+                 out_len, float(self.compression_factor), float(self.scale_factor), hip.stream())
         if not self.normalized:
             y = y/self._normalization_factor**2
         return y.view(*lead, out_len)
@@ -508,9 +484,7 @@ class MelFilterbank:
         rows = int(np.prod(lead)) if lead else 1
         x2 = x.reshape(rows, K, N).float().contiguous()
         out = torch.empty(rows, a.shape[0], N, dtype=torch.float32, device=x.device)
-        hip.check(hip.lib().brv_matmul_f32(
-            hip.ptr(a), hip.ptr(x2), hip.ptr(out), rows, a.shape[0], N, K, 0,
-            hip.stream()), 'brv_matmul_f32')
+        hip.call('brv_matmul_f32', a, x2, out, rows, a.shape[0], N, K, 0, hip.stream())
         return out.view(*lead, a.shape[0], N)
 
     def __call__(self, x):

@@ -101,12 +101,9 @@ class FlatAdam(torch.optim.Adam):
         slot = self._slot
         step = self._step_count + 1      # (committed after the launch: a failed step retried keeps its bias correction)
         try:
-            hip.check(hip.lib().brv_clip_adam_step2(
-                hip.ptr(flat), hip.ptr(grads), hip.ptr(grads2), hip.ptr(self._exp_avg),
-                hip.ptr(self._exp_avg_sq), flat.numel(), float(grad_scale),
-                float(max_norm), float(group['lr']), float(beta1), float(beta2),
-                float(group['eps']), step, hip.ptr(self._scratch), slot,
-                hip.ptr(self.last_grad_norm), hip.stream()), 'brv_clip_adam_step2')
+            hip.call('brv_clip_adam_step2', flat, grads, grads2, self._exp_avg, self._exp_avg_sq, flat.numel(),
+                     float(grad_scale), float(max_norm), float(group['lr']), float(beta1), float(beta2),
+                     float(group['eps']), step, self._scratch, slot, self.last_grad_norm, hip.stream())
         except Exception:
             # the accumulators' zero / non-zero state is unknown after a failed launch: start over
             self._scratch.zero_()

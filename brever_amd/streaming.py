@@ -108,10 +108,7 @@ class ConvTasNetStreamer(_StreamSlots):
         self.hop = model.cfg.filter_length//2
         self.lag = self.hop               # the output lags the input by one hop
         self.sources = model.output_sources
-        nbytes = hip.lib().brv_ctn_stream_state_bytes(model._cfg_ptr())
-        if nbytes < 0:
-            hip.check(int(nbytes), 'brv_ctn_stream_state_bytes')
-        self.state_bytes = int(nbytes)
+        self.state_bytes = int(hip.query('brv_ctn_stream_state_bytes', model._cfg_ptr()))
         self._state = torch.zeros(self.max_streams*self.state_bytes, dtype=torch.uint8,
                                   device=model.flat_params().device)
         self._open = [False]*self.max_streams
@@ -120,8 +117,7 @@ class ConvTasNetStreamer(_StreamSlots):
 
     def _reset(self, ids):
         t = self._ids_tensor(ids)
-        hip.check(hip.lib().brv_ctn_stream_reset(self.model._cfg_ptr(), hip.ptr(self._state), hip.ptr(t),
-                                                 len(ids), hip.stream()), 'brv_ctn_stream_reset')
+        hip.call('brv_ctn_stream_reset', self.model._cfg_ptr(), self._state, t, len(ids), hip.stream())
 
     # ---- compute --------------------------------------------------------------------------------
     def process(self, x, ids):
@@ -140,19 +136,15 @@ class ConvTasNetStreamer(_StreamSlots):
         hip.require_device(flat)
         if flat.device != self.device:
             raise RuntimeError(f'the model moved to {flat.device}; the streams live on {self.device}')
-        lib = hip.lib()
         cfg = model._cfg_ptr()
-        nbytes = lib.brv_ctn_stream_workspace_bytes(cfg, n, hops, int(self.use_amp))
-        if nbytes < 0:
-            hip.check(int(nbytes), 'brv_ctn_stream_workspace_bytes')
+        nbytes = hip.query('brv_ctn_stream_workspace_bytes', cfg, n, hops, int(self.use_amp))
         if self._ws is None or self._ws.numel() < nbytes:
             self._ws = None
             self._ws = torch.empty(int(nbytes), dtype=torch.uint8, device=self.device)
         y = torch.empty(n, self.sources, L, dtype=torch.float32, device=self.device)
         t = self._ids_tensor(ids)
-        hip.check(lib.brv_ctn_stream_step(
-            cfg, hip.ptr(flat), hip.ptr(self._state), hip.ptr(t), n, hip.ptr(x), hops, hip.ptr(y),
-            int(self.use_amp), hip.ptr(self._ws), self._ws.numel(), None, hip.stream()), 'brv_ctn_stream_step')
+        hip.call('brv_ctn_stream_step', cfg, flat, self._state, t, n, x, hops, y, int(self.use_amp), self._ws,
+                 self._ws.numel(), None, hip.stream())
         return y
 
     def flush(self, ids, rest=None):
@@ -175,8 +167,7 @@ class ConvTasNetStreamer(_StreamSlots):
             out.append(self.process(x, ids))
         tail = torch.empty(n, self.sources, self.hop, dtype=torch.float32, device=self.device)
         t = self._ids_tensor(ids)
-        hip.check(hip.lib().brv_ctn_stream_tail(self.model._cfg_ptr(), hip.ptr(self._state), hip.ptr(t), n,
-                                                hip.ptr(tail), hip.stream()), 'brv_ctn_stream_tail')
+        hip.call('brv_ctn_stream_tail', self.model._cfg_ptr(), self._state, t, n, tail, hip.stream())
         out.append(tail[..., :r] if r else tail)
         return torch.cat(out, dim=-1)
 
@@ -195,9 +186,10 @@ class DCCRNStreamer(_StreamSlots):
         self.lag = self.lag_for(model)           # (validates the model)
         if int(max_streams) < 1:
             raise ValueError(f'max_streams must be >= 1, got {max_streams}')
-        nbytes = hip.lib().brv_dccrn_stream_state_bytes(ctypes.byref(self._geometry(model)))
-        if nbytes < 0:
-            raise ValueError(f'this DCCRN cannot stream: {hip.lib().brv_last_error().decode()}')
+        try:
+            nbytes = hip.query('brv_dccrn_stream_state_bytes', ctypes.byref(self._geometry(model)))
+        except RuntimeError:
+            raise ValueError(f'this DCCRN cannot stream: {hip.lib().brv_last_error().decode()}') from None
         hip.require_device(model.flat_params())
         self.model = model
         self.use_amp = bool(use_amp)
@@ -304,8 +296,7 @@ class DCCRNStreamer(_StreamSlots):
     def _reset(self, ids):
         t = self._ids_tensor(ids)
         cfg = self._geometry(self.model)
-        hip.check(hip.lib().brv_dccrn_stream_reset(ctypes.byref(cfg), hip.ptr(self._state), hip.ptr(t), len(ids),
-                                                   hip.stream()), 'brv_dccrn_stream_reset')
+        hip.call('brv_dccrn_stream_reset', ctypes.byref(cfg), self._state, t, len(ids), hip.stream())
         for i in ids:
             self._hops[i] = 0
             self._ended[i] = False
@@ -318,10 +309,7 @@ class DCCRNStreamer(_StreamSlots):
         if flat.device != self.device:
             raise RuntimeError(f'the model moved to {flat.device}; the streams live on {self.device}')
         cfg = self._config()
-        lib = hip.lib()
-        nbytes = lib.brv_dccrn_stream_workspace_bytes(ctypes.byref(cfg), n, hops, int(self.use_amp))
-        if nbytes < 0:
-            hip.check(int(nbytes), 'brv_dccrn_stream_workspace_bytes')
+        nbytes = hip.query('brv_dccrn_stream_workspace_bytes', ctypes.byref(cfg), n, hops, int(self.use_amp))
         if self._ws is None or self._ws.numel() < nbytes:
             self._ws = None
             self._ws = torch.empty(int(nbytes), dtype=torch.uint8, device=self.device)
@@ -345,10 +333,8 @@ class DCCRNStreamer(_StreamSlots):
         cfg, flat, tb = self._call(ids, n, hops)
         y = torch.empty(n, L, dtype=torch.float32, device=self.device)
         t = self._ids_tensor(ids)
-        hip.check(hip.lib().brv_dccrn_stream_step(
-            ctypes.byref(cfg), hip.ptr(flat), hip.ptr(tb['window']), hip.ptr(tb['basis']), hip.ptr(tb['synthesis']),
-            hip.ptr(self._state), hip.ptr(t), n, hip.ptr(x), hops, hip.ptr(y), int(self.use_amp), hip.ptr(self._ws),
-            self._ws.numel(), None, hip.stream()), 'brv_dccrn_stream_step')
+        hip.call('brv_dccrn_stream_step', ctypes.byref(cfg), flat, tb['window'], tb['basis'], tb['synthesis'],
+                 self._state, t, n, x, hops, y, int(self.use_amp), self._ws, self._ws.numel(), None, hip.stream())
         for i in ids:
             self._hops[i] += hops
         return y
@@ -381,10 +367,9 @@ class DCCRNStreamer(_StreamSlots):
         cfg, flat, tb = self._call(ids, n, hops)
         y = torch.empty(n, self.lag + r, dtype=torch.float32, device=self.device)
         t = self._ids_tensor(ids)
-        hip.check(hip.lib().brv_dccrn_stream_tail(
-            ctypes.byref(cfg), hip.ptr(flat), hip.ptr(tb['window']), hip.ptr(tb['basis']), hip.ptr(tb['synthesis']),
-            hip.ptr(self._state), hip.ptr(t), n, hip.ptr(rest) if r else None, r, hip.ptr(y), int(self.use_amp),
-            hip.ptr(self._ws), self._ws.numel(), None, hip.stream()), 'brv_dccrn_stream_tail')
+        hip.call('brv_dccrn_stream_tail', ctypes.byref(cfg), flat, tb['window'], tb['basis'], tb['synthesis'],
+                 self._state, t, n, rest if r else None, r, y, int(self.use_amp), self._ws, self._ws.numel(), None,
+                 hip.stream())
         for i in ids:
             self._ended[i] = True
         return y

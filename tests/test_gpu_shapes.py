@@ -1004,3 +1004,20 @@ def test_mode_mismatch_between_calls_is_loud(monkeypatch):
     snr(out, batch[:, 1:].cuda(), lengths.cuda()).mean().backward()
     got = torch.cat([p.grad.reshape(-1) for p in net.parameters()])
     assert torch.isfinite(got).all()
+
+
+@pytest.mark.parametrize('sign', [1.0, -1.0])
+def test_call_with_tensors_equals_the_call_with_explicit_pointers(sign):
+    """`hip.call` hands a tensor's address to a pointer parameter itself (`hip._c_ptr.from_param`): on
+    `brv_combine` at n = 5 (odd, below one wavefront) the result is bit for bit the one of the same call with
+    `hip.ptr(...)` arguments, and both are a + sign*b (one fp32 operation per element: exact)."""
+    from brever_amd import hip
+    dev = _cuda()
+    gen = torch.Generator().manual_seed(11)
+    a, b = torch.randn(5, generator=gen).to(dev), torch.randn(5, generator=gen).to(dev)
+    by_tensor, by_pointer = torch.full((7,), 9.0, device=dev), torch.full((7,), 9.0, device=dev)
+    hip.call('brv_combine', a, b, by_tensor, 5, sign, hip.stream())
+    hip.call('brv_combine', hip.ptr(a), hip.ptr(b), hip.ptr(by_pointer), 5, sign, hip.stream())
+    assert torch.equal(by_tensor, by_pointer)
+    assert torch.equal(by_tensor[:5], a + sign*b)
+    assert torch.equal(by_tensor[5:], torch.full((2,), 9.0, device=dev))       # nothing written past n

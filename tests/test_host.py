@@ -152,6 +152,112 @@ def test_library_exports_every_declared_symbol():
     assert lib.brv_version() >= 100
 
 
+def test_header_parser_is_strict():
+    """`hip.parse_header`: a closed type map and no default -- a type it does not know or a prototype it cannot
+    split raises, naming the prototype; comments declare nothing."""
+    ptr, i64 = hip._c_ptr, ctypes.c_int64
+    good = hip.parse_header("""
+        /* brv_in_a_comment(int64_t n); spans
+           lines: int brv_other_comment(void); */
+        // int brv_line_comment(float x);
+        #define BRV_MACRO(x) brv_macro(x);
+        typedef void* brv_stream_t;
+        typedef struct brv_thing { int32_t a, b; const float* p[4]; } brv_thing;
+        int brv_a(const brv_thing* cfg, const float* x, float* y, int64_t n, int32_t part, int flag,
+                  uint32_t bits, float eps, const char* name, char* buf, brv_stream_t stream);
+        int64_t brv_b(int64_t n);
+        void* brv_c(int by);
+        const char* brv_d(void);
+        void brv_e(void* handle);
+    """)
+    assert good == {
+        'brv_a': (ctypes.c_int, [ptr, ptr, ptr, i64, ctypes.c_int32, ctypes.c_int, ctypes.c_uint32, ctypes.c_float,
+                                 ctypes.c_char_p, ctypes.c_char_p, ptr]),
+        'brv_b': (i64, [i64]),
+        'brv_c': (ctypes.c_void_p, [ctypes.c_int]),
+        'brv_d': (ctypes.c_char_p, []),
+        'brv_e': (None, [ptr]),
+    }
+    assert good['brv_c'][0] is not ptr                     # a returned pointer is a plain c_void_p (an int)
+    for bad in ('int brv_x(const float* a, size_t n);', 'int brv_x(unsigned int n);', 'size_t brv_x(int64_t n);',
+                'double brv_x(void);', 'int brv_x(double v);', 'float* brv_x(void);', 'int brv_x(int64_t);\n'
+                'int brv_y(const float* a, void (*done)(int), int64_t n);', 'int brv_x(int (*cb)(void));',
+                'int brv_x(float** rows);', 'int (*brv_x(void))(int);', 'int brv_x(int64_t n'):
+        with pytest.raises(RuntimeError, match='brv_y' if 'brv_y' in bad else 'brv_x'):
+            hip.parse_header(bad)
+
+
+def test_signatures_come_from_the_header():
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    assert os.path.samefile(hip.HEADER_PATH, os.path.join(root, 'include', 'brever_hip.h'))
+    header = open(hip.HEADER_PATH).read()
+    declared = set(re.findall(r'\b(brv_[a-z0-9_]+)\s*\(', header)) - {'brv_ctn_config'}
+    assert set(hip.SIGNATURES) == declared and len(declared) == 200
+    assert hip.SIGNATURES == hip.parse_header(header)
+    # every entry point whose last parameter is the stream ends with the pointer argtype
+    text = re.sub(r'/\*.*?\*/', '', header, flags=re.S)
+    with_stream = set(re.findall(r'\b(brv_\w+)\s*\([^;]*\bbrv_stream_t\s+\w+\s*\)\s*;', text))
+    assert len(with_stream) > 150
+    for name in with_stream:
+        assert hip.SIGNATURES[name][1][-1] is hip._c_ptr, name
+    # spot checks against the header's text: a float is a float, a count is 64 bits wide
+    assert hip.SIGNATURES['brv_combine'] == (ctypes.c_int, [hip._c_ptr]*3 + [ctypes.c_int64, ctypes.c_float,
+                                                                              hip._c_ptr])
+    assert hip.SIGNATURES['brv_ctn_workspace_offset'][1][3] is ctypes.c_char_p
+    assert hip.SIGNATURES['brv_last_error'] == (ctypes.c_char_p, [])
+    assert hip.SIGNATURES['brv_prof_destroy'][0] is None
+
+
+def test_a_missing_header_is_named(monkeypatch, tmp_path):
+    monkeypatch.setattr(hip, 'HEADER_PATH', str(tmp_path/'include'/'brever_hip.h'))
+    with pytest.raises(RuntimeError, match=str(tmp_path/'include'/'brever_hip.h')):
+        hip._header_signatures()
+
+
+def test_pointer_argtype_takes_tensors():
+    """`hip._c_ptr.from_param`: a tensor passes its address; whatever `c_void_p` takes goes through as before."""
+    conv = hip._c_ptr.from_param
+    assert issubclass(hip._c_ptr, ctypes.c_void_p)
+    assert conv(None) is None
+    t = torch.zeros(4)
+    assert conv(t).value == t.data_ptr() and conv(t[2:]).value == t.data_ptr() + 8
+    assert conv(torch.nn.Parameter(t)).value == t.data_ptr()
+    given = ctypes.c_void_p(1234)
+    assert conv(given) is given
+    n = ctypes.c_int64(0)
+    for obj in (b'abc', 0, 4096, ctypes.byref(n), (ctypes.c_uint8*4)(), ctypes.pointer(n)):
+        assert repr(conv(obj)) == repr(ctypes.c_void_p.from_param(obj))         # same address, same kind
+    for obj in (1.5, [1, 2], (t,), 'text'.encode, object()):
+        with pytest.raises(TypeError):
+            conv(obj)
+    # through a real call: byref / bytes (the FLAC entry points of data.py) and a tensor as the output buffer
+    frames = ctypes.c_int64(-1)
+    junk = b'not a flac stream' + bytes(64)
+    assert hip.lib().brv_flac_info(junk, len(junk), ctypes.byref(frames), None, None, None) == -10
+    assert hip.lib().brv_flac_decode(junk, len(junk), torch.zeros(8), 4) < 0
+
+
+def test_call_and_query_raise_with_the_librarys_message():
+    with pytest.raises(RuntimeError, match=r'^brv_combine failed with status -1: requires n >= 1$'):
+        hip.call('brv_combine', None, None, None, 0, 1.0, None)
+    t = torch.zeros(4)
+    with pytest.raises(RuntimeError, match=r'^brv_combine failed with status -1: requires n >= 1$'):
+        hip.call('brv_combine', t, t, t, 0, 1.0, hip._c_ptr(0))
+    with pytest.raises(RuntimeError, match=r'^brv_ctn_param_count failed with status -1: null config$'):
+        hip.query('brv_ctn_param_count', None)
+    assert hip.query('brv_stoi_frames', 0) == 0
+    from brever_amd.models import ConvTasNet
+    net = ConvTasNet()
+    assert hip.query('brv_ctn_param_count', ctypes.byref(net.cfg)) == 4_935_217
+    with pytest.raises(AttributeError):
+        hip.call('brv_no_such_entry_point')
+    with pytest.raises(TypeError, match='at least 6 arguments'):
+        hip.call('brv_combine', t, t, t, 4, 1.0)              # an argument short: refused by ctypes, not passed on
+    with pytest.raises(ctypes.ArgumentError):
+        hip.call('brv_combine', t, t, t, 4.5, 1.0, None)      # a float where the header says int64_t
+
+
 def test_layout_queries_match_reference_constants():
     from brever_amd.models import ConvTasNet, count_params
     net = ConvTasNet()

@@ -40,8 +40,8 @@ def main():
     dev = torch.device('cuda', 0)
     lib = hip.lib()
     dt = torch.bfloat16 if lowp else torch.float32
-    rows = lib.brv_cconv_rows_bf16 if lowp else lib.brv_cconv_rows
-    wgrad = lib.brv_cconv_wgrad_bf16 if lowp else lib.brv_cconv_wgrad
+    rows = 'brv_cconv_rows_bf16' if lowp else 'brv_cconv_rows'
+    wgrad = 'brv_cconv_wgrad_bf16' if lowp else 'brv_cconv_wgrad'
 
     def img(*shape):
         if not lowp:
@@ -55,8 +55,8 @@ def main():
         shape = (Bn, M//2 if split else M) + ((2*H, W + 1) if transposed else (H//2, W - 1))
         out = torch.empty(shape, device=dev)
         out2 = torch.empty_like(out) if split else None
-        return timed(lambda: hip.check(rows(hip.ptr(x), hip.ptr(x2), seg, hip.ptr(wp), None, hip.ptr(out), hip.ptr(out2),
-                                            M//4 if split else 0, Bn, C, M, H, W, int(transposed), hip.stream()), 'rows'))
+        return timed(lambda: hip.call(rows, x, x2, seg, wp, None, out, out2, M//4 if split else 0, Bn, C, M, H, W,
+                                      int(transposed), hip.stream()))
 
     def wg(small, small2, big):
         Bn, C, Hb, Wb = big.shape
@@ -65,8 +65,7 @@ def main():
         Hs, Ws = small.shape[2:]
         out = torch.empty(A, 10*C, device=dev)
         ws = torch.empty(lib.brv_cconv_wgrad_workspace_bytes(Bn, A, C, Hs), dtype=torch.uint8, device=dev)
-        return timed(lambda: hip.check(wgrad(hip.ptr(small), hip.ptr(small2), hip.ptr(big), hip.ptr(out), hip.ptr(ws),
-                                             Bn, A, C, Hs, Ws, seg, hip.stream()), 'wgrad'))
+        return timed(lambda: hip.call(wgrad, small, small2, big, out, ws, Bn, A, C, Hs, Ws, seg, hip.stream()))
 
     H, W = 256, 501
     tot = [0.0, 0.0, 0.0]

@@ -26,12 +26,11 @@ def main():
         bias = torch.zeros(co, device=dev)
         y = torch.empty(1, co, H, W, device=dev)
         wp = torch.empty(lib.brv_conv2d_packed_size(co, ci, k), dtype=torch.float16, device=dev)
-        hip.check(lib.brv_conv2d_pack_f16(hip.ptr(w), hip.ptr(wp), co, ci, k, hip.stream()), 'pack')
+        hip.call('brv_conv2d_pack_f16', w, wp, co, ci, k, hip.stream())
 
         def run():
-            hip.check(lib.brv_conv2d_mfma_forward(
-                hip.ptr(x), hip.ptr(wp), hip.ptr(bias), None, None, None, 0, hip.ptr(y), 1, ci, H, W,
-                co, k, ci*H*W, co*H*W, 1.0, hip.stream()), 'conv')
+            hip.call('brv_conv2d_mfma_forward', x, wp, bias, None, None, None, 0, y, 1, ci, H, W, co, k, ci*H*W, co*H*W,
+                     1.0, hip.stream())
         for _ in range(3):
             run()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

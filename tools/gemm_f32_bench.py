@@ -31,7 +31,6 @@ def build(mask):
 def run():
     import torch
     from brever_amd import hip
-    lib = hip.lib()
     dev = torch.device('cuda')
     BT = 16*3999
     #        name                M    N    K    ta tb  bias acc
@@ -47,9 +46,8 @@ def run():
         d = torch.zeros(M, N, device=dev)
         bv = torch.randn(N, device=dev)
         def call():
-            hip.check(lib.brv_gemm_f32(hip.ptr(a), hip.ptr(b), hip.ptr(d), 1, M, N, K, a.shape[1], b.shape[1], N,
-                                       0, 0, 0, ta, tb, 1, 0, 0, hip.ptr(bv) if bias else None,
-                                       2 if bias else acc, hip.stream()), 'brv_gemm_f32')
+            hip.call('brv_gemm_f32', a, b, d, 1, M, N, K, a.shape[1], b.shape[1], N, 0, 0, 0, ta, tb, 1, 0, 0,
+                     bv if bias else None, 2 if bias else acc, hip.stream())
         for _ in range(3):
             call()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

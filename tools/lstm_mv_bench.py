@@ -4,7 +4,6 @@ import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from brever_amd import hip
-lib = hip.lib()
 dev = torch.device('cuda', 0)
 G, B, T, H = 4, 16, 495, 128
 torch.manual_seed(0)
@@ -26,10 +25,8 @@ def timeit(fn, n=10):
 
 
 for suffix in ('_bf16', ''):
-    f = getattr(lib, 'brv_lstm_recurrent_forward' + suffix); b = getattr(lib, 'brv_lstm_recurrent_backward' + suffix)
-    tf = timeit(lambda: hip.check(f(hip.ptr(gates), hip.ptr(w_hh), hip.ptr(bias), hip.ptr(y), hip.ptr(act), hip.ptr(cs),
-                                    G*B, T, H, G, hip.stream()), 'fwd'))
-    tb = timeit(lambda: hip.check(b(hip.ptr(act), hip.ptr(cs), hip.ptr(w_hh), hip.ptr(dy), hip.ptr(dg), G*B, T, H, G,
-                                    hip.stream()), 'bwd'))
+    f, b = 'brv_lstm_recurrent_forward' + suffix, 'brv_lstm_recurrent_backward' + suffix
+    tf = timeit(lambda: hip.call(f, gates, w_hh, bias, y, act, cs, G*B, T, H, G, hip.stream()))
+    tb = timeit(lambda: hip.call(b, act, cs, w_hh, dy, dg, G*B, T, H, G, hip.stream()))
     print(f"{'bf16 MFMA' if suffix else 'fp32     '}: forward {tf:7.1f} us ({tf/T*1e3:5.0f} ns/step)   backward {tb:7.1f} us "
           f"({tb/T*1e3:5.0f} ns/step)")

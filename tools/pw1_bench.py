@@ -15,10 +15,10 @@ for C1, C2, Cout in ((128, 0, 128), (128, 128, 128), (128, 0, 256), (256, 128, 1
     w = torch.randn(Cout, C1 + C2, device=dev)/16
     bias = torch.randn(Cout, device=dev)
     wp = torch.empty(lib.brv_nhwc_conv1x1_packed_size(Cout, C1, C2), dtype=torch.float16, device=dev)
-    hip.check(lib.brv_nhwc_conv1x1_pack(hip.ptr(w), hip.ptr(wp), Cout, C1, C2, hip.stream()), 'pack')
+    hip.call('brv_nhwc_conv1x1_pack', w, wp, Cout, C1, C2, hip.stream())
     y = torch.empty(npx, Cout, dtype=torch.float16, device=dev)
-    run = lambda: hip.check(lib.brv_nhwc_conv1x1_forward(hip.ptr(x1), C1, C1, hip.ptr(x2), C2, C2, hip.ptr(wp), hip.ptr(bias),
-                                                         hip.ptr(y), Cout, npx, Cout, 1.0, hip.stream()), 'fwd')
+    run = lambda: hip.call('brv_nhwc_conv1x1_forward', x1, C1, C1, x2, C2, C2, wp, bias, y, Cout, npx, Cout, 1.0,
+                           hip.stream())
     run(); torch.cuda.synchronize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
