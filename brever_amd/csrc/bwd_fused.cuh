@@ -26,6 +26,7 @@
 // Reference: autograd of brever/models/convtasnet/convtasnet.py:240-260 (Conv1DBlock.forward).
 #pragma once
 #include "tcn_kernels.cuh"
+#include "gfx950.cuh"
 
 namespace brv {
 
@@ -93,7 +94,7 @@ inline void bf_tile_shape(int T, int dil, int P, int& K, int& R) {
 // prefetch included, in front of the first MFMA of every chunk)
 // (The channel count is a multiple of 64 on this path -- hidden_channels = 512 -- so no channel masks.)
 #ifdef BF_STAMP
-#define BF_MARK(i) do { long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); \
+#define BF_MARK(i) do { const long long t_ = stamp_cycles(); \
                         if (threadIdx.x == 0 && fp.dbg) fp.dbg[(long long)blockIdx.x*8 + (i)] = t_; } while (0)
 #else
 #define BF_MARK(i) do { } while (0)
@@ -178,7 +179,7 @@ __global__ __launch_bounds__(256, BF_WPS) void dwconv_bwd_fused_kernel(const Bwd
     if (s0) pv0 = *s0;
     if (tid + 256 < (3 + P)*HL_CG) { const float* s1 = ptab_src(tid + 256); if (s1) pv1 = *s1; }
   }
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // tables visible; LDS only: pv0 / pv1 stay in flight
+  lds_barrier();   // tables visible; LDS only: pv0 / pv1 stay in flight
 
   // z2 rows of phase 1 and z1 rows of phase 2: requested across the phase boundaries in two batches of four
   // rows per thread (the window has at most 256 rows = 8 per thread)

@@ -25,6 +25,7 @@
 #include <type_traits>
 
 #include "common.cuh"
+#include "gfx950.cuh"
 #include "status.h"
 #include "../../include/brever_hip.h"
 
@@ -67,9 +68,8 @@ __device__ __forceinline__ bf16x8 cc_frag(const unsigned char* img, int col0, in
   const int g4 = lane >> 4, i = lane & 15, q = i >> 2, pp = i & 3;
   const int chunk = (col0 >> 3) + 2*(g4 & 1) + (pp >> 1);
   const int row = 8*(g4 >> 1) + q;
-  typedef __attribute__((address_space(3))) s16x4* lds_p;
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(img + cc_off(row, chunk) + 8*(pp & 1)));
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(img + cc_off(row + 4, chunk) + 8*(pp & 1)));
+  const s16x4 lo = lds_read_tr_tracked(img + cc_off(row, chunk) + 8*(pp & 1));
+  const s16x4 hi = lds_read_tr_tracked(img + cc_off(row + 4, chunk) + 8*(pp & 1));
   typedef __attribute__((ext_vector_type(8))) short s16x8;
   const s16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
   return __builtin_bit_cast(bf16x8, v);

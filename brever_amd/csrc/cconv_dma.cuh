@@ -20,8 +20,8 @@
 //     DMA burst: loads return in order, so a weight fragment requested behind a DMA burst would pull that burst's
 //     round trip into the chunk that uses the fragment (the defect of the rotating ring of the register loaders);
 //   * one hand-placed s_waitcnt vmcnt(U (R - 2)) per chunk (U = DMAs per wave and chunk): the image of the NEXT
-//     chunk has landed, the R - 2 younger ones stay in flight; every LDS access of the loop is inline asm (hipcc puts
-//     vmcnt(0) in front of any LDS access it can see while DMAs are pending).
+//     chunk has landed, the R - 2 younger ones stay in flight; every LDS access of the loop is inline asm
+//     (gfx950.cuh, rule 1).
 // What a row's neighbours leak: a row is fetched as 128 (+1) consecutive frames of memory, so frames past the row's
 // end arrive holding the NEXT row's first frames (and frame -1 the previous row's last). In the strided form those
 // columns only feed output frames >= Wout, which are not stored. In the transposed form out[Win] reads in[Win] and
@@ -30,29 +30,6 @@
 // descriptors reach 16 bytes in front of and behind the tensor: a bf16 image handed to these kernels must have 16
 // readable bytes on BOTH sides (brever_hip.h; the Python side allocates its bf16 images that way, `_bf16_empty`).
 #pragma once
-
-namespace dma {
-
-typedef __attribute__((address_space(3))) void* lds_void_p;
-
-__device__ __forceinline__ unsigned int lds_a(const void* p) { return (unsigned int)(unsigned long long)p; }
-
-template <int OFF>
-__device__ __forceinline__ s16x4 read_tr(unsigned int addr) {
-  static_assert(OFF >= 0 && OFF < 65536, "ds offset field");
-  s16x4 v;
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF) : "memory");
-  return v;
-}
-// the fragment halves are valid once at most N younger LDS operations are pending (DS operations return in order)
-template <int N>
-__device__ __forceinline__ void wait_lgkm(s16x4& a, s16x4& b) {
-  asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(a), "+v"(b) : "n"(N) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory"); }
-
-}  // namespace dma
 
 // NTAP weight taps (tap_i) reading NSLOT staged input rows (tap_row): NSLOT = NTAP, or 3 rows for the 5 taps of the
 // pair form (tap t reads slot t >> 1 into accumulator set t & 1, as cconv_tile_lean)
@@ -74,7 +51,7 @@ __device__ __forceinline__ void cconv_tile_dma(const CConvParams& p, unsigned ch
   const int plane = p.Hin*p.Win;
   const bf16_t* in_b = static_cast<const bf16_t*>(p.in) + (long long)b*p.in_bs;
   const bf16_t* in2_b = SEG && p.in_seg > 0 ? static_cast<const bf16_t*>(p.in2) + (long long)b*p.in_bs : nullptr;
-  const unsigned int lds0 = dma::lds_a(lds);
+  const unsigned int lds0 = lds_addr(lds);
 
   // ---- DMA sources. One instruction = 64 lanes x 16 bytes = four 256-byte image rows: wave w stages rows
   // 4 q .. 4 q + 3 (q = w & 3: image q >> 1, channels 4 (q & 1) ..) of tile k = w >> 2 for every tap. Lane l: row
@@ -113,7 +90,7 @@ __device__ __forceinline__ void cconv_tile_dma(const CConvParams& p, unsigned ch
     unsigned char* dst = lds + (cc % R)*BUFB + dk*4096 + dq*1024;
 #pragma unroll
     for (int t = 0; t < NSLOT; ++t)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (dma::lds_void_p)(dst + t*TAPB), 16, (int)voff[t], 0, 0, 0);
+      dma16_buf(rs, dst + t*TAPB, voff[t]);
   };
   // ---- the two frames of the transposed form that must read as zero (shift = -1): in[Win] in the plain image and
   // in[-1] in the shifted one (they arrive holding the neighbouring rows' frames). Lane 4 t + j of a wave patches
@@ -124,16 +101,15 @@ __device__ __forceinline__ void cconv_tile_dma(const CConvParams& p, unsigned ch
     if (lane < 4*NSLOT) {
       const int t = lane >> 2, prow = 4*dq + (lane & 3);
       const unsigned int row = lds0 + (cc % R)*BUFB + t*TAPB + dk*4096 + 256*prow;
-      const unsigned int z = 0;
       if (dimg == 0) {
         if (col_end >= 128*dk && col_end < 128*dk + 128) {
           const int cw = col_end & 127;
           const unsigned int dst = row + 16*((cw >> 3) ^ cc_swz(prow)) + 2*(cw & 7);
-          asm volatile("ds_write_b16 %0, %1" :: "v"(dst), "v"(z) : "memory");
+          lds_write2(dst, 0);
         }
       } else if (f0 == 0 && dk == 0) {
         const unsigned int dst = row + 16*cc_swz(prow);
-        asm volatile("ds_write_b16 %0, %1" :: "v"(dst), "v"(z) : "memory");
+        lds_write2(dst, 0);
       }
     }
   };
@@ -189,9 +165,9 @@ __device__ __forceinline__ void cconv_tile_dma(const CConvParams& p, unsigned ch
   a_burst(0, S0{});
 #pragma unroll
   for (int c = 0; c < R - 1; ++c) burst(c);
-  dma::wait_vm<U*(R - 2)>();
+  wait_vm<U*(R - 2)>();
   patch(0);
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  wait_lgkm<0>();
   __builtin_amdgcn_s_barrier();
 
   auto body = [&](int cc, auto cur_tag, auto nxt_tag) {
@@ -204,8 +180,8 @@ __device__ __forceinline__ void cconv_tile_dma(const CConvParams& p, unsigned ch
       constexpr int slot = decltype(slot_tag)::value, par = decltype(par_tag)::value;
 #pragma unroll
       for (int nf = 0; nf < NF; ++nf) {
-        lo[par][nf] = dma::read_tr<slot*TAPB>(img + fr_lo[nf]);
-        hi[par][nf] = dma::read_tr<slot*TAPB>(img + fr_hi[nf]);
+        lo[par][nf] = lds_read_tr<slot*TAPB>(img + fr_lo[nf]);
+        hi[par][nf] = lds_read_tr<slot*TAPB>(img + fr_hi[nf]);
       }
     };
     auto step = [&](auto t_tag) {
@@ -220,8 +196,8 @@ __device__ __forceinline__ void cconv_tile_dma(const CConvParams& p, unsigned ch
         if constexpr (more) issue(std::integral_constant<int, PAIR ? (tn >> 1) : tn>{}, std::integral_constant<int, par ^ 1>{});
 #pragma unroll
         for (int nf = 0; nf < NF; ++nf) {
-          if constexpr (more) dma::wait_lgkm<2*NF>(lo[par][nf], hi[par][nf]);
-          else dma::wait_lgkm<0>(lo[par][nf], hi[par][nf]);
+          if constexpr (more) wait_lgkm<2*NF>(lo[par][nf], hi[par][nf]);
+          else wait_lgkm<0>(lo[par][nf], hi[par][nf]);
         }
       }
       typedef __attribute__((ext_vector_type(8))) short s16x8;
@@ -244,9 +220,9 @@ __device__ __forceinline__ void cconv_tile_dma(const CConvParams& p, unsigned ch
     if constexpr (NTAP > 4) step(std::integral_constant<int, 4>{});
     // chunk cc + 1 has landed once only the R - 2 younger bursts are pending (the weights of chunk cc + 1 were
     // requested before the youngest burst: landed as well)
-    dma::wait_vm<U*(R - 2)>();
+    wait_vm<U*(R - 2)>();
     patch(cc + 1);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wait_lgkm<0>();
     __builtin_amdgcn_s_barrier();
   };
 #pragma unroll 1
@@ -254,7 +230,7 @@ __device__ __forceinline__ void cconv_tile_dma(const CConvParams& p, unsigned ch
     body(cc, S0{}, S1{});
     if (cc + 1 < p.ncc) body(cc + 1, S1{}, S0{});
   }
-  dma::wait_vm<0>();                               // (the bursts past the end)
+  wait_vm<0>();                               // (the bursts past the end)
 
   // ---- D[m][frame] -> out[b][m][row][frame] (+ bias)
   const int oes = p.out_bf16 ? 2 : 4;        // bytes per output element

@@ -38,7 +38,7 @@ __global__ __launch_bounds__(WG_THREADS) void cconv_wgrad_dma_kernel(const CWgra
   const int pair0 = by*p.pairs_per;
   const int pair1 = pair0 + p.pairs_per < p.npairs ? pair0 + p.pairs_per : p.npairs;
   const int nitems = (pair1 - pair0)*p.nstage;
-  const unsigned int lds0 = dma::lds_a(lds);
+  const unsigned int lds0 = lds_addr(lds);
   constexpr unsigned int kFar = 0x80000000u;
 
   // ---- DMA units of this wave: u = wid + 8 i. Units 0..15: `small` rows 8 u .., 16..31: the same rows shifted,
@@ -100,7 +100,7 @@ __global__ __launch_bounds__(WG_THREADS) void cconv_wgrad_dma_kernel(const CWgra
         if (row < 0 || row >= p.Hb || (last && f + lpiece[i] >= p.Wb)) v = kFar;
       }
       if (!live) v = kFar;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (dma::lds_void_p)dst, 16, (int)v, 0, 0, 0);
+      dma16_buf(rs, dst, v);
     }
   };
   // ---- after a stage has landed: the frames of `small` that must not contribute. Lane l of the wave patches row
@@ -108,7 +108,7 @@ __global__ __launch_bounds__(WG_THREADS) void cconv_wgrad_dma_kernel(const CWgra
   // staged itself).
   // masks the 16-byte piece at `dst` down to its first `keep` elements
   auto keep_first = [&](unsigned int dst, int keep) {
-    u32x4 v;
+    u32x4 v;      // (read + wait as ONE statement: split in two, hipcc schedules the masks' scalar compares between them)
     asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(dst) : "memory");
 #pragma unroll
     for (int d = 0; d < 4; ++d) {
@@ -117,7 +117,7 @@ __global__ __launch_bounds__(WG_THREADS) void cconv_wgrad_dma_kernel(const CWgra
       if (e0 >= keep) w = 0; else if (e0 + 1 >= keep) w &= 0xffffu;
       v[d] = w;
     }
-    asm volatile("ds_write_b128 %0, %1" :: "v"(dst), "v"(v) : "memory");
+    lds_write16(dst, v);
   };
   auto patch = [&](int it) {
     if (it >= nitems) return;
@@ -135,8 +135,7 @@ __global__ __launch_bounds__(WG_THREADS) void cconv_wgrad_dma_kernel(const CWgra
       const int row = 8*(u & 15) + (lane & 7);
       const unsigned int img = st + (u >= 16 ? WG_SMALLB : 0) + 128*row;
       if (u >= 16 && stg == 0) {                 // frame -1 of the row (the previous row's last frame arrived there)
-        const unsigned int dst = img + 16*wg_swz(row), z = 0;
-        asm volatile("ds_write_b16 %0, %1" :: "v"(dst), "v"(z) : "memory");
+        lds_write2(img + 16*wg_swz(row), 0);
       }
       const int lim = p.Ws + (u >= 16 ? 1 : 0) - f;       // first column of the stage that must be zero
       if (stg == p.nstage - 1 && lim > 0 && lim < WG_F && (lim & 7))       // the piece that straddles the end
@@ -152,9 +151,9 @@ __global__ __launch_bounds__(WG_THREADS) void cconv_wgrad_dma_kernel(const CWgra
 
   issue(0);
   issue(1);
-  dma::wait_vm<WD_U>();
+  wait_vm<WD_U>();
   patch(0);
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  wait_lgkm<0>();
   __builtin_amdgcn_s_barrier();
 
   const int m = lane & 31, g = lane >> 5;
@@ -200,14 +199,14 @@ __global__ __launch_bounds__(WG_THREADS) void cconv_wgrad_dma_kernel(const CWgra
     WD_FRAGS(2, af0, bf0) WD_MFMAS(af1, bf1, 6)
     WD_FRAGS(3, af1, bf1) WD_MFMAS(af0, bf0, 6)
     WD_MFMAS(af1, bf1, 0)
-    dma::wait_vm<WD_U>();                           // stage it + 1 has landed; it + 2 stays in flight
+    wait_vm<WD_U>();                           // stage it + 1 has landed; it + 2 stays in flight
     patch(it + 1);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wait_lgkm<0>();
     __builtin_amdgcn_s_barrier();
   }
 #undef WD_FRAGS
 #undef WD_MFMAS
-  dma::wait_vm<0>();
+  wait_vm<0>();
 
   // ---- D[a][c] of tap (i, j) -> part[split][2 i + j][a][c] (as cconv_wgrad_kernel)
   const int c = ctile*WG_C + m;

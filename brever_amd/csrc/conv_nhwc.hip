@@ -23,7 +23,7 @@
 //    workgroup reads the same fragments from LDS instead of each streaming them from L2;
 //  * one raw s_barrier per tap (16 MFMAs per wave); DMAs stay in flight across the barriers
 //    behind counted s_waitcnt vmcnt(N); every LDS access of the loop is inline asm with counted
-//    lgkmcnt waits (hipcc would drain vmcnt(0) before any ds_read it can see);
+//    lgkmcnt waits (gfx950.cuh, rule 1);
 //  * a folded GroupNorm (+SiLU) is applied in LDS: each lane rewrites the slots its own DMAs
 //    filled (ordered by its own vmcnt), spread over the taps of the previous chunk;
 //  * the next tile's first patch and weights are prefetched during the current tile's last
@@ -37,6 +37,7 @@
 
 #include "../../include/brever_hip.h"
 #include "common.cuh"
+#include "gfx950.cuh"
 #include "status.h"
 
 using namespace brv;
@@ -47,8 +48,6 @@ namespace {
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef _Float16 h4 __attribute__((ext_vector_type(4)));
 typedef float f32x8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) void* cn_lds_p;
-typedef __attribute__((address_space(1))) const void* cn_glb_p;
 
 constexpr int CN_WAVES = 8, CN_THREADS = 64*CN_WAVES;
 constexpr int CN_COLS = 32;                   // output columns of a tile (rows: 4*PF)
@@ -97,54 +96,16 @@ __device__ __forceinline__ float cn_silu(float v) {
   return v*__builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-1.4426950408889634f*v));
 }
 
-__device__ __forceinline__ void cn_glds16(const void* g, unsigned char* l) {
-  __builtin_amdgcn_global_load_lds((cn_glb_p)g, (cn_lds_p)l, 16, 0, 0);
-}
-__device__ __forceinline__ unsigned int cn_lds_addr(const void* p) {
-  return (unsigned int)(unsigned long long)p;
-}
-template <int OFF>
-__device__ __forceinline__ u32x4 cn_read16(unsigned int addr) {
-  u32x4 v;
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF) : "memory");
-  return v;
-}
-__device__ __forceinline__ void cn_write16(unsigned int addr, const u32x4& v) {
-  asm volatile("ds_write_b128 %0, %1" :: "v"(addr), "v"(v) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void cn_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory"); }
-// the fragments of one k-step become valid at this wait (whole-vector ties: the compiler must
-// not read a component before it)
+// the fragments of one k-step become valid at this wait (gfx950.cuh, rule 2)
 template <int N>
 __device__ __forceinline__ void cn_wait_frags(u32x4 (&a)[2], u32x4 (&b)[4]) {
-  asm volatile("s_waitcnt lgkmcnt(%6)"
-               : "+v"(a[0]), "+v"(a[1]), "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(b[3])
-               : "n"(N) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void cn_wait5(u32x4& a, u32x4& b, u32x4& c, u32x4& d, u32x4& e) {
-  asm volatile("s_waitcnt lgkmcnt(%5)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e) : "n"(N) : "memory");
-}
-
-template <int N>
-__device__ __forceinline__ void cn_wait_tie2(u32x4& a, u32x4& b) {
-  asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(a), "+v"(b) : "n"(N) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void cn_wait_tie1(u32x4& a) {
-  asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(a) : "n"(N) : "memory");
+  wait_lgkm<N>(a[0], a[1], b[0], b[1], b[2], b[3]);
 }
 
 template <int V> using cn_int = std::integral_constant<int, V>;
 
 #ifdef CN_DIAG
-__device__ __forceinline__ unsigned long long cn_stamp() {
-  unsigned long long t;
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory");
-  return t;
-}
-#define CN_STAMP(i) do { if (diag_on) stamps[TP][i] = cn_stamp(); } while (0)
+#define CN_STAMP(i) do { if (diag_on) stamps[TP][i] = stamp_cycles(); } while (0)
 #else
 #define CN_STAMP(i) do { } while (0)
 #endif
@@ -199,7 +160,7 @@ __global__ __launch_bounds__(CN_THREADS) void conv_nhwc_kernel(const ConvNhwcPar
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);       // wave-uniform: scalar branches
   const int wco = wave >> 2, wpx = wave & 3;
   const int n32 = lane & 31, khalf = lane >> 5;
-  const unsigned int smem_a = cn_lds_addr(smem);
+  const unsigned int smem_a = lds_addr(smem);
 
   // ---- this workgroup's tiles: XCD k (own L2) takes the k-th contiguous eighth of the tiles,
   // a workgroup a contiguous run of them: halo rows / columns are shared in one L2
@@ -271,7 +232,7 @@ __global__ __launch_bounds__(CN_THREADS) void conv_nhwc_kernel(const ConvNhwcPar
     const int c0 = (second ? chunk - p.n_chunks1 : chunk)*CN_CK + (nx_pk[r] & 3)*8;
     const bool ok = nx_pk[r] >= 0 && c0 < cs;
     const void* src = ok ? (const void*)(base + (long long)(nx_pk[r] >> 2)*cs + c0) : (const void*)p.zeros;
-    cn_glds16(src, smem + par*PBYTES + (r*CN_WAVES + wave)*1024);
+    dma16_flat(src, smem + par*PBYTES + (r*CN_WAVES + wave)*1024);
   };
   // the table piece of a chunk, private to the wave (ordered by its own vmcnt): lanes 0-7 the 32
   // scales, 8-15 the 32 shifts of the chunk's channels (FOLD), lanes 16-47 the 128 biases of the
@@ -281,7 +242,7 @@ __global__ __launch_bounds__(CN_THREADS) void conv_nhwc_kernel(const ConvNhwcPar
     if (FOLD == 1 && lane < 16) src = (lane < 8 ? nx_sc : nx_sh) + chunk*CN_CK + (lane & 7)*4;
     if (lane >= 16 && lane < 48 && p.bias && nx_bias_co + (lane - 16)*4 + 4 <= p.Cout)
       src = nx_bias + (lane - 16)*4;
-    cn_glds16(src, smem + OFF_TAB + (par*CN_WAVES + wave)*CN_TAB);
+    dma16_flat(src, smem + OFF_TAB + (par*CN_WAVES + wave)*CN_TAB);
   };
   // rewrite own slot r of the patch with parity par: silu?(scale*x + shift), zero for padding.
   // Split in two so that the arithmetic sits behind the MFMAs of the tap: reads (5 DS
@@ -289,15 +250,15 @@ __global__ __launch_bounds__(CN_THREADS) void conv_nhwc_kernel(const ConvNhwcPar
   struct XfRaw { u32x4 raw, s0, s1, t0, t1; };
   auto transform_reads = [&](int r, int par, int chunk, XfRaw& v) {
     const unsigned int sa = smem_a + par*PBYTES + (r*CN_WAVES + wave)*1024 + lane*16;
-    v.raw = cn_read16<0>(sa);
+    v.raw = lds_read16<0>(sa);
     if (FOLD == 2) {                               // the workgroup's own table: [scale Cin | shift Cin]
       const unsigned int ta = smem_a + OFF_FOLD + (chunk*CN_CK + (nx_pk[r] & 3)*8)*4;
-      v.s0 = cn_read16<0>(ta); v.s1 = cn_read16<16>(ta);
-      v.t0 = cn_read16<CN_MAXC*4>(ta); v.t1 = cn_read16<CN_MAXC*4 + 16>(ta);
+      v.s0 = lds_read16<0>(ta); v.s1 = lds_read16<16>(ta);
+      v.t0 = lds_read16<CN_MAXC*4>(ta); v.t1 = lds_read16<CN_MAXC*4 + 16>(ta);
     } else {                                       // this wave's table piece of the chunk
       const unsigned int ta = smem_a + OFF_TAB + (par*CN_WAVES + wave)*CN_TAB + (nx_pk[r] & 3)*32;
-      v.s0 = cn_read16<0>(ta); v.s1 = cn_read16<16>(ta);
-      v.t0 = cn_read16<128>(ta); v.t1 = cn_read16<144>(ta);
+      v.s0 = lds_read16<0>(ta); v.s1 = lds_read16<16>(ta);
+      v.t0 = lds_read16<128>(ta); v.t1 = lds_read16<144>(ta);
     }
   };
   auto transform_write = [&](int r, int par, const XfRaw& v) {
@@ -320,7 +281,7 @@ __global__ __launch_bounds__(CN_THREADS) void conv_nhwc_kernel(const ConvNhwcPar
       o[j] = ok ? t : 0.f;
     }
     const h8 ov = __builtin_convertvector(o, h8);
-    cn_write16(sa, __builtin_bit_cast(u32x4, ov));
+    lds_write16(sa, __builtin_bit_cast(u32x4, ov));
   };
 
   // ---- weight stream (CN_DA taps ahead): piece `wave` of the tap's 8 KB
@@ -329,7 +290,7 @@ __global__ __launch_bounds__(CN_THREADS) void conv_nhwc_kernel(const ConvNhwcPar
   int a_cob = decode(tile_lo).cob;
   unsigned int a_off = (unsigned int)a_cob*(unsigned int)taps_per_tile*CN_ASLOT;
   auto issue_weights = [&](int slot) {
-    if (!(CN_ABL & 2)) cn_glds16(p.wp + a_off + a_lane, smem + OFF_A + slot*CN_ASLOT + wave*1024);
+    if (!(CN_ABL & 2)) dma16_flat(p.wp + a_off + a_lane, smem + OFF_A + slot*CN_ASLOT + wave*1024);
     a_off += CN_ASLOT;
     if (++a_pos == taps_per_tile) {
       a_pos = 0;
@@ -355,14 +316,14 @@ __global__ __launch_bounds__(CN_THREADS) void conv_nhwc_kernel(const ConvNhwcPar
     constexpr int kh = TAP / KS, kw = TAP % KS;
     if (CN_ABL & 32) return;
     const unsigned int ab = a_rd + slot*CN_ASLOT;
-    a[0] = cn_read16<KSTEP*4096>(ab);
-    a[1] = cn_read16<KSTEP*4096 + 1024>(ab);
+    a[0] = lds_read16<KSTEP*4096>(ab);
+    a[1] = lds_read16<KSTEP*4096 + 1024>(ab);
     const unsigned int bb = (b_col[kw] ^ (KSTEP*32)) + par*PBYTES;
-    b[0] = cn_read16<(0 + kh)*PC*64>(bb);
-    if constexpr (PF > 1) b[1] = cn_read16<(1 + kh)*PC*64>(bb);
+    b[0] = lds_read16<(0 + kh)*PC*64>(bb);
+    if constexpr (PF > 1) b[1] = lds_read16<(1 + kh)*PC*64>(bb);
     if constexpr (PF > 2) {
-      b[2] = cn_read16<(2 + kh)*PC*64>(bb);
-      b[3] = cn_read16<(3 + kh)*PC*64>(bb);
+      b[2] = lds_read16<(2 + kh)*PC*64>(bb);
+      b[3] = lds_read16<(3 + kh)*PC*64>(bb);
     }
   };
 
@@ -407,7 +368,7 @@ __global__ __launch_bounds__(CN_THREADS) void conv_nhwc_kernel(const ConvNhwcPar
     }
 #ifdef CN_DIAG
     unsigned long long es[13]; int esn = 0;
-    es[esn++] = cn_stamp();
+    es[esn++] = stamp_cycles();
 #endif
     const unsigned int stg = smem_a + par*PBYTES;
     int tv = tid;                      // opaque: keeps the epilogue's address arithmetic out of the
@@ -418,8 +379,8 @@ __global__ __launch_bounds__(CN_THREADS) void conv_nhwc_kernel(const ConvNhwcPar
     const int c8 = tv & 15, co = q.cob*128 + c8*8;
     // biases of the tile: this wave's table piece of the chunk just finished
     const unsigned int ba = smem_a + OFF_TAB + (par*CN_WAVES + wave)*CN_TAB + 256 + c8*32;
-    u32x4 b0 = cn_read16<0>(ba), b1 = cn_read16<16>(ba);
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(b0), "+v"(b1) :: "memory");
+    u32x4 b0 = lds_read16<0>(ba), b1 = lds_read16<16>(ba);
+    wait_lgkm<0>(b0, b1);
     float bv[8];
 #pragma unroll
     for (int j = 0; j < 4; ++j) { bv[j] = __uint_as_float(b0[j]); bv[4 + j] = __uint_as_float(b1[j]); }
@@ -445,7 +406,7 @@ __global__ __launch_bounds__(CN_THREADS) void conv_nhwc_kernel(const ConvNhwcPar
         for (int it = 0; it < 4; ++it)
           if (ok[it]) rr[it] = *reinterpret_cast<const u32x4*>(rb + pix[it]*p.Crs + co);
       }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      wait_lgkm<0>();
       __builtin_amdgcn_s_barrier();              // last readers of the buffer / of the previous pass
 #pragma unroll
       for (int cf = 0; cf < 2; ++cf)
@@ -455,21 +416,21 @@ __global__ __launch_bounds__(CN_THREADS) void conv_nhwc_kernel(const ConvNhwcPar
 #pragma unroll
           for (int j = 0; j < 4; ++j) o[j] = (_Float16)acc[cf][pf][g*4 + j];
           const unsigned int a = stg + (wpx*32 + n32)*ESTRIDE + (wco*64 + cf*32 + g*8 + khalf*4)*2;
-          asm volatile("ds_write_b64 %0, %1" :: "v"(a), "v"(o) : "memory");
+          lds_write8(a, o);
         }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      wait_lgkm<0>();
       __builtin_amdgcn_s_barrier();
 #ifdef CN_DIAG
-      es[esn++] = cn_stamp();
+      es[esn++] = stamp_cycles();
 #endif
 #pragma unroll
       for (int it = 0; it < 4; ++it) {
         const int px = (it*CN_THREADS + tv) >> 4;
-        raw[it] = cn_read16<0>(stg + px*ESTRIDE + c8*16);
+        raw[it] = lds_read16<0>(stg + px*ESTRIDE + c8*16);
       }
-      asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(raw[0]), "+v"(raw[1]), "+v"(raw[2]), "+v"(raw[3]) :: "memory");
+      wait_lgkm<0>(raw[0], raw[1], raw[2], raw[3]);
 #ifdef CN_DIAG
-      es[esn++] = cn_stamp();
+      es[esn++] = stamp_cycles();
 #endif
 #pragma unroll
       for (int it = 0; it < 4; ++it) {
@@ -493,7 +454,7 @@ __global__ __launch_bounds__(CN_THREADS) void conv_nhwc_kernel(const ConvNhwcPar
         }
       }
 #ifdef CN_DIAG
-      es[esn++] = cn_stamp();
+      es[esn++] = stamp_cycles();
 #endif
     }
 #ifdef CN_DIAG
@@ -503,7 +464,7 @@ __global__ __launch_bounds__(CN_THREADS) void conv_nhwc_kernel(const ConvNhwcPar
     if (p.stats) {
       // threads tv, tv + 16, ... hold the same 8 channels: [32 threads][16 octets][16 values] in
       // the staging buffer, then one fp64 atomic per (channel, moment) and tile
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      wait_lgkm<0>();
       __builtin_amdgcn_s_barrier();
       const unsigned int sa = stg + ((tv >> 4)*16 + c8)*64;
       u32x4 w0, w1, w2, w3;
@@ -512,8 +473,8 @@ __global__ __launch_bounds__(CN_THREADS) void conv_nhwc_kernel(const ConvNhwcPar
         w0[j] = __float_as_uint(st_s[j]); w1[j] = __float_as_uint(st_s[4 + j]);
         w2[j] = __float_as_uint(st_q[j]); w3[j] = __float_as_uint(st_q[4 + j]);
       }
-      cn_write16(sa, w0); cn_write16(sa + 16, w1); cn_write16(sa + 32, w2); cn_write16(sa + 48, w3);
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      lds_write16(sa, w0); lds_write16(sa + 16, w1); lds_write16(sa + 32, w2); lds_write16(sa + 48, w3);
+      wait_lgkm<0>();
       __builtin_amdgcn_s_barrier();
       if (tv < 256) {
         const int oc = tv >> 4, k = tv & 15;            // octet, value (0-7 sums, 8-15 squares)
@@ -578,17 +539,17 @@ __global__ __launch_bounds__(CN_THREADS) void conv_nhwc_kernel(const ConvNhwcPar
   for (int r = 0; r < ROUNDS; ++r) issue_patch(r, 0, 0);
 #pragma unroll
   for (int d = 0; d < DA; ++d) issue_weights(d);
-  cn_wait_vm<0>();
+  wait_vm<0>();
   if (FOLD && !(CN_ABL & 8)) {
 #pragma unroll
     for (int r = 0; r < ROUNDS; ++r) {
       XfRaw v;
       transform_reads(r, 0, 0, v);
-      cn_wait5<0>(v.raw, v.s0, v.s1, v.t0, v.t1);
+      wait_lgkm<0>(v.raw, v.s0, v.s1, v.t0, v.t1);
       transform_write(r, 0, v);
     }
   }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  wait_lgkm<0>();
   __builtin_amdgcn_s_barrier();
 
   // prefetch position: the chunk after the one being computed
@@ -610,7 +571,7 @@ __global__ __launch_bounds__(CN_THREADS) void conv_nhwc_kernel(const ConvNhwcPar
 #ifdef CN_DIAG
   unsigned long long stamps[9][4];
   bool diag_on = false;
-  const unsigned long long k_t0 = cn_stamp();
+  const unsigned long long k_t0 = stamp_cycles();
   const unsigned long long k_r0 = __builtin_amdgcn_s_memrealtime();
 #endif
   auto tap_body = [&](auto tpc, int par) {
@@ -618,7 +579,7 @@ __global__ __launch_bounds__(CN_THREADS) void conv_nhwc_kernel(const ConvNhwcPar
     CN_STAMP(0);
     // (1) own DMAs of the next tap's weights (and, at tap 8, of the whole next patch) landed;
     //     own fragment reads returned; then everybody's
-    cn_wait_vm<S::top(TP)>();
+    wait_vm<S::top(TP)>();
     CN_STAMP(1);
     cn_wait_frags<0>(fa[0], fb[0]);
     __builtin_amdgcn_s_barrier();
@@ -635,9 +596,9 @@ __global__ __launch_bounds__(CN_THREADS) void conv_nhwc_kernel(const ConvNhwcPar
       if (TP < ROUNDS) issue_patch(TP, nx_chunk, par ^ 1);
       if constexpr (XF) {                      // piece TP-3 of the next patch: own DMA landed
         XfRaw xv;
-        cn_wait_vm<S::piece(TP)>();
+        wait_vm<S::piece(TP)>();
         transform_reads(TP - 3, par ^ 1, nx_chunk, xv);
-        cn_wait5<0>(xv.raw, xv.s0, xv.s1, xv.t0, xv.t1);
+        wait_lgkm<0>(xv.raw, xv.s0, xv.s1, xv.t0, xv.t1);
         transform_write(TP - 3, par ^ 1, xv);
       }
     };
@@ -657,26 +618,26 @@ __global__ __launch_bounds__(CN_THREADS) void conv_nhwc_kernel(const ConvNhwcPar
       const unsigned int ab1 = a_rd + ring*CN_ASLOT, bb1 = (b_col[kw] ^ 32) + par*PBYTES;
       const unsigned int ab0 = a_rd + nring*CN_ASLOT, bb0 = b_col[nkw] + npar*PBYTES;
       // k-step 0 on fa[0] / fb[0]; k-step 1's fragments requested in the order their MFMAs need them
-      one_mfma(0, 0, fa[0][0], fb[0][0]); fa[1][0] = cn_read16<4096>(ab1);
-      one_mfma(1, 0, fa[0][1], fb[0][0]); fb[1][0] = cn_read16<(0 + kh)*PC*64>(bb1);
-      one_mfma(0, 1, fa[0][0], fb[0][1]); fa[1][1] = cn_read16<4096 + 1024>(ab1);
-      one_mfma(1, 1, fa[0][1], fb[0][1]); fb[1][1] = cn_read16<(1 + kh)*PC*64>(bb1);
-      one_mfma(0, 2, fa[0][0], fb[0][2]); fb[1][2] = cn_read16<(2 + kh)*PC*64>(bb1);
-      one_mfma(1, 2, fa[0][1], fb[0][2]); fb[1][3] = cn_read16<(3 + kh)*PC*64>(bb1);
+      one_mfma(0, 0, fa[0][0], fb[0][0]); fa[1][0] = lds_read16<4096>(ab1);
+      one_mfma(1, 0, fa[0][1], fb[0][0]); fb[1][0] = lds_read16<(0 + kh)*PC*64>(bb1);
+      one_mfma(0, 1, fa[0][0], fb[0][1]); fa[1][1] = lds_read16<4096 + 1024>(ab1);
+      one_mfma(1, 1, fa[0][1], fb[0][1]); fb[1][1] = lds_read16<(1 + kh)*PC*64>(bb1);
+      one_mfma(0, 2, fa[0][0], fb[0][2]); fb[1][2] = lds_read16<(2 + kh)*PC*64>(bb1);
+      one_mfma(1, 2, fa[0][1], fb[0][2]); fb[1][3] = lds_read16<(3 + kh)*PC*64>(bb1);
       one_mfma(0, 3, fa[0][0], fb[0][3]);
       one_mfma(1, 3, fa[0][1], fb[0][3]);
       // k-step 1; the next tap's k-step 0 fragments (tap 8: first tap of the next chunk)
-      cn_wait_tie2<4>(fa[1][0], fb[1][0]);
-      one_mfma(0, 0, fa[1][0], fb[1][0]); fa[0][0] = cn_read16<0>(ab0);
-      cn_wait_tie1<4>(fa[1][1]);
-      one_mfma(1, 0, fa[1][1], fb[1][0]); fb[0][0] = cn_read16<(0 + nkh)*PC*64>(bb0);
-      cn_wait_tie1<4>(fb[1][1]);
-      one_mfma(0, 1, fa[1][0], fb[1][1]); fa[0][1] = cn_read16<1024>(ab0);
-      one_mfma(1, 1, fa[1][1], fb[1][1]); fb[0][1] = cn_read16<(1 + nkh)*PC*64>(bb0);
-      cn_wait_tie1<5>(fb[1][2]);
-      one_mfma(0, 2, fa[1][0], fb[1][2]); fb[0][2] = cn_read16<(2 + nkh)*PC*64>(bb0);
-      one_mfma(1, 2, fa[1][1], fb[1][2]); fb[0][3] = cn_read16<(3 + nkh)*PC*64>(bb0);
-      cn_wait_tie1<6>(fb[1][3]);
+      wait_lgkm<4>(fa[1][0], fb[1][0]);
+      one_mfma(0, 0, fa[1][0], fb[1][0]); fa[0][0] = lds_read16<0>(ab0);
+      wait_lgkm<4>(fa[1][1]);
+      one_mfma(1, 0, fa[1][1], fb[1][0]); fb[0][0] = lds_read16<(0 + nkh)*PC*64>(bb0);
+      wait_lgkm<4>(fb[1][1]);
+      one_mfma(0, 1, fa[1][0], fb[1][1]); fa[0][1] = lds_read16<1024>(ab0);
+      one_mfma(1, 1, fa[1][1], fb[1][1]); fb[0][1] = lds_read16<(1 + nkh)*PC*64>(bb0);
+      wait_lgkm<5>(fb[1][2]);
+      one_mfma(0, 2, fa[1][0], fb[1][2]); fb[0][2] = lds_read16<(2 + nkh)*PC*64>(bb0);
+      one_mfma(1, 2, fa[1][1], fb[1][2]); fb[0][3] = lds_read16<(3 + nkh)*PC*64>(bb0);
+      wait_lgkm<6>(fb[1][3]);
       one_mfma(0, 3, fa[1][0], fb[1][3]);
       one_mfma(1, 3, fa[1][1], fb[1][3]);
     };
@@ -742,10 +703,10 @@ __global__ __launch_bounds__(CN_THREADS) void conv_nhwc_kernel(const ConvNhwcPar
       next_tile(cur);
     }
   }
-  cn_wait_vm<0>();
+  wait_vm<0>();
 #ifdef CN_DIAG
   if (blockIdx.x == 0 && tid == 0) {
-    p.dbg[8*9*4] = cn_stamp() - k_t0;
+    p.dbg[8*9*4] = stamp_cycles() - k_t0;
     p.dbg[8*9*4 + 1] = __builtin_amdgcn_s_memrealtime() - k_r0;
   }
 #endif

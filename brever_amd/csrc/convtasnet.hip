@@ -261,8 +261,7 @@ int launch_gemm_rows_t(const GemmRowsParams& p0, int batch, hipStream_t st) {
 // records the 100 MHz real-time counter: slot 0 = end of the kernel before, slot 1 = start
 // of the kernel after a stamped launch (slots 2 / 3 = first entry / last exit inside it)
 __global__ void diag_stamp_kernel(long long* out, int slot) {
-  long long t;
-  asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory");
+  const long long t = stamp_realtime();
   if (threadIdx.x == 0) {
     out[slot] = t;
     if (slot == 0) { out[2] = 0x7fffffffffffffffLL; out[3] = 0; }

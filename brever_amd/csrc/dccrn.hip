@@ -10,6 +10,7 @@
 
 #include "../../include/brever_hip.h"
 #include "common.cuh"
+#include "gfx950.cuh"
 #include "status.h"
 
 using namespace brv;
@@ -386,13 +387,9 @@ __device__ __forceinline__ float fast_sigm(float x) { return __builtin_amdgcn_rc
 __device__ __forceinline__ float fast_tanh(float x) {
   return 2.f*__builtin_amdgcn_rcpf(1.f + __expf(-2.f*x)) - 1.f;
 }
-// Workgroup barrier that orders LDS traffic only. `__syncthreads()` also waits for every outstanding
-// global store and load of the wave (s_waitcnt vmcnt(0)): inside a recurrence that puts one HBM round trip
-// (the step's y / activation stores, the prefetch of the next step's input) into EVERY time step. The
+// The step barrier is lds_barrier (gfx950.cuh), not `__syncthreads()`: inside a recurrence that would put one HBM
+// round trip (the step's y / activation stores, the prefetch of the next step's input) into EVERY time step. The
 // outputs of a step are not read by this kernel again, so only the LDS hand-over needs the barrier.
-__device__ __forceinline__ void lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
 __global__ __launch_bounds__(512) void lstm_fwd_reg_kernel(const float* gates_in, const float* w_hh,
                                                            const float* bias, float* y, float* act,
                                                            float* cs, int T, int H, int per_group) {
@@ -519,26 +516,10 @@ __global__ __launch_bounds__(512) void lstm_bwd_reg_kernel(const float* act, con
 // memory round trip per time step). The loads below are invisible to it; the kernel waits by hand with a
 // counted vmcnt (loads, stores and their order are fixed per step), tied to the registers it releases.
 // Round 6: those loads are plain (compiler-tracked) loads again, and the two kernels DCCRN's use_amp step runs
-// (lstm_fwd_mv_kernel / lstm_bwd_mv_kernel) prefetch through LDS instead (dma_dword below). What went wrong with
-// register destinations the compiler does not know to be in flight: it may COPY such a register (the phi copies of
-// the rotating register sets at the loop's back edge: `v_mov_b32 v135, v136` one step after `global_load_dword
-// v136` was issued, three steps before the counted wait) or park a temporary in it -- correct as long as the
-// load happens to have landed, garbage when HBM is busy (the side stream's weight gradients): one run in three of
-// tests/test_gpu_sizes.py::test_dccrn_default_size_gradients_fp32_and_use_amp had LSTM gradients 10^3 off.
+// (lstm_fwd_mv_kernel / lstm_bwd_mv_kernel) prefetch through LDS instead: dma4_m0, which has no register
+// destination. What went wrong with register destinations the compiler does not know to be in flight, and the rule
+// that came of it: gfx950.cuh, rule 4. The issuing wave waits with a counted vmcnt, other waves read behind a barrier.
 __device__ __forceinline__ float load_untracked(const float* p) { return *p; }
-// Asynchronous global -> LDS copy, one dword per lane (LDS-DMA): lane l of the wave writes LDS byte address
-// `lds_wave_base` (wave-uniform) + 4 l. There is NO register destination, so nothing the compiler does with
-// registers can touch a load in flight; the issuing wave waits with a counted vmcnt, other waves read behind a
-// barrier. Issued as assembly: a DMA the compiler can see makes it drain vmcnt(0) in front of every LDS read.
-// (m0 is reserved for exactly this use; the kernels below contain no other user of it.)
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"
-__device__ __forceinline__ void dma_dword(const float* lane_src, unsigned int lds_wave_base) {
-  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dword %0, off"
-               :: "v"(lane_src), "s"(lds_wave_base) : "memory", "m0");
-}
-#pragma clang diagnostic pop
-__device__ __forceinline__ unsigned int lds_u32(const void* p) { return (unsigned int)(unsigned long long)p; }
 __device__ __forceinline__ float quad_sum(float v) {
   v += __shfl_xor(v, 1, 64);
   v += __shfl_xor(v, 2, 64);
@@ -617,23 +598,23 @@ __global__ __launch_bounds__(512) void lstm_bwd_quad_kernel(const float* act, co
   dg[0][q*GS + u] = 0.f; dg[1][q*GS + u] = 0.f;
   float dc = 0.f;
   // What step t needs of the forward pass -- ig, fg, gg, og, c_t, c_{t-1}, dy_t -- through an LDS ring (round 6: see
-  // dma_dword; the layout and the counts are those of lstm_bwd_mv_kernel). Slot t & 7 = [activations 4 H | c_t | c_{t-1}
+  // dma4_m0; the layout and the counts are those of lstm_bwd_mv_kernel). Slot t & 7 = [activations 4 H | c_t | c_{t-1}
   // | dy_t]; per wave and step two LDS-DMAs kPre = 4 steps ahead, then ONE store. This kernel has ONE barrier per step:
   // the wave's DMAs of step t - 1 (issued at step t + 3; 10 younger operations) land before the barrier ending step t.
   constexpr int kRing = 8, kPre = 4, kSlot = 7*H;
   __shared__ float ring[kRing][kSlot];
   const int wu = __builtin_amdgcn_readfirstlane(j >> 6), lane = j & 63;
-  const unsigned int ring_a = lds_u32(&ring[0][0]) + 256u*(unsigned int)wu;
+  const unsigned int ring_a = lds_addr(&ring[0][0]) + 256u*(unsigned int)wu;
   const int part2 = wu < 6 ? wu >> 1 : 2;                         // 0: c_t, 1: c_{t-1}, 2: dy_t
-  const unsigned int ring_b = lds_u32(&ring[0][0]) + (unsigned int)((4 + part2)*H*4 + 256*(wu & 1));
+  const unsigned int ring_b = lds_addr(&ring[0][0]) + (unsigned int)((4 + part2)*H*4 + 256*(wu & 1));
   const float* src_a = act + (long long)b*T*4*H + 64*wu + lane;
   const float* src_b = (part2 == 2 ? dy : cs) + (long long)b*T*H + 64*(wu & 1) + lane;
   auto issue = [&](int t) {
     const int tt = t > 0 ? t : 0;
     const int tb = part2 == 1 ? (tt > 0 ? tt - 1 : 0) : tt;
     const unsigned int slot = (unsigned int)((t & (kRing - 1))*kSlot*4);
-    dma_dword(src_a + (long long)tt*4*H, ring_a + slot);
-    dma_dword(src_b + (long long)tb*H, ring_b + slot);
+    dma4_m0(src_a + (long long)tt*4*H, ring_a + slot);
+    dma4_m0(src_b + (long long)tb*H, ring_b + slot);
   };
   struct Saved { float ig, fg, gg, og, c, cp, dy; };
   auto step = [&](int t) {
@@ -661,14 +642,14 @@ __global__ __launch_bounds__(512) void lstm_bwd_quad_kernel(const float* act, co
     dg[t & 1][q*GS + u] = dq;
     dgates[((long long)b*T + t)*4*H + q*H + u] = dq;
     dc = dct*fg;
-    asm volatile("s_waitcnt vmcnt(10)" ::: "memory");            // this wave's pieces of step t - 1 are in LDS
+    wait_vm<10>();            // this wave's pieces of step t - 1 are in LDS
     lds_barrier();
   };
   for (int t = T - 1; t > T - 1 - kPre; --t) issue(t);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  wait_vm<0>();
   __syncthreads();
   for (int t = T - 1; t >= 0; --t) step(t);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  wait_vm<0>();
 }
 
 // ---- matrix-pipe layout (H == 128, use_amp): the step's matrix-vector product on the bf16 MFMA -------------------
@@ -712,7 +693,6 @@ __device__ __forceinline__ void lstm_mv_prio(int w) {
 // A fragments straight from LDS: NR 16-byte reads 64 bytes apart and one wait, as inline assembly under the lanes'
 // own branch (written as a select, hipcc turned `take ? *p : 0` into a FLAT load through a pointer that is either
 // the LDS address or a zeroed scratch slot, with a full vmcnt(0) lgkmcnt(0) wait per fragment)
-__device__ __forceinline__ unsigned int lstm_lds_addr(const void* p) { return (unsigned int)(unsigned long long)p; }
 __device__ __forceinline__ void lstm_read4(unsigned int a, u32x4 (&q)[4]) {
   asm volatile("ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:64\n\tds_read_b128 %2, %4 offset:128\n\t"
                "ds_read_b128 %3, %4 offset:192\n\ts_waitcnt lgkmcnt(0)"
@@ -740,7 +720,7 @@ __global__ __launch_bounds__(512) void lstm_fwd_mv_kernel(const float* gates_in,
   for (int g = 0; g < 4; ++g) bq[g] = bias ? bias[g*H + u] : 0.f;
   if (tid < 2*H) (&hb[0][0])[tid] = 0;
   float c = 0.f;
-  // Input rows through an LDS ring (round 6: see dma_dword). Slot t & 7 holds the 4 H gate inputs of step t; wave
+  // Input rows through an LDS ring (round 6: see dma4_m0). Slot t & 7 holds the 4 H gate inputs of step t; wave
   // w copies dwords 64 w .. 64 w + 63 of a row (one LDS-DMA per wave and step), kPre = 4 steps ahead. Per wave and
   // step, in order: 1 DMA, then 1 + 2 HAS_ACT stores. The wave's DMA of step t + 1 (issued at step t - 3) must have
   // landed before the barrier that ends step t: younger than it are the stores of step t - 3 and everything of
@@ -748,10 +728,10 @@ __global__ __launch_bounds__(512) void lstm_fwd_mv_kernel(const float* gates_in,
   constexpr int kRing = 8, kPre = 4, S = HAS_ACT ? 3 : 1;
   __shared__ float ring[kRing][4*H];
   const int wu = __builtin_amdgcn_readfirstlane(w);
-  const unsigned int ring0 = lds_u32(&ring[0][0]) + 256u*(unsigned int)wu;
+  const unsigned int ring0 = lds_addr(&ring[0][0]) + 256u*(unsigned int)wu;
   const float* gi = gates_in + (long long)b*T*4*H + 64*w + lane;
   auto issue = [&](int t) {
-    dma_dword(gi + (long long)(t < T ? t : T - 1)*4*H, ring0 + (unsigned int)((t & (kRing - 1))*4*H*4));
+    dma4_m0(gi + (long long)(t < T ? t : T - 1)*4*H, ring0 + (unsigned int)((t & (kRing - 1))*4*H*4));
   };
   struct In { float g0, g1, g2, g3; };
   auto step = [&](int t) {
@@ -763,7 +743,7 @@ __global__ __launch_bounds__(512) void lstm_fwd_mv_kernel(const float* gates_in,
     if (LSTM_MV_MASK) {
 #pragma unroll
       for (int kq = 0; kq < 4; ++kq) aq[kq] = u32x4{0u, 0u, 0u, 0u};
-      if (take && !(LSTM_MV_ABL & 8)) lstm_read4(lstm_lds_addr(hb[t & 1] + 8*j), aq);
+      if (take && !(LSTM_MV_ABL & 8)) lstm_read4(lds_addr(hb[t & 1] + 8*j), aq);
     } else {
       // every lane reads (rows of A all equal): plain loads, the compiler waits fragment by fragment
 #pragma unroll
@@ -805,14 +785,14 @@ __global__ __launch_bounds__(512) void lstm_fwd_mv_kernel(const float* gates_in,
         act[row*4*H + j*H + u] = j == 0 ? ig : j == 1 ? fg : j == 2 ? gg : og;
       }
     } else if (hn == 123.456f) y[row*H + u] = ig + fg + gg + og;
-    asm volatile("s_waitcnt vmcnt(%0)" :: "n"(S + 3*(1 + S)) : "memory");     // this wave's piece of row t + 1 is in LDS
+    wait_vm<S + 3*(1 + S)>();     // this wave's piece of row t + 1 is in LDS
     if (!(LSTM_MV_ABL & 16)) lds_barrier();
   };
   for (int t = 0; t < kPre; ++t) issue(t);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  wait_vm<0>();
   __syncthreads();
   for (int t = 0; t < T; ++t) step(t);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  wait_vm<0>();
 }
 
 __global__ __launch_bounds__(512) void lstm_bwd_mv_kernel(const float* act, const float* cs, const float* w_hh,
@@ -837,7 +817,7 @@ __global__ __launch_bounds__(512) void lstm_bwd_mv_kernel(const float* act, cons
       wf[nb][ks] = lstm_frag8(w_hh + (long long)(64*w + 32*ks + 8*q)*H + 16*nb + n, H);
   (&dgb[0][0])[tid] = 0; (&dgb[0][0])[tid + 512] = 0;
   float dc = 0.f;
-  // Saved tensors through an LDS ring (round 6: see dma_dword). Slot t & 7 = [activations of step t: 4 H | c_t: H |
+  // Saved tensors through an LDS ring (round 6: see dma4_m0). Slot t & 7 = [activations of step t: 4 H | c_t: H |
   // c_{t-1}: H | dy_t: H]; per wave and step TWO LDS-DMAs, kPre = 4 steps ahead: wave w copies dwords 64 w .. of the
   // activation row, and waves (0, 1) / (2, 3) / (4, 5) the halves of c_t / c_{t-1} / dy_t (waves 6, 7 repeat 4, 5:
   // the same bytes to the same place, so that every wave issues the same number of operations). Per wave and
@@ -847,17 +827,17 @@ __global__ __launch_bounds__(512) void lstm_bwd_mv_kernel(const float* act, cons
   constexpr int kRing = 8, kPre = 4, kSlot = 7*H;
   __shared__ float ring[kRing][kSlot];
   const int wu = __builtin_amdgcn_readfirstlane(w);
-  const unsigned int ring_a = lds_u32(&ring[0][0]) + 256u*(unsigned int)wu;
+  const unsigned int ring_a = lds_addr(&ring[0][0]) + 256u*(unsigned int)wu;
   const int part2 = wu < 6 ? wu >> 1 : 2;                         // 0: c_t, 1: c_{t-1}, 2: dy_t
-  const unsigned int ring_b = lds_u32(&ring[0][0]) + (unsigned int)((4 + part2)*H*4 + 256*(wu & 1));
+  const unsigned int ring_b = lds_addr(&ring[0][0]) + (unsigned int)((4 + part2)*H*4 + 256*(wu & 1));
   const float* src_a = act + (long long)b*T*4*H + 64*w + lane;
   const float* src_b = (part2 == 2 ? dy : cs) + (long long)b*T*H + 64*(w & 1) + lane;
   auto issue = [&](int t) {
     const int tt = t > 0 ? t : 0;
     const int tb = part2 == 1 ? (tt > 0 ? tt - 1 : 0) : tt;
     const unsigned int slot = (unsigned int)((t & (kRing - 1))*kSlot*4);
-    dma_dword(src_a + (long long)tt*4*H, ring_a + slot);
-    dma_dword(src_b + (long long)tb*H, ring_b + slot);
+    dma4_m0(src_a + (long long)tt*4*H, ring_a + slot);
+    dma4_m0(src_b + (long long)tb*H, ring_b + slot);
   };
   struct Saved { float ig, fg, gg, og, c, cp, dy; };
   auto step = [&](int t) {
@@ -892,14 +872,14 @@ __global__ __launch_bounds__(512) void lstm_bwd_mv_kernel(const float* act, cons
     dgb[t & 1][q*H + u] = f2bf(dq);
     dgates[((long long)b*T + t)*4*H + q*H + u] = dq;
     dc = dct*fg;
-    asm volatile("s_waitcnt vmcnt(10)" ::: "memory");            // this wave's pieces of step t - 1 are in LDS
+    wait_vm<10>();            // this wave's pieces of step t - 1 are in LDS
     lds_barrier();
   };
   for (int t = T - 1; t > T - 1 - kPre; --t) issue(t);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  wait_vm<0>();
   __syncthreads();
   for (int t = T - 1; t >= 0; --t) step(t);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  wait_vm<0>();
 }
 
 // out = a - b  /  a + b  (the real / imaginary recombination of ComplexWrapper)

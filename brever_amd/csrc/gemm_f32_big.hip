@@ -30,6 +30,7 @@
 #include <stdint.h>
 
 #include "common.cuh"
+#include "gfx950.cuh"
 #include "status.h"
 #include "gemm_f32_big.h"
 
@@ -72,10 +73,8 @@ __device__ __forceinline__ float4 norm_pro(float4 v, float mean, float rstd, flo
 }
 __device__ __forceinline__ float4 ld4s(const float* p) { return make_float4(p[0], p[1], p[2], p[3]); }
 
-// Barrier of the product kernels: LDS traffic of this wavefront complete, then s_barrier. The barriers
-// here only order LDS stages; __syncthreads() also waits for every global access in flight (vmcnt(0)
-// counts loads AND stores on gfx9), i.e. for the epilogue's stores at every tile end.
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+// Barrier of the product kernels: lds_barrier (gfx950.cuh). The barriers here only order LDS stages;
+// __syncthreads() would also wait for the epilogue's stores at every tile end.
 
 // MFMA fragment from a k-major LDS plane [k][rows] (bf16, row stride ld): lane (r = lane & 31, h = lane >> 5)
 // gets plane[k0 + 8h + j][c0 + r], j = 0 .. 7, through two transposing reads (ds_read_b64_tr_b16: 4 rows x
@@ -85,9 +84,8 @@ typedef __attribute__((ext_vector_type(8))) short big_s16x8;
 __device__ __forceinline__ bf16x8 tr_frag16(const bf16_t* plane, int ld, int k0, int c0, int lane) {
   const int g4 = lane >> 4, i = lane & 15, q = i >> 2, pp = i & 3;
   const bf16_t* p0 = plane + (k0 + 8*(g4 >> 1) + q)*ld + c0 + 16*(g4 & 1) + 4*pp;
-  typedef __attribute__((address_space(3))) s16x4* lds_p;
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(p0));
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(p0 + 4*ld));
+  const s16x4 lo = lds_read_tr_tracked(p0);
+  const s16x4 hi = lds_read_tr_tracked(p0 + 4*ld);
   const big_s16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
   return __builtin_bit_cast(bf16x8, v);
 }

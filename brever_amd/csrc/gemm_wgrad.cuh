@@ -17,6 +17,7 @@
 // nn.ConvTranspose1d layers in brever/models/convtasnet/convtasnet.py.
 #pragma once
 #include "gemm_rows.cuh"
+#include "gfx950.cuh"
 
 namespace brv {
 
@@ -63,9 +64,8 @@ __device__ __forceinline__ bf16x8 tr_frag(const bf16_t* tile, int ld, int row0,
   const int row = row0 + 8*(g4 >> 1) + q;
   const bf16_t* p0 = tile + row*ld + col;
 #ifndef BRV_WGRAD_SCALAR_FRAG
-  typedef __attribute__((address_space(3))) s16x4* lds_p;
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(p0));
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(p0 + 4*ld));
+  const s16x4 lo = lds_read_tr_tracked(p0);
+  const s16x4 hi = lds_read_tr_tracked(p0 + 4*ld);
   const s16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
   return __builtin_bit_cast(bf16x8, v);
 #else

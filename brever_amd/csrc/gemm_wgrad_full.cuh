@@ -20,6 +20,7 @@
 #include <type_traits>
 #include "gemm_wgrad.cuh"
 #include "gemm_ws.cuh"
+#include "gfx950.cuh"
 
 namespace brv {
 
@@ -56,42 +57,9 @@ struct WgradFullParams {
 #endif
 };
 
-typedef __attribute__((address_space(3))) void* lds_void_p;
-
-// 16 bytes per lane, global -> LDS without a VGPR round trip: LDS destination is
-// `dst` (wave-uniform) + lane*16; rows outside the descriptor arrive as zeros.
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t r, unsigned char* dst, unsigned int voff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_void_p)dst, 16, (int)voff, 0, 0, 0);
-}
-
-// Inside the pipelined loop EVERY LDS access is inline asm: hipcc orders each ds_read /
-// ds_write it can see behind all pending LDS-DMA with s_waitcnt vmcnt(0) (it cannot tell
-// the stage being filled from the stage being read), which would drain the two chunks in
-// flight once per chunk. The waits are therefore placed by hand: vmcnt(W2_DMA) retires the
-// older chunk, lgkmcnt(n) the fragment reads (DS operations return in order).
-__device__ __forceinline__ unsigned int lds_addr(const void* p) {
-  return (unsigned int)(unsigned long long)p;            // low 32 bits of a flat LDS address
-}
-__device__ __forceinline__ s16x4 lds_read_tr(unsigned int addr) {
-  s16x4 v;
-  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(v) : "v"(addr) : "memory");
-  return v;
-}
-// the result is valid only after lds_wait16 (whole-vector operands: a per-component tie
-// lets the compiler copy components out BEFORE the wait, i.e. before the data arrived)
-__device__ __forceinline__ u32x4 lds_read16(unsigned int addr) {
-  u32x4 v;
-  asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(addr) : "memory");
-  return v;
-}
-__device__ __forceinline__ void lds_wait16(u32x4& a, u32x4& b) {
-  asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b) :: "memory");
-}
+// Inside the pipelined loop EVERY LDS access is inline asm and the waits are placed by hand (gfx950.cuh, rules
+// 1 - 3): vmcnt(W2_DMA) retires the older chunk, lgkmcnt(n) the fragment reads.
 __device__ __forceinline__ uint4 as_uint4(const u32x4& v) { return make_uint4(v.x, v.y, v.z, v.w); }
-__device__ __forceinline__ void lds_write16(unsigned int addr, const uint4& q) {
-  u32x4 v; v.x = q.x; v.y = q.y; v.z = q.z; v.w = q.w;
-  asm volatile("ds_write_b128 %0, %1" :: "v"(addr), "v"(v) : "memory");
-}
 struct TrAddr { unsigned int a0, a1; };                  // the two 4-row reads of one fragment
 // fragment (frames row0..row0+15, 32 channels from col0) of the swizzled G image: half image
 // = col >> 7, row stride 256 B, 16-byte slot (c ^ ((row & 7) << 1)) -- the 4 rows x 32 B a
@@ -118,10 +86,6 @@ __device__ __forceinline__ TrAddr tr_addr_h(unsigned int img, int row0, int col0
   return t;
 }
 struct Frag { s16x4 lo, hi; };
-template <int N>
-__device__ __forceinline__ void lds_wait16_n(u32x4& a, u32x4& b) {
-  asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(a), "+v"(b) : "n"(N) : "memory");
-}
 __device__ __forceinline__ Frag frag_issue(const TrAddr& t) {
   Frag f; f.lo = lds_read_tr(t.a0); f.hi = lds_read_tr(t.a1); return f;
 }
@@ -129,19 +93,14 @@ __device__ __forceinline__ bf16x8 frag_value(const Frag& f) {
   const s16x8 v = __builtin_shufflevector(f.lo, f.hi, 0, 1, 2, 3, 4, 5, 6, 7);
   return __builtin_bit_cast(bf16x8, v);
 }
-// s_waitcnt lgkmcnt(N) that the four fragments of one k-step depend on
+// s_waitcnt lgkmcnt(N) that the fragments of one k-step depend on
 template <int N>
-__device__ __forceinline__ void frag_wait3(Frag& a, Frag& b, Frag& c) {
-  asm volatile("s_waitcnt lgkmcnt(%6)"
-               : "+v"(a.lo), "+v"(a.hi), "+v"(b.lo), "+v"(b.hi), "+v"(c.lo), "+v"(c.hi)
-               : "n"(N) : "memory");
+__device__ __forceinline__ void frag_wait(Frag& a, Frag& b, Frag& c) {
+  wait_lgkm<N>(a.lo, a.hi, b.lo, b.hi, c.lo, c.hi);
 }
 template <int N>
-__device__ __forceinline__ void frag_wait(Frag& a, Frag& b, Frag& c, Frag& d) {
-  asm volatile("s_waitcnt lgkmcnt(%8)"
-               : "+v"(a.lo), "+v"(a.hi), "+v"(b.lo), "+v"(b.hi), "+v"(c.lo), "+v"(c.hi),
-                 "+v"(d.lo), "+v"(d.hi)
-               : "n"(N) : "memory");
+__device__ __forceinline__ void frag_wait(Frag& a, Frag& b, Frag& c, Frag& d, Frag& e) {
+  wait_lgkm<N>(a.lo, a.hi, b.lo, b.hi, c.lo, c.hi, d.lo, d.hi, e.lo, e.hi);
 }
 
 __global__ __launch_bounds__(64*W2_NW) void wgrad_full_kernel(const WgradFullParams p) {
@@ -218,10 +177,10 @@ __global__ __launch_bounds__(64*W2_NW) void wgrad_full_kernel(const WgradFullPar
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int ld = j < 2 ? p.ldg0 : p.ldg1;
-      dma16(j < 2 ? r0 : r1, gimg + (wid + 8*j)*1024, gvoff[j] + (unsigned int)(t0*ld*2));
+      dma16_buf(j < 2 ? r0 : r1, gimg + (wid + 8*j)*1024, gvoff[j] + (unsigned int)(t0*ld*2));
     }
     unsigned char* himg = smem + W2_OFF_H + st*W2_HBYTES;
-    dma16(rh, himg + wid*1024, (unsigned int)((t0 + hrow)*p.ldh*2 + hch*2));
+    dma16_buf(rh, himg + wid*1024, (unsigned int)((t0 + hrow)*p.ldh*2 + hch*2));
   };
 
   // bias gradient = column sums of G: the workgroups of a block take the chunks in turn;
@@ -263,7 +222,7 @@ __global__ __launch_bounds__(64*W2_NW) void wgrad_full_kernel(const WgradFullPar
 #pragma unroll
     for (int j = 0; j < 4; j += 2) {
       u32x4 ga = lds_read16(gimg + 8*j*1024), gb = lds_read16(gimg + 8*(j + 1)*1024);
-      lds_wait16(ga, gb);
+      wait_lgkm<0>(ga, gb);
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
         float f[8]; unpack8(as_uint4(h ? gb : ga), f);
@@ -276,7 +235,7 @@ __global__ __launch_bounds__(64*W2_NW) void wgrad_full_kernel(const WgradFullPar
   auto transform_chunk = [&](int st, int par, bool bias_turn, int nvalid) {
     u32x4 raw, dummy = {0u, 0u, 0u, 0u}; uint4 packed;
     h_read(st, raw);
-    lds_wait16(raw, dummy);
+    wait_lgkm<0>(raw, dummy);
     h_math(raw, nvalid, packed);
     h_write(par, packed);
     if (bias_turn) bias_pass(st, nvalid);
@@ -298,9 +257,9 @@ __global__ __launch_bounds__(64*W2_NW) void wgrad_full_kernel(const WgradFullPar
   int b2 = b1, t2 = t1;
   issue_chunk(b1, t1, 1, total > 1);
   advance(b2, t2);
-  asm volatile("s_waitcnt vmcnt(%0)" :: "n"(W2_DMA) : "memory");     // chunk 0 landed
+  wait_vm<W2_DMA>();     // chunk 0 landed
   transform_chunk(0, 0, want_bias && htile == 0, T);
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  wait_lgkm<0>();
   __builtin_amdgcn_s_barrier();
 
   // One chunk of the pipeline with COMPILE-TIME stage numbers: with runtime LDS offsets
@@ -334,29 +293,29 @@ __global__ __launch_bounds__(64*W2_NW) void wgrad_full_kernel(const WgradFullPar
       acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ga, h1, acc[1], 0, 0, 0);
     };
     // chunk c+1 (issued one iteration ago): landed once only chunk c+2's DMAs are pending
-    if (dbg & 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(%0)" :: "n"(W2_DMA) : "memory");
+    if (dbg & 1) wait_vm<0>();
+    else wait_vm<W2_DMA>();
     if (t1 == 0 && b1 < b_hi) item_coefs(b1);
     const int nvalid = b1 < b_hi ? T - t1 : 0;
     u32x4 raw, rdummy = {0u, 0u, 0u, 0u}; uint4 packed = make_uint4(0, 0, 0, 0);
     h_read(NX, raw);                                  // oldest in the LDS queue
     if (!(dbg & 2)) {
     issue(0); issue(1);
-    lds_wait16_n<6>(raw, rdummy);                     // <= 6 pending: raw + k-step 0 are back
-    frag_wait3<6>(fa[0], fc[0], fd[0]); mfma(0);
+    wait_lgkm<6>(raw, rdummy);                     // <= 6 pending: raw + k-step 0 are back
+    frag_wait<6>(fa[0], fc[0], fd[0]); mfma(0);
     if (!(dbg & 4)) h_math(raw, nvalid, packed);      // VALU between the MFMAs
     issue(2);
-    frag_wait3<6>(fa[1], fc[1], fd[1]); mfma(1);
+    frag_wait<6>(fa[1], fc[1], fd[1]); mfma(1);
     issue(3);
-    frag_wait3<6>(fa[2], fc[2], fd[2]); mfma(2);
-    frag_wait3<0>(fa[3], fc[3], fd[3]); mfma(3);
+    frag_wait<6>(fa[2], fc[2], fd[2]); mfma(2);
+    frag_wait<0>(fa[3], fc[3], fd[3]); mfma(3);
     } else {
-      lds_wait16_n<0>(raw, rdummy);
+      wait_lgkm<0>(raw, rdummy);
       if (!(dbg & 4)) h_math(raw, nvalid, packed);
     }
     if (!(dbg & 4)) h_write(PAR ^ 1, packed);
     if (want_bias && (c + 1) % p.n_htiles == htile) bias_pass(NX, nvalid);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wait_lgkm<0>();
     __builtin_amdgcn_s_barrier();
     b1 = b2; t1 = t2;
     advance(b2, t2);
@@ -370,7 +329,7 @@ __global__ __launch_bounds__(64*W2_NW) void wgrad_full_kernel(const WgradFullPar
     body(std::integral_constant<int, 4>{}, c + 4);
     body(std::integral_constant<int, 5>{}, c + 5);
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  wait_vm<0>();
 
   // ---- epilogue: this workgroup is the only writer of its tile ---------------------------
   const int fr = lane & 31, fh = lane >> 5;

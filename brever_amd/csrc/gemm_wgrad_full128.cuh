@@ -32,22 +32,6 @@ __device__ __forceinline__ TrAddr tr_addr_h3(unsigned int img, int row0, int col
   t.a1 = t.a0 + 4*W3_LDH*2;
   return t;
 }
-// transposing read with the stage / k-step / column-group part of the address as the instruction's 16-bit immediate:
-// ONE address register per operand and lane instead of one per read (40 of them in a chunk: the kernel spilled)
-template <int OFF>
-__device__ __forceinline__ s16x4 lds_read_tr_o(unsigned int addr) {
-  static_assert(OFF >= 0 && OFF < 65536, "ds offset field");
-  s16x4 v;
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF) : "memory");
-  return v;
-}
-template <int N>
-__device__ __forceinline__ void frag_wait5(Frag& a, Frag& b, Frag& c, Frag& d, Frag& e) {
-  asm volatile("s_waitcnt lgkmcnt(%10)"
-               : "+v"(a.lo), "+v"(a.hi), "+v"(b.lo), "+v"(b.hi), "+v"(c.lo), "+v"(c.hi),
-                 "+v"(d.lo), "+v"(d.hi), "+v"(e.lo), "+v"(e.hi)
-               : "n"(N) : "memory");
-}
 
 __global__ __launch_bounds__(64*W2_NW) void wgrad_full128_kernel(const WgradFullParams p) {
   __shared__ __attribute__((aligned(1024))) unsigned char smem[W3_SMEM];
@@ -118,7 +102,7 @@ __global__ __launch_bounds__(64*W2_NW) void wgrad_full128_kernel(const WgradFull
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int ld = j < 2 ? p.ldg0 : p.ldg1;
-      dma16(j < 2 ? r0 : r1, gimg + (wid + 8*j)*1024, gvoff[j] + (unsigned int)(t0*ld*2));
+      dma16_buf(j < 2 ? r0 : r1, gimg + (wid + 8*j)*1024, gvoff[j] + (unsigned int)(t0*ld*2));
     }
     hr[0] = buf_load16(rh, (unsigned int)((t0 + hrow)*p.ldh*2 + hch*2));
     hr[1] = buf_load16(rh, (unsigned int)((t0 + hrow + 32)*p.ldh*2 + hch*2));
@@ -149,7 +133,7 @@ __global__ __launch_bounds__(64*W2_NW) void wgrad_full128_kernel(const WgradFull
 #pragma unroll
     for (int j = 0; j < 4; j += 2) {
       u32x4 ga = lds_read16(gimg + 8*j*1024), gb = lds_read16(gimg + 8*(j + 1)*1024);
-      lds_wait16(ga, gb);
+      wait_lgkm<0>(ga, gb);
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
         float f[8]; unpack8(as_uint4(h ? gb : ga), f);
@@ -181,14 +165,15 @@ __global__ __launch_bounds__(64*W2_NW) void wgrad_full128_kernel(const WgradFull
     // loads it can see; the asm wait below is for the DMA'd G image, which it cannot)
     uint4 pk0, pk1;
     h_math(hra[0], hrow, T, pk0); h_math(hra[1], hrow + 32, T, pk1);
-    asm volatile("s_waitcnt vmcnt(%0)" :: "n"(W3_VM) : "memory");
+    wait_vm<W3_VM>();
     h_write(0, hrow, pk0); h_write(0, hrow + 32, pk1);
     if (want_bias && htile == 0) bias_pass(0, T);
   }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  wait_lgkm<0>();
   __builtin_amdgcn_s_barrier();
 
-  // lane parts of the fragment addresses (stage, k-step and column group are immediates of the reads)
+  // lane parts of the fragment addresses (stage, k-step and column group are immediates of the reads: ONE address
+  // register per operand and lane instead of one per read -- 40 of them in a chunk: the kernel spilled)
   const TrAddr ga0 = tr_addr_g(smem_a, 0, 32*wid, lane);            // a0 / a1: rows q and q + 4 (own swizzles)
   const unsigned int ha0 = tr_addr_h3(smem_a + W3_OFF_HT, 0, 0, lane).a0;
   const int total6 = ceil_div(total, 6)*6;
@@ -203,7 +188,7 @@ __global__ __launch_bounds__(64*W2_NW) void wgrad_full128_kernel(const WgradFull
     const int nvalid = b1 < b_hi ? T - t1 : 0;
     if (t1 == 0 && b1 < b_hi) item_coefs(b1);
     // chunk c + 1 (G image and H pieces): landed once only chunk c + 2's operations are pending
-    asm volatile("s_waitcnt vmcnt(%0)" :: "n"(W3_VM) : "memory");
+    wait_vm<W3_VM>();
     // (the other parity of the transformed image was last read by the MFMAs of chunk c - 1: free since the barrier)
     {
       uint4 pk;
@@ -215,13 +200,13 @@ __global__ __launch_bounds__(64*W2_NW) void wgrad_full128_kernel(const WgradFull
     const unsigned int g0a = ga0.a0 + ST*W2_GBYTES, g1a = ga0.a1 + ST*W2_GBYTES;
     auto issue = [&](auto s_tag) {
       constexpr int s_ = decltype(s_tag)::value;
-      fa[s_ % W3_SETS].lo = lds_read_tr_o<s_*16*256>(g0a);
-      fa[s_ % W3_SETS].hi = lds_read_tr_o<s_*16*256>(g1a);
+      fa[s_ % W3_SETS].lo = lds_read_tr<s_*16*256>(g0a);
+      fa[s_ % W3_SETS].hi = lds_read_tr<s_*16*256>(g1a);
       constexpr int hb_ = PAR*W3_HT_BYTES + s_*16*W3_LDH*2;
-      fh[s_ % W3_SETS][0].lo = lds_read_tr_o<hb_>(ha0);           fh[s_ % W3_SETS][0].hi = lds_read_tr_o<hb_ + 4*W3_LDH*2>(ha0);
-      fh[s_ % W3_SETS][1].lo = lds_read_tr_o<hb_ + 64>(ha0);      fh[s_ % W3_SETS][1].hi = lds_read_tr_o<hb_ + 64 + 4*W3_LDH*2>(ha0);
-      fh[s_ % W3_SETS][2].lo = lds_read_tr_o<hb_ + 128>(ha0);     fh[s_ % W3_SETS][2].hi = lds_read_tr_o<hb_ + 128 + 4*W3_LDH*2>(ha0);
-      fh[s_ % W3_SETS][3].lo = lds_read_tr_o<hb_ + 192>(ha0);     fh[s_ % W3_SETS][3].hi = lds_read_tr_o<hb_ + 192 + 4*W3_LDH*2>(ha0);
+      fh[s_ % W3_SETS][0].lo = lds_read_tr<hb_>(ha0);           fh[s_ % W3_SETS][0].hi = lds_read_tr<hb_ + 4*W3_LDH*2>(ha0);
+      fh[s_ % W3_SETS][1].lo = lds_read_tr<hb_ + 64>(ha0);      fh[s_ % W3_SETS][1].hi = lds_read_tr<hb_ + 64 + 4*W3_LDH*2>(ha0);
+      fh[s_ % W3_SETS][2].lo = lds_read_tr<hb_ + 128>(ha0);     fh[s_ % W3_SETS][2].hi = lds_read_tr<hb_ + 128 + 4*W3_LDH*2>(ha0);
+      fh[s_ % W3_SETS][3].lo = lds_read_tr<hb_ + 192>(ha0);     fh[s_ % W3_SETS][3].hi = lds_read_tr<hb_ + 192 + 4*W3_LDH*2>(ha0);
     };
     auto mfma = [&](int s) {
       const bf16x8 ga = frag_value(fa[s % W3_SETS]);
@@ -234,14 +219,14 @@ __global__ __launch_bounds__(64*W2_NW) void wgrad_full128_kernel(const WgradFull
     // two k-steps of fragments in registers, 20 reads issued ahead (lgkmcnt counts to 15: the last reads of the second
     // k-step wait at the issue port for the first to return -- a third set would gain nothing)
     issue(I0{}); issue(I1{});
-    frag_wait5<10>(fa[0], fh[0][0], fh[0][1], fh[0][2], fh[0][3]); mfma(0);
+    frag_wait<10>(fa[0], fh[0][0], fh[0][1], fh[0][2], fh[0][3]); mfma(0);
     issue(I2{});
-    frag_wait5<10>(fa[1], fh[1][0], fh[1][1], fh[1][2], fh[1][3]); mfma(1);
+    frag_wait<10>(fa[1], fh[1][0], fh[1][1], fh[1][2], fh[1][3]); mfma(1);
     issue(I3{});
-    frag_wait5<10>(fa[0], fh[0][0], fh[0][1], fh[0][2], fh[0][3]); mfma(2);
-    frag_wait5<0>(fa[1], fh[1][0], fh[1][1], fh[1][2], fh[1][3]); mfma(3);
+    frag_wait<10>(fa[0], fh[0][0], fh[0][1], fh[0][2], fh[0][3]); mfma(2);
+    frag_wait<0>(fa[1], fh[1][0], fh[1][1], fh[1][2], fh[1][3]); mfma(3);
     if (want_bias && (c + 1) % p.n_htiles == htile) bias_pass(NX, nvalid);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wait_lgkm<0>();
     __builtin_amdgcn_s_barrier();
     b1 = b2; t1 = t2;
     advance(b2, t2);
@@ -255,7 +240,7 @@ __global__ __launch_bounds__(64*W2_NW) void wgrad_full128_kernel(const WgradFull
     body(std::integral_constant<int, 4>{}, c + 4);
     body(std::integral_constant<int, 5>{}, c + 5);
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  wait_vm<0>();
 
   // ---- epilogue: this workgroup is the only writer of its tile ---------------------------
   const int fr = lane & 31, fh_ = lane >> 5;

@@ -22,6 +22,7 @@
 #pragma once
 #include "gemm_rows.cuh"
 #include "tcn_kernels.cuh"
+#include "gfx950.cuh"
 
 namespace brv {
 
@@ -77,10 +78,8 @@ __global__ __launch_bounds__(64*NW) void gemm_ws_kernel(const GemmRowsParams p) 
   constexpr int NA = AT == 2 ? 2 : (AT == 3 ? 3 : 1);                // raw chunks per staged chunk
 
 #ifdef BRV_DIAG
-  long long t_entry;
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_entry) :: "memory");
-  long long r_entry;
-  asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(r_entry) :: "memory");
+  const long long t_entry = stamp_cycles();
+  const long long r_entry = stamp_realtime();
 #endif
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int wm = wid / C::WN, wn = wid % C::WN;
@@ -405,11 +404,6 @@ __global__ __launch_bounds__(64*NW) void gemm_ws_kernel(const GemmRowsParams p) 
 
 #ifdef BRV_DIAG
   long long cyc_mfma = 0, cyc_epi = 0, cyc_stage = 0, cyc_total0 = 0;
-  auto stamp = [&]() -> long long {
-    long long t;
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory");
-    return t;
-  };
 #define BRV_STAMP(expr) do { if (dbg & 64) { expr; } } while (0)
 #else
 #define BRV_STAMP(expr) do { } while (0)
@@ -420,7 +414,7 @@ __global__ __launch_bounds__(64*NW) void gemm_ws_kernel(const GemmRowsParams p) 
 #ifdef BRV_DIAG
     long long ts0 = 0, ts1 = 0;
 #endif
-    BRV_STAMP(ts0 = stamp());
+    BRV_STAMP(ts0 = stamp_cycles());
     const long long recs = (dbg & 1) ? 0 : 1;
     // per-item descriptors: frames >= T fall outside and are dropped / read as zero
     const __amdgpu_buffer_rsrc_t rout = make_rsrc(
@@ -480,7 +474,7 @@ __global__ __launch_bounds__(64*NW) void gemm_ws_kernel(const GemmRowsParams p) 
         *reinterpret_cast<float4*>(Cw + fr*C::LDW + 32*f + 8*g + 4*fh) =
             make_float4(acc[f][4*g], acc[f][4*g + 1], acc[f][4*g + 2], acc[f][4*g + 3]);
 
-    BRV_STAMP(ts1 = stamp(); cyc_mfma += ts1 - ts0);
+    BRV_STAMP(ts1 = stamp_cycles(); cyc_mfma += ts1 - ts0);
     if (b != st_item) { flush_stats(); st_item = b; }
     float mrs = 0.f;                                    // -mean*rstd
     float rstd = 1.f;
@@ -568,7 +562,7 @@ __global__ __launch_bounds__(64*NW) void gemm_ws_kernel(const GemmRowsParams p) 
       }
     }
     st_sum += (double)tile_s; st_sq += (double)tile_q;
-    BRV_STAMP(cyc_epi += stamp() - ts1);
+    BRV_STAMP(cyc_epi += stamp_cycles() - ts1);
   };
 
   // ---- main loop: A prefetched one tile ahead behind counted waits; (b, t0) of the
@@ -597,7 +591,7 @@ __global__ __launch_bounds__(64*NW) void gemm_ws_kernel(const GemmRowsParams p) 
       for (int pass = 0; pass < NPASS; ++pass) buf_store16(rnull, kOob - 32u*pass, make_uint4(pass, 0, 0, 0));
     }
     int buf = 0;
-    BRV_STAMP(cyc_total0 = stamp());
+    BRV_STAMP(cyc_total0 = stamp_cycles());
 #if GW_AHEAD == 2
     // two tiles in flight: the loop walks pairs of tiles so that the two register sets alternate statically
     auto one = [&](int tile, uint4 (&ar)[C::ACH*NA]) {
@@ -624,7 +618,7 @@ __global__ __launch_bounds__(64*NW) void gemm_ws_kernel(const GemmRowsParams p) 
 #ifdef BRV_DIAG
       long long tq = 0;
 #endif
-      BRV_STAMP(tq = stamp());
+      BRV_STAMP(tq = stamp_cycles());
       update_affine(b_cur);
       store_tile(b_cur, t_cur, buf, araw);
       __syncthreads();
@@ -632,7 +626,7 @@ __global__ __launch_bounds__(64*NW) void gemm_ws_kernel(const GemmRowsParams p) 
       if (t_nxt >= t_items) { t_nxt = 0; ++b_nxt; }
       const bool more = tile + 1 < t_end;
       load_tile(more ? b_nxt : b_cur, t_nxt, more, araw);
-      BRV_STAMP(cyc_stage += stamp() - tq);
+      BRV_STAMP(cyc_stage += stamp_cycles() - tq);
       process_tile(b_cur, t_cur + 32*wm, buf);
       b_cur = b_nxt; t_cur = t_nxt;
     }
@@ -670,12 +664,11 @@ __global__ __launch_bounds__(64*NW) void gemm_ws_kernel(const GemmRowsParams p) 
   if ((dbg & 64) && p.dbg_out && lane == 0) {
     long long* o = p.dbg_out + ((long long)(blockIdx.y*gridDim.x + blockIdx.x)*NW + wid)*4;
     if (wid == 1) {
-      long long r_exit;
-      asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(r_exit) :: "memory");
-      o[0] = stamp() - t_entry; o[1] = r_exit - r_entry; o[2] = r_entry; o[3] = r_exit;
+      const long long r_exit = stamp_realtime();
+      o[0] = stamp_cycles() - t_entry; o[1] = r_exit - r_entry; o[2] = r_entry; o[3] = r_exit;
     }
     else if (wid == 2) { o[0] = KP; o[1] = gridDim.x; o[2] = EM; o[3] = t_end - t_begin; }
-    else { o[0] = cyc_stage; o[1] = cyc_mfma; o[2] = cyc_epi; o[3] = stamp() - cyc_total0; }
+    else { o[0] = cyc_stage; o[1] = cyc_mfma; o[2] = cyc_epi; o[3] = stamp_cycles() - cyc_total0; }
   }
 #endif
 }

@@ -25,6 +25,7 @@
 
 #include "../../include/brever_hip.h"
 #include "common.cuh"
+#include "gfx950.cuh"
 #include "status.h"
 
 namespace {
@@ -449,7 +450,7 @@ template <> struct Q4Raw<true> { typedef q4_u32x2 type; };
 // Round 6: plain, compiler-tracked loads. Until then these were assembly loads the compiler could not see, waited for
 // by a hand-counted vmcnt three steps later -- but a register the compiler does not know to be in flight may be copied
 // (the rotating register sets need phi copies at the loop's back edge) or reused before the load has landed: see
-// csrc/dccrn.hip `dma_dword`, where the same scheme produced wrong LSTM gradients in one run of three under HBM load.
+// csrc/gfx950.cuh, rule 4, where the same scheme produced wrong LSTM gradients in one run of three under HBM load.
 // The hand-counted waits below stay (they are no-ops behind the compiler's own).
 __device__ __forceinline__ void q4_load(f32x4& v, const float* p, long long i) {
   v = *reinterpret_cast<const f32x4*>(p + i);
@@ -463,7 +464,6 @@ __device__ __forceinline__ f32x4 q4_value(const q4_u32x2& u) {
   return f32x4{__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u),
                __uint_as_float(u.y << 16), __uint_as_float(u.y & 0xffff0000u)};
 }
-__device__ __forceinline__ void q4_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 __device__ __forceinline__ float q4_pick(const f32x4& v, int j) {
   return j == 0 ? v[0] : j == 1 ? v[1] : j == 2 ? v[2] : v[3];
 }
@@ -504,12 +504,10 @@ __global__ __launch_bounds__(512) void lstm_q4_fwd_kernel(const float* __restric
     const int tt = t_first + (t < T ? t : T - 1)*t_inc;
     q4_load(r, gates_in, gbase + (long long)tt*4*LH);
   };
-  // per step: 1 load (step t + 3), then the stores: 3 younger loads may stay in flight
-  auto wait_set = [](Raw& r) { asm volatile("s_waitcnt vmcnt(3)" : "+v"(r) :: "memory"); };
   // A fragment row m = chain m % 4: lane (m = lane & 15, j) reads 16 bytes of chain (lane & 3)
   const int arow = (lane & 3)*HROW + 8*j;
   auto step = [&](Raw& r, int t) {
-    wait_set(r);
+    brv::wait_vm<3>(r);      // per step: 1 load (step t + 3), then the stores: 3 younger loads may stay in flight
     const int tt = t_first + t*t_inc;
     const uint16_t* hp = hb[t & 1] + arow;
     f32x4 acc[4];
@@ -535,11 +533,11 @@ __global__ __launch_bounds__(512) void lstm_q4_fwd_kernel(const float* __restric
         store4(act, st*4*LH + 4*u, f32x4{ig, fg, gg, og}, IO16);
       }
     }
-    q4_barrier();
+    brv::lds_barrier();
   };
   Raw s0, s1, s2, s3;
   fetch(0, s0); fetch(1, s1); fetch(2, s2);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // (the counted wait needs full queues behind it)
+  brv::wait_vm<0>();       // (the counted wait needs full queues behind it)
   __syncthreads();
   int t = 0;
   while (true) {
@@ -548,7 +546,7 @@ __global__ __launch_bounds__(512) void lstm_q4_fwd_kernel(const float* __restric
     fetch(t + 3, s1); step(s2, t); if (++t >= T) break;
     fetch(t + 3, s2); step(s3, t); if (++t >= T) break;
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  brv::wait_vm<0>();
 }
 
 template <bool IO16>
@@ -592,10 +590,6 @@ __global__ __launch_bounds__(512) void lstm_q4_bwd_kernel(const float* __restric
     q4_load1(v.cp, cs, (tc > 0 ? st - 1 : st)*LH + u);
     q4_load1(v.dyv, dyrow, (long long)tt*dy_ld);
   };
-  // per step: 4 loads (step t - 3), then one store: 12 younger loads may stay in flight
-  auto wait_set = [](Saved& v) {
-    asm volatile("s_waitcnt vmcnt(12)" : "+v"(v.a), "+v"(v.cv), "+v"(v.cp), "+v"(v.dyv) :: "memory");
-  };
   const int arow = (lane & 3)*GR + 64*w + 8*j;
   auto step = [&](Saved& cur, int t) {
     // this wave's slice of the gate gradients of step t + 1 (zeros for the last step), all four chains
@@ -613,8 +607,9 @@ __global__ __launch_bounds__(512) void lstm_q4_bwd_kernel(const float* __restric
     const f32x4 e1 = j == 0 ? p[1] : j == 1 ? p[3] : j == 2 ? p[5] : p[7];
 #pragma unroll
     for (int cc = 0; cc < QC; ++cc) { part[w][cc][32*j + n] = e0[cc]; part[w][cc][32*j + 16 + n] = e1[cc]; }
-    q4_barrier();
-    wait_set(cur);
+    brv::lds_barrier();
+    // per step: 4 loads (step t - 3), then one store: 12 younger loads may stay in flight
+    brv::wait_vm<12>(cur.a, cur.cv, cur.cp, cur.dyv);
     const int tt = rev ? T - 1 - t : t;
     float dht = cur.dyv;
 #pragma unroll
@@ -630,11 +625,11 @@ __global__ __launch_bounds__(512) void lstm_q4_bwd_kernel(const float* __restric
     for (int g = 0; g < 4; ++g) gw[g*LH] = brv::f2bf(d[g]);
     if (live) store4(dgates, (chain*T + tt)*4*LH + 4*u, d, IO16);
     dc = dct*fg;
-    q4_barrier();
+    brv::lds_barrier();
   };
   Saved s0, s1, s2, s3;
   fetch(T - 1, s0); fetch(T - 2, s1); fetch(T - 3, s2);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  brv::wait_vm<0>();
   __syncthreads();
   int t = T - 1;
   while (true) {
@@ -643,7 +638,7 @@ __global__ __launch_bounds__(512) void lstm_q4_bwd_kernel(const float* __restric
     fetch(t - 3, s1); step(s2, t); if (--t < 0) break;
     fetch(t - 3, s2); step(s3, t); if (--t < 0) break;
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  brv::wait_vm<0>();
 }
 
 #ifndef BRV_LSTM_Q4

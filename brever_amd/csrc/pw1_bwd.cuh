@@ -15,6 +15,7 @@
 #pragma once
 #include "gemm_rows.cuh"
 #include "gemm_wgrad.cuh"
+#include "gfx950.cuh"
 
 namespace brv {
 
@@ -271,7 +272,7 @@ struct Pw1DgradWsParams {
   long long* dbg;                // -DWSD_STAMP: s_memtime stamps of wave 0 (producer) / 4 (consumer), 64 per workgroup
 };
 #ifdef WSD_STAMP
-#define WSD_MARK(role, idx) do { long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); \
+#define WSD_MARK(role, idx) do { const long long t_ = stamp_cycles(); \
     if (lane == 0 && pp.dbg && (idx) < 32) pp.dbg[(long long)blockIdx.x*64 + (role)*32 + (idx)] = t_; } while (0)
 #else
 #define WSD_MARK(role, idx) do { } while (0)
@@ -362,7 +363,7 @@ __global__ __launch_bounds__(512) void pw1_dgrad_ws_kernel(const Pw1DgradWsParam
 #pragma unroll
       for (int ci = 0; ci < 8; ++ci)               // own image: ordered behind this wave's reads of tile i - 1
         *reinterpret_cast<uint4*>(es + (er + 4*ci)*WSD_LDE + ec*8) = eraw[ci];
-      if (wid == 0) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); WSD_MARK(0, 3 + 3*i); }
+      if (wid == 0) { wait_vm<0>(); WSD_MARK(0, 3 + 3*i); }
       __syncthreads();                             // x image of tile i complete, Ds[buf] free
       if (wid == 0) WSD_MARK(0, 4 + 3*i);
       if (i == n_tiles) break;
@@ -601,19 +602,15 @@ __device__ __forceinline__ bf16x8 rc_tr_frag(const unsigned char* img, int row0,
   const int g4 = lane >> 4, i = lane & 15, q = i >> 2, pp = i & 3;
   const int chunk = (col0 >> 3) + 2*(g4 & 1) + (pp >> 1);
   const int row = row0 + 8*(g4 >> 1) + q;
-  typedef __attribute__((address_space(3))) s16x4* lds_p;
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(img + rc_off(row, chunk) + 8*(pp & 1)));
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(img + rc_off(row + 4, chunk) + 8*(pp & 1)));
+  const s16x4 lo = lds_read_tr_tracked(img + rc_off(row, chunk) + 8*(pp & 1));
+  const s16x4 hi = lds_read_tr_tracked(img + rc_off(row + 4, chunk) + 8*(pp & 1));
   const s16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
   return __builtin_bit_cast(bf16x8, v);
 }
 
 // 4 rows x 16 columns (16-bit) per 16-lane group, delivered column-major (T10): `addr` = byte address of
 // this lane's row / 4-column piece
-__device__ __forceinline__ s16x4 rc_tr4(const unsigned char* addr) {
-  typedef __attribute__((address_space(3))) s16x4* lds_p;
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)addr);
-}
+__device__ __forceinline__ s16x4 rc_tr4(const unsigned char* addr) { return lds_read_tr_tracked(addr); }
 
 // Orientation: z1 is rebuilt as z1[frame][channel] = x W1^T with the frames in the accumulator REGISTERS
 // and the channel on the LANE, so that (a) every per-channel quantity (bias, bias gradient) is per lane,
