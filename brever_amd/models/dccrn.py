@@ -9,7 +9,7 @@ complex LSTM, the mask application, iSTFT) runs in ``libbrever_hip.so``.
 
 Forward and backward are ``torch.autograd.Function`` pieces whose two sides call the HIP
 kernels (``brv_im2col / brv_col2im / brv_complex_weight_pack`` around ``brv_gemm_f32``,
-``brv_batchnorm2d_*``, ``brv_lstm_recurrent_*``, ``brv_gemm_f32``, ``brv_dccrn_apply_mask*``,
+``brv_batchnorm2d_*``, ``brv_lstm_recurrent_*``, ``brv_dccrn_apply_mask*``,
 ``brv_stft_forward`` / ``brv_istft_backward`` and its adjoint); torch only concatenates, slices
 and transposes between them. fp32 activations throughout; ``use_amp`` runs the matrix products (convolutions, LSTM input
 projections) with bf16 operands and fp32 accumulation, otherwise on the exact-fp32 MFMA.
@@ -21,13 +21,9 @@ import torch.nn as nn
 
 from .. import hip
 from ..modules.stft import STFT
+from ._ops import AMP as _AMP, LSTMFunction as _LSTMFunction, LinearFunction, _ParamOnly, amp, col2im, combine, gemm
+from ._ops import gemm_conv, im2col, row_sum
 from .base import BreverBaseModel, ModelRegistry
-
-
-class _ParamOnly(nn.Module):
-    def forward(self, *args, **kwargs):
-        raise RuntimeError('this module only stores parameters; the compute runs in '
-                           'libbrever_hip.so')
 
 
 class ComplexWrapper(_ParamOnly):
@@ -127,39 +123,6 @@ class DCCRNMaskNet(_ParamOnly):
                               num_layers=lstm_layers)
 
 
-_AMP = {'on': False}      # set by DCCRN.loss / _enhance around the forward pass (use_amp)
-
-
-def _gemm(a, b, d, batch, M, N, K, lda, ldb, ldd, a_bs, b_bs, d_bs, trans_a=0, trans_b=0,
-          kbatch=1, a_kbs=0, b_kbs=0, bias=None, lowp=False):
-    """fp32 matrices in HBM; ``lowp``: operands rounded to bf16 inside the kernel, fp32
-    accumulation (``use_amp``), else the exact-fp32 MFMA. A bf16 ``b`` or ``d`` tensor (the
-    column matrices of the use_amp convolutions) selects ``brv_gemm_bf16_mixed``."""
-    flags = int(b.dtype == torch.bfloat16) | int(d.dtype == torch.bfloat16) << 1
-    if flags:
-        assert lowp
-        hip.call('brv_gemm_bf16_mixed', a, b, d, batch, M, N, K, lda, ldb, ldd, a_bs, b_bs, d_bs, trans_a, trans_b,
-                 kbatch, a_kbs, b_kbs, bias, 0, flags, hip.stream())
-        return
-    if not lowp:
-        hip.gemm_f32(a, b, d, batch, M, N, K, lda, ldb, ldd, a_bs, b_bs, d_bs, trans_a, trans_b, kbatch, a_kbs,
-                     b_kbs, bias, 0)
-        return
-    hip.call('brv_gemm_bf16', a, b, d, batch, M, N, K, lda, ldb, ldd, a_bs, b_bs, d_bs, trans_a, trans_b, kbatch, a_kbs,
-             b_kbs, bias, 0, hip.stream())
-
-
-def _gemm_conv(a, img, d, batch, M, N, K, lda, ldd, a_bs, img_bs, d_bs, mode, image, geom, grid,
-               trans_b=0, kbatch=1, a_kbs=0, img_kbs=0, bias=None):
-    """``_gemm(lowp=True)`` whose B operand is the column matrix of ``img`` -- never written out
-    (``brv_gemm_bf16_conv``): ``image`` = (C, H, W) of ``img``, ``grid`` = the pixel grid of the
-    columns; mode 1 = im2col, mode 2 = the gather form of col2im."""
-    (kh, kw), (sh, sw), (ph, pw) = geom
-    hip.call('brv_gemm_bf16_conv', a, img, d, batch, M, N, K, lda, ldd, a_bs, img_bs, d_bs, 0, trans_b, kbatch, a_kbs,
-             img_kbs, bias, 0, mode, image[0], image[1], image[2], kh, kw, sh, sw, ph, pw, grid[0], grid[1],
-             hip.stream())
-
-
 _IMPLICIT = os.environ.get('BRV_DCCRN_IM2COL', '0') != '1'     # use_amp: implicit GEMM convolutions
 _COL_KEEP_BYTES = int(float(os.environ.get('BRV_DCCRN_COL_KEEP_GB', '8'))*2**30)   # per column matrix kept for backward
 
@@ -229,8 +192,6 @@ def _cconv_wgrad(small, big, small2=None):
 # the input depends on them, and the backward pass has a long stretch -- the recurrences' BPTT, 64 chains = a quarter
 # of the CUs for 0.9 ms -- that the decoder's weight gradients fill. BRV_DCCRN_WGRAD_SIDE=0: everything in order.
 _WGRAD_SIDE = os.environ.get('BRV_DCCRN_WGRAD_SIDE', '1') != '0'
-# BRV_LSTM_MV=0: the fp32 recurrence kernels under use_amp too (round 4)
-_LSTM_MV = os.environ.get('BRV_LSTM_MV', '1') != '0'
 _side = {'streams': {}, 'pending': {}}     # both keyed by device index
 
 
@@ -261,30 +222,54 @@ def _side_allowed(params):
     return all(p.grad is None and not getattr(p, '_post_accumulate_grad_hooks', None) for p in params)
 
 
-def _im2col(x, geom, grid, lowp=False):
-    """``lowp``: the column matrix in bf16 (half the bytes of the largest tensor of the layer)."""
-    (kh, kw), (sh, sw), (ph, pw) = geom
-    B, C, H, W = x.shape
-    col = torch.empty(B, C*kh*kw, grid[0]*grid[1], dtype=torch.bfloat16 if lowp else torch.float32,
-                      device=x.device)
-    hip.call('brv_im2col_bf16' if lowp else 'brv_im2col', x, col, B, C, H, W, kh, kw, sh, sw, ph, pw,
-             grid[0], grid[1], hip.stream())
-    return col
+def _grads_on_two_streams(dev, side_ok, data_grad, param_grads, inputs):
+    """``data_grad()`` on the current stream and ``param_grads()`` behind it -- on the side stream if ``side_ok``, which
+    waits for what is queued when this is called (``inputs``, the tensors ``param_grads`` reads, exist by then) but
+    not for the data gradient. The join with the consuming stream is queued once per backward pass (``_join_side``)."""
+    if not side_ok:
+        return data_grad(), param_grads()
+    side = _side_stream(dev)
+    side.wait_stream(torch.cuda.current_stream(dev))
+    dx = data_grad()
+    with torch.cuda.stream(side):
+        grads = param_grads()
+    for t in inputs:
+        if t is not None:
+            t.record_stream(side)
+    if not _side['pending'].get(dev.index):
+        _side['pending'][dev.index] = True
+        torch.autograd.Variable._execution_engine.queue_callback(lambda: _join_side(dev))
+    return dx, grads
 
 
-def _col2im(col, bias, C, image, geom, grid):
-    (kh, kw), (sh, sw), (ph, pw) = geom
-    B = col.shape[0]
-    y = torch.empty(B, C, image[0], image[1], dtype=torch.float32, device=col.device)
-    hip.call('brv_col2im_bf16' if col.dtype == torch.bfloat16 else 'brv_col2im', col, bias, y, B, C,
-             image[0], image[1], kh, kw, sh, sw, ph, pw, grid[0], grid[1], hip.stream())
-    return y
+def _wgrad_columns(a, img, Cw, geom):
+    """Weight-gradient matrix (M, 2 Cw) of a (transposed) convolution: the sum over the batch of a[b] (M, pixels) @
+    col(img[b])^T, the column matrix of ``img`` over the pixel grid of ``a`` read in place (``brv_gemm_bf16_conv``)."""
+    B, C, H, W = img.shape
+    M, Ho, Wo = a.shape[1:]
+    dwc = torch.empty(M, 2*Cw, dtype=torch.float32, device=a.device)
+    gemm_conv(a, img, dwc, 1, M, 2*Cw, Ho*Wo, Ho*Wo, 2*Cw, 0, 0, 0, 1, (C, H, W), geom, (Ho, Wo), trans_b=1, kbatch=B,
+              a_kbs=M*Ho*Wo, img_kbs=C*H*W)
+    return dwc
 
 
-def _combine(a, b, sign):
-    out = torch.empty_like(a)
-    hip.call('brv_combine', a, b, out, a.numel(), float(sign), hip.stream())
-    return out
+def _unpack_param_grads(dwc, wshape, R, Cw, Cout, transpose, sums=None, dy=None):
+    """dwc (2R, 2Cw) -> (d Wr, d Wi); channel sums of dy (``sums``, or taken here) -> (d br, d bi)
+    (bias = [br - bi | br + bi])."""
+    dwr = torch.empty(wshape, dtype=torch.float32, device=dwc.device)
+    dwi = torch.empty_like(dwr)
+    hip.call('brv_complex_weight_unpack', dwc, dwr, dwi, R, Cw, -1.0 if transpose else 1.0, hip.stream())
+    if sums is None:
+        sums = row_sum(dy, dy.shape[0], 2*Cout, dy.shape[2]*dy.shape[3])
+    dbr = torch.empty(Cout, dtype=torch.float32, device=dwc.device)
+    dbi = torch.empty_like(dbr)
+    hip.call('brv_complex_bias_unpack', sums, dbr, dbi, Cout, hip.stream())
+    return dwr, dwi, dbr, dbi
+
+
+def _split_skip_grad(dx, s):
+    """Gradient of the materialised concatenation [x_r, skip_r, x_i, skip_i] (``s`` channels each) -> dx, dskip."""
+    return torch.cat([dx[:, :s], dx[:, 2*s:3*s]], dim=1), torch.cat([dx[:, s:2*s], dx[:, 3*s:]], dim=1)
 
 
 class _ComplexConvFunction(torch.autograd.Function):
@@ -351,23 +336,23 @@ class _ComplexConvFunction(torch.autograd.Function):
             Cout = R
             Ho, Wo = (H + 2*ph - kh)//sh + 1, (W + 2*pw - kw)//sw + 1
             y = torch.empty(B, 2*Cout, Ho, Wo, dtype=torch.float32, device=x.device)
-            _gemm_conv(wc, x, y, B, 2*Cout, Ho*Wo, 2*Cw, 2*Cw, Ho*Wo, 0, 2*Cin*H*W, 2*Cout*Ho*Wo, 1,
-                       (2*Cin, H, W), geom, (Ho, Wo), bias=bias)
+            gemm_conv(wc, x, y, B, 2*Cout, Ho*Wo, 2*Cw, 2*Cw, Ho*Wo, 0, 2*Cin*H*W, 2*Cout*Ho*Wo, 1,
+                      (2*Cin, H, W), geom, (Ho, Wo), bias=bias)
         elif transpose:
             Cout = wr.shape[1]
             Ho, Wo = (H - 1)*sh - 2*ph + kh + oph, (W - 1)*sw - 2*pw + kw + opw
             col = torch.empty(B, 2*Cw, H*W, dtype=torch.bfloat16 if lowp else torch.float32,
                               device=x.device)
-            _gemm(wc, x, col, B, 2*Cw, H*W, 2*Cin, 2*Cw, H*W, H*W, 0, 2*Cin*H*W, 2*Cw*H*W,
-                  trans_a=1, lowp=lowp)
-            y = _col2im(col, bias, 2*Cout, (Ho, Wo), geom, (H, W))
+            gemm(wc, x, col, B, 2*Cw, H*W, 2*Cin, 2*Cw, H*W, H*W, 0, 2*Cin*H*W, 2*Cw*H*W,
+                 trans_a=1, lowp=lowp)
+            y = col2im(col, bias, 2*Cout, (Ho, Wo), geom, (H, W))
         else:
             Cout = R
             Ho, Wo = (H + 2*ph - kh)//sh + 1, (W + 2*pw - kw)//sw + 1
-            col = _im2col(x, geom, (Ho, Wo), lowp)
+            col = im2col(x, geom, (Ho, Wo), lowp)
             y = torch.empty(B, 2*Cout, Ho, Wo, dtype=torch.float32, device=x.device)
-            _gemm(wc, col, y, B, 2*Cout, Ho*Wo, 2*Cw, 2*Cw, Ho*Wo, Ho*Wo, 0, 2*Cw*Ho*Wo,
-                  2*Cout*Ho*Wo, bias=bias, lowp=lowp)
+            gemm(wc, col, y, B, 2*Cout, Ho*Wo, 2*Cw, 2*Cw, Ho*Wo, Ho*Wo, 0, 2*Cw*Ho*Wo,
+                 2*Cout*Ho*Wo, bias=bias, lowp=lowp)
             # kept for the weight gradient (no second im2col in backward; 3 GB over the six encoder layers at
             # 16 x 4 s -- the device has 288), unless one matrix alone is out of proportion
             if any(ctx.needs_input_grad[:5]) and col.numel()*col.element_size() <= _COL_KEEP_BYTES:
@@ -379,19 +364,6 @@ class _ComplexConvFunction(torch.autograd.Function):
         return y
 
     @staticmethod
-    def _unpack_param_grads(dwc, dy, wshape, R, Cw, Cout, B, HoWo, transpose):
-        """dwc (2R, 2Cw) -> (d Wr, d Wi); channel sums of dy -> (d br, d bi) (bias = [br - bi | br + bi])."""
-        dwr = torch.empty(wshape, dtype=torch.float32, device=dy.device)
-        dwi = torch.empty_like(dwr)
-        hip.call('brv_complex_weight_unpack', dwc, dwr, dwi, R, Cw, -1.0 if transpose else 1.0, hip.stream())
-        sums = torch.empty(2*Cout, dtype=torch.float32, device=dy.device)
-        hip.call('brv_row_sum', dy, sums, B, 2*Cout, HoWo, hip.stream())
-        dbr = torch.empty(Cout, dtype=torch.float32, device=dy.device)
-        dbi = torch.empty_like(dbr)
-        hip.call('brv_complex_bias_unpack', sums, dbr, dbi, Cout, hip.stream())
-        return dwr, dwi, dbr, dbi
-
-    @staticmethod
     def backward(ctx, dy):
         x, wc = ctx.saved_tensors[:2]
         skip = ctx.saved_tensors[2] if ctx.two else None
@@ -400,89 +372,67 @@ class _ComplexConvFunction(torch.autograd.Function):
         B = x.shape[0]
         lowp = ctx.lowp
         khw = geom[0][0]*geom[0][1]
-        dwc = None if ctx.rows else torch.empty_like(wc)
         dskip = None
         if ctx.rows:
             def param_grads():
                 """dW (complex pair) and the bias gradients: only dy, x (and skip) go in."""
                 if transpose:
-                    dwc_ = _cconv_wgrad(x, dy, small2=skip)
+                    dwc = _cconv_wgrad(x, dy, small2=skip)
                 elif 2*Cin >= 8:
-                    dwc_ = _cconv_wgrad(dy, x)
+                    dwc = _cconv_wgrad(dy, x)
                 else:        # (2 real input channels of the first encoder: the column-matrix kernel wastes less there)
-                    dwc_ = torch.empty_like(wc)
-                    _gemm_conv(dy, x, dwc_, 1, 2*Cout, 2*Cw, Ho*Wo, Ho*Wo, 2*Cw, 0, 0, 0, 1, (2*Cin, H, W), geom,
-                               (Ho, Wo), trans_b=1, kbatch=B, a_kbs=2*Cout*Ho*Wo, img_kbs=2*Cin*H*W)
-                return _ComplexConvFunction._unpack_param_grads(dwc_, dy, wshape, R, Cw, Cout, B, Ho*Wo, transpose)
-            side = _side_stream(dy.device) if ctx.side_ok else None
-            if side is not None:
-                side.wait_stream(torch.cuda.current_stream(dy.device))      # dy, x exist; dx is not waited for
-            # (ADVICE r4: the input of the first encoder layer -- the spectrogram, built under no_grad -- needs no
-            # gradient: its transposed row convolution at the largest resolution, H = 256, was computed and dropped)
-            need_dx = ctx.needs_input_grad[0] or (ctx.two and ctx.needs_input_grad[7]) or bool(ctx.seg)
-            dx = None
-            if not need_dx:
-                pass
-            elif transpose:
-                dx = _cconv_rows(dy, wc, None, 2*Cin, 2*Cw, khw, 0, split_out=ctx.two, wp=ctx.wp_bwd)
-                if ctx.two:
-                    dx, dskip = dx
-            else:
-                dx = _cconv_rows(dy, wc, None, 2*Cin, khw, 2*Cw, 1, wp=ctx.wp_bwd)
-            if side is None:
-                dwr, dwi, dbr, dbi = param_grads()
-            else:
-                with torch.cuda.stream(side):
-                    dwr, dwi, dbr, dbi = param_grads()
-                for t in (x, dy, skip):
-                    if t is not None:
-                        t.record_stream(side)
-                if not _side['pending'].get(dy.device.index):
-                    _side['pending'][dy.device.index] = True
-                    dev = dy.device
-                    torch.autograd.Variable._execution_engine.queue_callback(lambda: _join_side(dev))
-            if ctx.seg and not ctx.two and dx is not None:      # the concatenation was materialised (segments off the chunk of 8)
-                s = ctx.seg
-                dx, dskip = (torch.cat([dx[:, :s], dx[:, 2*s:3*s]], dim=1),
-                             torch.cat([dx[:, s:2*s], dx[:, 3*s:]], dim=1))
+                    dwc = _wgrad_columns(dy, x, Cw, geom)
+                return _unpack_param_grads(dwc, wshape, R, Cw, Cout, transpose, dy=dy)
+
+            def data_grad():
+                # (ADVICE r4: the input of the first encoder layer -- the spectrogram, built under no_grad -- needs no
+                # gradient: its transposed row convolution at the largest resolution, H = 256, was computed and dropped)
+                if not (ctx.needs_input_grad[0] or (ctx.two and ctx.needs_input_grad[7]) or bool(ctx.seg)):
+                    return None
+                if transpose:
+                    return _cconv_rows(dy, wc, None, 2*Cin, 2*Cw, khw, 0, split_out=ctx.two, wp=ctx.wp_bwd)
+                return _cconv_rows(dy, wc, None, 2*Cin, khw, 2*Cw, 1, wp=ctx.wp_bwd)
+            dx, (dwr, dwi, dbr, dbi) = _grads_on_two_streams(dy.device, ctx.side_ok, data_grad, param_grads,
+                                                             (x, dy, skip))
+            if ctx.two and dx is not None:
+                dx, dskip = dx
+            elif ctx.seg and dx is not None:      # the concatenation was materialised (segments off the chunk of 8)
+                dx, dskip = _split_skip_grad(dx, ctx.seg)
             return dx, dwr, dbr, dwi, dbi, None, None, dskip
         elif transpose and lowp and _IMPLICIT:
             dx = torch.empty_like(x)
-            _gemm_conv(wc, dy, dx, B, 2*Cin, H*W, 2*Cw, 2*Cw, H*W, 0, 2*Cout*Ho*Wo, 2*Cin*H*W, 1,
-                       (2*Cout, Ho, Wo), geom, (H, W))
-            _gemm_conv(x, dy, dwc, 1, 2*Cin, 2*Cw, H*W, H*W, 2*Cw, 0, 0, 0, 1, (2*Cout, Ho, Wo), geom,
-                       (H, W), trans_b=1, kbatch=B, a_kbs=2*Cin*H*W, img_kbs=2*Cout*Ho*Wo)
+            gemm_conv(wc, dy, dx, B, 2*Cin, H*W, 2*Cw, 2*Cw, H*W, 0, 2*Cout*Ho*Wo, 2*Cin*H*W, 1,
+                      (2*Cout, Ho, Wo), geom, (H, W))
+            dwc = _wgrad_columns(x, dy, Cw, geom)
         elif not transpose and lowp and _IMPLICIT:
-            _gemm_conv(dy, x, dwc, 1, 2*Cout, 2*Cw, Ho*Wo, Ho*Wo, 2*Cw, 0, 0, 0, 1, (2*Cin, H, W), geom,
-                       (Ho, Wo), trans_b=1, kbatch=B, a_kbs=2*Cout*Ho*Wo, img_kbs=2*Cin*H*W)
+            dwc = _wgrad_columns(dy, x, Cw, geom)
             # data gradient: product + scatter (the generic gather form doubles the matrix work at
             # stride 2 and shrinks M to 2*Cin: measured 3.8x slower than this pair)
             col = torch.empty(B, 2*Cw, Ho*Wo, dtype=torch.bfloat16, device=x.device)
-            _gemm(wc, dy, col, B, 2*Cw, Ho*Wo, 2*Cout, 2*Cw, Ho*Wo, Ho*Wo, 0, 2*Cout*Ho*Wo,
-                  2*Cw*Ho*Wo, trans_a=1, lowp=lowp)
-            dx = _col2im(col, None, 2*Cin, (H, W), geom, (Ho, Wo))
+            gemm(wc, dy, col, B, 2*Cw, Ho*Wo, 2*Cout, 2*Cw, Ho*Wo, Ho*Wo, 0, 2*Cout*Ho*Wo,
+                 2*Cw*Ho*Wo, trans_a=1, lowp=lowp)
+            dx = col2im(col, None, 2*Cin, (H, W), geom, (Ho, Wo))
         elif transpose:
-            dcol = _im2col(dy, geom, (H, W), lowp)                 # (B, 2*Cw, H*W)
+            dwc = torch.empty_like(wc)
+            dcol = im2col(dy, geom, (H, W), lowp)                 # (B, 2*Cw, H*W)
             dx = torch.empty_like(x)
-            _gemm(wc, dcol, dx, B, 2*Cin, H*W, 2*Cw, 2*Cw, H*W, H*W, 0, 2*Cw*H*W, 2*Cin*H*W,
-                  lowp=lowp)
-            _gemm(x, dcol, dwc, 1, 2*Cin, 2*Cw, H*W, H*W, H*W, 2*Cw, 0, 0, 0, trans_b=1,
-                  kbatch=B, a_kbs=2*Cin*H*W, b_kbs=2*Cw*H*W, lowp=lowp)
+            gemm(wc, dcol, dx, B, 2*Cin, H*W, 2*Cw, 2*Cw, H*W, H*W, 0, 2*Cw*H*W, 2*Cin*H*W,
+                 lowp=lowp)
+            gemm(x, dcol, dwc, 1, 2*Cin, 2*Cw, H*W, H*W, H*W, 2*Cw, trans_b=1,
+                 kbatch=B, a_kbs=2*Cin*H*W, b_kbs=2*Cw*H*W, lowp=lowp)
         else:
+            dwc = torch.empty_like(wc)
             col, ctx.col = ctx.col, None                           # the forward pass's column matrix, if kept
             if col is None:
-                col = _im2col(x, geom, (Ho, Wo), lowp)             # (B, 2*Cw, Ho*Wo)
-            _gemm(dy, col, dwc, 1, 2*Cout, 2*Cw, Ho*Wo, Ho*Wo, Ho*Wo, 2*Cw, 0, 0, 0, trans_b=1,
-                  kbatch=B, a_kbs=2*Cout*Ho*Wo, b_kbs=2*Cw*Ho*Wo, lowp=lowp)
-            _gemm(wc, dy, col, B, 2*Cw, Ho*Wo, 2*Cout, 2*Cw, Ho*Wo, Ho*Wo, 0, 2*Cout*Ho*Wo,
-                  2*Cw*Ho*Wo, trans_a=1, lowp=lowp)                           # the buffer now holds dcol
-            dx = _col2im(col, None, 2*Cin, (H, W), geom, (Ho, Wo))
-        dwr, dwi, dbr, dbi = _ComplexConvFunction._unpack_param_grads(dwc, dy, wshape, R, Cw, Cout, B, Ho*Wo,
-                                                                      transpose)
+                col = im2col(x, geom, (Ho, Wo), lowp)             # (B, 2*Cw, Ho*Wo)
+            gemm(dy, col, dwc, 1, 2*Cout, 2*Cw, Ho*Wo, Ho*Wo, Ho*Wo, 2*Cw, trans_b=1,
+                 kbatch=B, a_kbs=2*Cout*Ho*Wo, b_kbs=2*Cw*Ho*Wo, lowp=lowp)
+            gemm(wc, dy, col, B, 2*Cw, Ho*Wo, 2*Cout, 2*Cw, Ho*Wo, Ho*Wo, 0, 2*Cout*Ho*Wo,
+                 2*Cw*Ho*Wo, trans_a=1, lowp=lowp)                           # the buffer now holds dcol
+            dx = col2im(col, None, 2*Cin, (H, W), geom, (Ho, Wo))
+        dwr, dwi, dbr, dbi = _unpack_param_grads(dwc, wshape, R, Cw, Cout, transpose, dy=dy)
         if ctx.seg and not ctx.two:          # the concatenation was materialised: deal its gradient back
-            s = ctx.seg
-            dx, dskip = (torch.cat([dx[:, :s], dx[:, 2*s:3*s]], dim=1),
-                         torch.cat([dx[:, s:2*s], dx[:, 3*s:]], dim=1))
+            dx, dskip = _split_skip_grad(dx, ctx.seg)
         return dx, dwr, dbr, dwi, dbi, None, None, dskip
 
 
@@ -538,7 +488,7 @@ class _ForkFunction(torch.autograd.Function):
     def backward(ctx, g1, g2):
         if g1 is None or g2 is None:
             return g1 if g2 is None else g2
-        return _combine(g1.contiguous(), g2.contiguous(), 1.0)
+        return combine(g1.contiguous(), g2.contiguous(), 1.0)
 
 
 # nn.BatchNorm2d.num_batches_tracked of the layers a training forward has passed: one multi-tensor add at the end of the
@@ -586,12 +536,7 @@ class _BatchNormActFunction(torch.autograd.Function):
                               for _ in range(3))
         hip.call('brv_batchnorm2d_backward', x, dy, mean, invstd, gamma, beta, slope if has_slope else None, dx, dgamma,
                  dbeta, dsl, B, C, H*W, hip.stream())
-        dslope = None
-        if has_slope:
-            tot = torch.empty(1, dtype=torch.float32, device=x.device)
-            hip.call('brv_row_sum', dsl, tot, 1, 1, C, hip.stream())
-            dslope = tot
-        return dx, dgamma, dbeta, dslope, None, None
+        return dx, dgamma, dbeta, row_sum(dsl, 1, 1, C) if has_slope else None, None, None
 
 
 # use_amp with the row kernels: the activations BETWEEN the layers live in HBM as bf16 -- the tensors the reference's
@@ -663,13 +608,11 @@ class _BlockFunction(torch.autograd.Function):
         ctx.set_materialize_grads(False)
         ctx.side_ok = _side_allowed((wr, br, wi, bi))
         B, C2, H, W = x.shape
-        ctx.x_f32 = None
         first = x16 is None and not transpose and C2 < 8      # the first encoder block: its fp32 image as it is
+        # (its weight gradient runs on the column-matrix kernel, which wants the fp32 image: the saved ``x16`` is it)
+        ctx.small_cin = first and any(ctx.needs_input_grad[4:8])
         if x16 is None:
             x = x.contiguous()
-            # (its weight gradient runs on the column-matrix kernel, which wants the fp32 image too)
-            if first and any(ctx.needs_input_grad[4:8]):
-                ctx.x_f32 = x
             x16 = x if first else _as_bf16(x)
         two = skip is not None
         if two and skip16 is None:
@@ -685,9 +628,9 @@ class _BlockFunction(torch.autograd.Function):
         Ho, Wo = (2*H, W + 1) if transpose else (H//2, W - 1)
         y16 = ctx.y16 = bool(_BF16_Y and norm is not None and out_bf16 and not first)
         y = torch.empty(B, 2*Cout, Ho, Wo, dtype=torch.bfloat16 if y16 else torch.float32, device=dev)
+        assert first or (_has_slack(x16) and (skip16 is None or _has_slack(skip16))), 'bf16 image without slack'
         hip.call('brv_cconv_rows_ex', x16, skip16, seg, wp_fwd, bias, y, None, 0, B, Cin2, 2*Cout, H, W, int(transpose),
                  int(not first), int(y16), hip.stream())
-        assert first or (_has_slack(x16) and (skip16 is None or _has_slack(skip16))), 'bf16 image without slack'
         ctx.dx_bf16 = x.dtype == torch.bfloat16          # (the input is the bf16 token of a block: its gradient is bf16)
         assert not two or skip.dtype == x.dtype
         ctx.cfg = (geom4, transpose, (H, W), (Ho, Wo), Cin2, Cout, R, Cw, wr.shape, seg, two)
@@ -731,14 +674,13 @@ class _BlockFunction(torch.autograd.Function):
         x16, wc = saved[:2]
         skip16 = saved[2] if two else None
         rest = saved[2 + int(two):]
-        khw = geom4[0][0]*geom4[0][1]
         dev = g.device
         g = g.contiguous()
         g2 = g2.contiguous() if g2 is not None else None
         B = x16.shape[0]
-        small_cin = ctx.x_f32 is not None
+        small_cin = ctx.small_cin
         dgamma = dbeta = dslope = None
-        sums = torch.empty(2*Cout, dtype=torch.float32, device=dev)       # channel sums of d(conv output)
+        sums = None                         # channel sums of d(conv output), where the norm's pass produces them
         if ctx.has_norm:
             if not ctx.training:
                 raise NotImplementedError('gradient of eval-mode batch norm is not built on the HIP path')
@@ -747,64 +689,42 @@ class _BlockFunction(torch.autograd.Function):
             dgamma, dbeta, dsl = (torch.empty(2*Cout, dtype=torch.float32, device=dev) for _ in range(3))
             dy = torch.empty_like(y) if small_cin else None
             dy16 = None if small_cin else _bf16_empty(y.shape, dev)
+            if not small_cin:
+                sums = torch.empty(2*Cout, dtype=torch.float32, device=dev)
             assert g2 is None or g2.dtype == g.dtype
             hip.call('brv_batchnorm2d_backward_ex', y, int(ctx.y16), g, g2, int(g.dtype == torch.bfloat16), mean,
                      invstd, gamma, beta, slope, dy if small_cin else dy16, int(not small_cin), dgamma, dbeta, dsl,
-                     None if small_cin else sums, B, 2*Cout, Ho*Wo, hip.stream())
+                     sums, B, 2*Cout, Ho*Wo, hip.stream())
             if ctx.has_slope:
-                dslope = torch.empty(1, dtype=torch.float32, device=dev)
-                hip.call('brv_row_sum', dsl, dslope, 1, 1, 2*Cout, hip.stream())
+                dslope = row_sum(dsl, 1, 1, 2*Cout)
         else:
             dy, dy16 = g, _as_bf16(g)
 
         def param_grads():
             """dW (complex pair) and the bias gradients: only dy, x (and skip) go in."""
             if small_cin:
-                geom = geom4[:3]
-                dwc = torch.empty_like(wc)
-                _gemm_conv(dy, ctx.x_f32, dwc, 1, 2*Cout, 2*Cw, Ho*Wo, Ho*Wo, 2*Cw, 0, 0, 0, 1, (Cin2, H, W), geom,
-                           (Ho, Wo), trans_b=1, kbatch=B, a_kbs=2*Cout*Ho*Wo, img_kbs=Cin2*H*W)
-                return _ComplexConvFunction._unpack_param_grads(dwc, dy, wshape, R, Cw, Cout, B, Ho*Wo, transpose)
-            if transpose:
-                dwc = _cconv_wgrad(x16, dy16, small2=skip16)
-            else:
-                dwc = _cconv_wgrad(dy16, x16)
-            if dy is not None:          # (no norm behind the convolution: the sums of the fp32 gradient)
-                hip.call('brv_row_sum', dy, sums, B, 2*Cout, Ho*Wo, hip.stream())
-            dwr = torch.empty(wshape, dtype=torch.float32, device=dev)
-            dwi = torch.empty_like(dwr)
-            hip.call('brv_complex_weight_unpack', dwc, dwr, dwi, R, Cw, -1.0 if transpose else 1.0, hip.stream())
-            dbr = torch.empty(Cout, dtype=torch.float32, device=dev)
-            dbi = torch.empty_like(dbr)
-            hip.call('brv_complex_bias_unpack', sums, dbr, dbi, Cout, hip.stream())
-            return dwr, dwi, dbr, dbi
+                dwc = _wgrad_columns(dy, x16, Cw, geom4[:3])
+                return _unpack_param_grads(dwc, wshape, R, Cw, Cout, transpose, dy=dy)
+            dwc = _cconv_wgrad(x16, dy16, small2=skip16) if transpose else _cconv_wgrad(dy16, x16)
+            # (no norm behind the convolution: the sums of the fp32 gradient)
+            return _unpack_param_grads(dwc, wshape, R, Cw, Cout, transpose,
+                                       sums=sums if sums is not None else row_sum(dy, B, 2*Cout, Ho*Wo))
 
-        side = _side_stream(dev) if ctx.side_ok else None
-        if side is not None:
-            side.wait_stream(torch.cuda.current_stream(dev))
-        need_dx = ctx.needs_input_grad[0] or (two and ctx.needs_input_grad[2])
-        dx = dskip = None
-        if need_dx:
+        def data_grad():
+            if not (ctx.needs_input_grad[0] or (two and ctx.needs_input_grad[2])):
+                return None, None
             src = dy16 if dy16 is not None else _as_bf16(dy)
             assert _has_slack(src), 'bf16 image without slack'
             M = Cin2
-            shape = (B, M//2 if two else M) + ((H, W))
-            dx = torch.empty(shape, dtype=torch.bfloat16 if ctx.dx_bf16 else torch.float32, device=dev)
+            dx = torch.empty(B, M//2 if two else M, H, W, dtype=torch.bfloat16 if ctx.dx_bf16 else torch.float32,
+                             device=dev)
             dskip = torch.empty_like(dx) if two else None
             # the data gradient of a (transposed) convolution is the other form with the same weights
             hip.call('brv_cconv_rows_ex', src, None, 0, ctx.wp_bwd, None, dx, dskip, M//4 if two else 0, B, 2*Cout, M,
                      Ho, Wo, int(not transpose), 1, int(ctx.dx_bf16), hip.stream())
-        if side is None:
-            dwr, dwi, dbr, dbi = param_grads()
-        else:
-            with torch.cuda.stream(side):
-                dwr, dwi, dbr, dbi = param_grads()
-            for t in (x16, skip16, dy, dy16, sums, ctx.x_f32):
-                if t is not None:
-                    t.record_stream(side)
-            if not _side['pending'].get(dev.index):
-                _side['pending'][dev.index] = True
-                torch.autograd.Variable._execution_engine.queue_callback(lambda: _join_side(dev))
+            return dx, dskip
+        (dx, dskip), (dwr, dwi, dbr, dbi) = _grads_on_two_streams(dev, ctx.side_ok, data_grad, param_grads,
+                                                                  (x16, skip16, dy, dy16, sums))
         return (dx, None, dskip, None, dwr, dbr, dwi, dbi, dgamma, dbeta, dslope, None, None, None, None, None, None)
 
 
@@ -854,11 +774,7 @@ class _CplxAffineFunction(torch.autograd.Function):
         dsl = torch.empty(C, dtype=torch.float32, device=x.device)
         hip.call('brv_cplx_affine_backward', x, dy, A, o, slope if has_slope else None, dx, dA, do, dsl, B, C, H*W,
                  hip.stream())
-        dslope = None
-        if has_slope:
-            dslope = torch.empty(1, dtype=torch.float32, device=x.device)
-            hip.call('brv_row_sum', dsl, dslope, 1, 1, C, hip.stream())
-        return dx, dA, do, dslope
+        return dx, dA, do, row_sum(dsl, 1, 1, C) if has_slope else None
 
 
 def _complex_batch_norm(x, norm, slope):
@@ -893,136 +809,6 @@ def _complex_batch_norm(x, norm, slope):
     return _CplxAffineFunction.apply(x, A, o, slope)
 
 
-class _LSTMFunction(torch.autograd.Function):
-    """G independent single-layer unidirectional nn.LSTMs (batch_first, zero initial state) in
-    one set of launches: x (G, B, T, I) -> hidden states (G, B, T, H), parameters stacked on a
-    leading group axis (w_ih (G, 4H, I), w_hh (G, 4H, H), b_ih / b_hh (G, 4H)). The input
-    projections and their gradients are batched matrix products over G; the recurrence runs
-    all G*B chains concurrently, one workgroup each."""
-
-    TILE_MIN_CHAINS = 256       # below this the one-chain-per-workgroup kernels have more parallelism
-    # use_amp: the tile kernels multiply on the bf16 MFMA (a step of 16 chains = 16 instructions per wave); DCCRN's 64
-    # long chains then run as 4 workgroups
-    TILE_MIN_CHAINS_LOWP = int(os.environ.get('BRV_LSTM_TILE_MIN_LOWP', '256'))
-
-    @staticmethod
-    def _interleave(w, H):
-        """Rows gate*H + unit -> 4*unit + gate (the gate layout of brv_lstm_tile_*)."""
-        G = w.shape[0]
-        return w.view(G, 4, H, *w.shape[2:]).transpose(1, 2).reshape(w.shape).contiguous()
-
-    @staticmethod
-    def _deinterleave(w, H):
-        G = w.shape[0]
-        return w.view(G, H, 4, *w.shape[2:]).transpose(1, 2).reshape(w.shape).contiguous()
-
-    @staticmethod
-    def forward(ctx, x, w_ih, w_hh, b_ih, b_hh):
-        lib = hip.lib()
-        x, w_ih, w_hh = x.contiguous(), w_ih.contiguous(), w_hh.contiguous()
-        G, B, T, I = x.shape
-        # x of shape (1, B, T, I) with several weight sets: ONE input shared by all groups (batch stride 0 in the
-        # products; its gradient is the sum over the groups) -- DCCRN's complex LSTM feeds [real; imag] to both modules
-        shared = ctx.shared = G == 1 and w_hh.shape[0] > 1
-        if shared:
-            G = w_hh.shape[0]
-        H = w_hh.shape[-1]
-        lowp = ctx.lowp = _AMP['on']
-        # many short chains (TF-GridNet): 16 chains per workgroup on the exact-fp32 MFMA, gates
-        # interleaved; few long chains (DCCRN): one workgroup per chain
-        tiled = ctx.tiled = bool(lib.brv_lstm_tile_supported(H)) and \
-            G*B >= (_LSTMFunction.TILE_MIN_CHAINS_LOWP if lowp else _LSTMFunction.TILE_MIN_CHAINS)
-        if tiled:
-            w_ih = _LSTMFunction._interleave(w_ih, H)
-        gates = torch.empty(G, B, T, 4*H, dtype=torch.float32, device=x.device)
-        _gemm(x, w_ih, gates, G, B*T, 4*H, I, I, I, 4*H, 0 if shared else B*T*I, 4*H*I, B*T*4*H, trans_b=1,
-              lowp=lowp)
-        bias = _combine(b_ih.detach().contiguous(), b_hh.detach().contiguous(), 1.0)
-        y = torch.empty(G, B, T, H, dtype=torch.float32, device=x.device)
-        act = torch.empty(G, B, T, 4*H, dtype=torch.float32, device=x.device)
-        cs = torch.empty(G, B, T, H, dtype=torch.float32, device=x.device)
-        # use_amp, few long chains: the step's matrix-vector product on the bf16 MFMA (csrc/dccrn.hip lstm_*_mv_kernel)
-        mv = ctx.mv = bool(lowp and not tiled and _LSTM_MV and lib.brv_lstm_recurrent_bf16_supported(H))
-        name = 'brv_lstm_tile_forward' if tiled else \
-            'brv_lstm_recurrent_forward_bf16' if mv else 'brv_lstm_recurrent_forward'
-        extra = (0, H, B*T*H, int(lowp)) if tiled else ()   # no reversed group, (G, B, T, H) output
-        hip.call(name, gates, w_hh, bias, y, act, cs, G*B, T, H, G, *extra, hip.stream())
-        ctx.save_for_backward(x, w_ih, w_hh, y, act, cs)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        lib = hip.lib()
-        x, w_ih, w_hh, y, act, cs = ctx.saved_tensors          # w_ih interleaved when tiled
-        G, B, T, I = x.shape
-        shared = ctx.shared
-        if shared:
-            G = w_hh.shape[0]
-        H = w_hh.shape[-1]
-        lowp = ctx.lowp
-        dy = dy.contiguous()
-        dg = torch.empty(G, B, T, 4*H, dtype=torch.float32, device=x.device)
-        name = 'brv_lstm_tile_backward' if ctx.tiled else \
-            'brv_lstm_recurrent_backward_bf16' if ctx.mv else 'brv_lstm_recurrent_backward'
-        extra = (0, H, B*T*H, int(lowp)) if ctx.tiled else ()
-        hip.call(name, act, cs, w_hh, dy, dg, G*B, T, H, G, *extra, hip.stream())
-        BT = B*T
-        dx = torch.empty_like(x)                                   # dg (BT, 4H) @ W_ih (4H, I)
-        if shared:                                                 # (summed over the groups: they are the k-batches)
-            _gemm(dg, w_ih, dx, 1, BT, I, 4*H, 4*H, I, I, 0, 0, 0, kbatch=G, a_kbs=BT*4*H, b_kbs=4*H*I, lowp=lowp)
-        else:
-            _gemm(dg, w_ih, dx, G, BT, I, 4*H, 4*H, I, I, BT*4*H, 4*H*I, BT*I, lowp=lowp)
-        dw_ih = torch.empty_like(w_ih)                             # dg^T (4H, BT) @ x (BT, I)
-        _gemm(dg, x, dw_ih, G, 4*H, I, BT, 4*H, I, I, BT*4*H, 0 if shared else BT*I, 4*H*I, trans_a=1, lowp=lowp)
-        # recurrent weight gradient: the gate gradients of frames 1.. against the hidden states of frames 0..T-2 of the
-        # same chain, through shifted views (round 5: a zero-filled shifted copy of y was built per call -- a 16 MB fill
-        # and a 16 MB copy in front of every product; the chains are the k-batches of the product instead)
-        dw_hh = torch.zeros_like(w_hh) if T == 1 else torch.empty_like(w_hh)
-        if T > 1:
-            # (one launch: the groups are the batch, the chains of a group the k-batches)
-            _gemm(dg.view(-1)[4*H:], y, dw_hh, G, 4*H, H, T - 1, 4*H, H, H, B*T*4*H, B*T*H, 4*H*H, trans_a=1,
-                  kbatch=B, a_kbs=T*4*H, b_kbs=T*H, lowp=lowp)
-        # bias gradients: column sums of dg (BT, 4H) per group, in a fixed order (no transposed copy)
-        db = torch.empty(G, 4*H, dtype=torch.float32, device=x.device)
-        scratch = torch.empty(lib.brv_col_sum_scratch_bytes(G, 4*H), dtype=torch.uint8, device=x.device)
-        hip.call('brv_col_sum', dg, db, scratch, G, BT, 4*H, hip.stream())
-        if ctx.tiled:
-            dw_ih, dw_hh, db = (_LSTMFunction._deinterleave(t, H) for t in (dw_ih, dw_hh, db))
-        return dx, dw_ih, dw_hh, db, db.clone()
-
-
-class _LinearLowpFunction(torch.autograd.Function):
-    """``ffnn._LinearFunction`` (nn.Linear on the feature axis of (B, features, frames): LSTMBlock.linear_r / linear_i,
-    dccrn.py:293-311) with the three products on bf16-rounded operands, fp32 accumulation: what torch.autocast makes of
-    nn.Linear; ``use_amp`` only (oracle/dccrn.py: _LSTMBlock._linear emulates it)."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias):
-        B, I, T = x.shape
-        O = weight.shape[0]
-        x = x.contiguous()
-        y = torch.empty(B, O, T, dtype=torch.float32, device=x.device)
-        _gemm(weight, x, y, B, O, T, I, I, T, T, 0, I*T, O*T, bias=bias, lowp=True)
-        ctx.save_for_backward(x, weight)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, weight = ctx.saved_tensors
-        B, I, T = x.shape
-        O = weight.shape[0]
-        dy = dy.contiguous()
-        dx = None
-        if ctx.needs_input_grad[0]:
-            dx = torch.empty_like(x)                       # W^T (I, O) @ dy[b] (O, T)
-            _gemm(weight, dy, dx, B, I, T, O, I, T, T, 0, O*T, I*T, trans_a=1, lowp=True)
-        dw = torch.empty_like(weight)                      # sum_b dy[b] (O, T) @ x[b]^T (T, I)
-        _gemm(dy, x, dw, 1, O, I, T, T, T, I, 0, 0, 0, trans_b=1, kbatch=B, a_kbs=O*T, b_kbs=I*T, lowp=True)
-        db = torch.empty(O, dtype=torch.float32, device=x.device)
-        hip.call('brv_row_sum', dy, db, B, O, T, hip.stream())
-        return dx, dw, db
-
-
 class _ComplexLinearFunction(torch.autograd.Function):
     """LSTMBlock.linear_r / linear_i (dccrn.py:293-311) on the recurrent block's (B, T, H) outputs, written straight into
     the two halves of the (B, 2 F, T) decoder input: the products read their operands transposed in place (no
@@ -1036,7 +822,7 @@ class _ComplexLinearFunction(torch.autograd.Function):
         out = torch.empty(B, 2*F_, T, dtype=torch.float32, device=real.device)
         for k, (x, w, b) in enumerate(((real, wr, br), (imag, wi, bi))):
             # out[b][k F : (k + 1) F] (F x T) = W (F x H) @ x[b]^T (H x T)
-            _gemm(w, x, out[:, k*F_:], B, F_, T, H, H, H, T, 0, T*H, 2*F_*T, trans_b=1, bias=b, lowp=lowp)
+            gemm(w, x, out[:, k*F_:], B, F_, T, H, H, H, T, 0, T*H, 2*F_*T, trans_b=1, bias=b, lowp=lowp)
         ctx.save_for_backward(real, imag, wr, wi)
         ctx.lowp = lowp
         return out
@@ -1052,12 +838,11 @@ class _ComplexLinearFunction(torch.autograd.Function):
         for k, (x, w) in enumerate(((real, wr), (imag, wi))):
             d = dy[:, k*F_:]                                   # (B, F, T) view: rows T apart, items 2 F T apart
             dx = torch.empty_like(x)                           # dx[b] (T x H) = d[b]^T (T x F) @ W (F x H)
-            _gemm(d, w, dx, B, T, H, F_, T, H, H, 2*F_*T, 0, T*H, trans_a=1, lowp=lowp)
+            gemm(d, w, dx, B, T, H, F_, T, H, H, 2*F_*T, 0, T*H, trans_a=1, lowp=lowp)
             dw = torch.empty_like(w)                           # sum_b d[b] (F x T) @ x[b] (T x H)
-            _gemm(d, x, dw, 1, F_, H, T, T, H, H, 0, 0, 0, kbatch=B, a_kbs=2*F_*T, b_kbs=T*H, lowp=lowp)
+            gemm(d, x, dw, 1, F_, H, T, T, H, H, 0, 0, 0, kbatch=B, a_kbs=2*F_*T, b_kbs=T*H, lowp=lowp)
             grads.append((dx, dw))
-        sums = torch.empty(2*F_, dtype=torch.float32, device=dy.device)
-        hip.call('brv_row_sum', dy, sums, B, 2*F_, T, hip.stream())
+        sums = row_sum(dy, B, 2*F_, T)
         return grads[0][0], grads[1][0], grads[0][1], sums[:F_], grads[1][1], sums[F_:], None
 
 
@@ -1143,7 +928,6 @@ class DCCRN(BreverBaseModel):
 
     def _lstm_block(self, x):
         """LSTMBlock (dccrn.py:293-311) on the encoder output (B, 2C, Fq, T) -> same shape."""
-        from .ffnn import _LinearFunction
         blk = self.mask_net.lstm
         B, C2, Fq, T = x.shape
         rows = x.reshape(B, C2*Fq, T).transpose(1, 2)        # (B, T, features): real then imag
@@ -1163,9 +947,9 @@ class DCCRN(BreverBaseModel):
             out = _ComplexLinearFunction.apply(real, imag, blk.linear_r.weight, blk.linear_r.bias, blk.linear_i.weight,
                                                blk.linear_i.bias, bool(_AMP['on'] and _LINEAR_LOWP))
             return out.view(B, C2, Fq, T)
-        linear = _LinearLowpFunction if (_AMP['on'] and _LINEAR_LOWP) else _LinearFunction
-        out_r = linear.apply(real.transpose(1, 2).contiguous(), blk.linear_r.weight, blk.linear_r.bias)
-        out_i = linear.apply(imag.transpose(1, 2).contiguous(), blk.linear_i.weight, blk.linear_i.bias)
+        lowp = bool(_AMP['on'] and _LINEAR_LOWP)
+        out_r = LinearFunction.apply(real.transpose(1, 2).contiguous(), blk.linear_r.weight, blk.linear_r.bias, lowp)
+        out_i = LinearFunction.apply(imag.transpose(1, 2).contiguous(), blk.linear_i.weight, blk.linear_i.bias, lowp)
         return torch.cat([out_r, out_i], dim=1).view(B, C2, Fq, T)
 
     def _blocks_ok(self, x):
@@ -1261,11 +1045,8 @@ class DCCRN(BreverBaseModel):
 
     def loss(self, batch, lengths, use_amp):
         inputs, labels = batch[:, 0], batch[:, 1]
-        _AMP['on'] = bool(use_amp)      # bf16-operand matrix products (the reference autocasts)
-        try:
+        with amp(use_amp):              # bf16-operand matrix products (the reference autocasts)
             outputs = self(inputs)
-        finally:
-            _AMP['on'] = False
         return self.criterion(outputs, labels, lengths).mean()
 
     def gather_grads(self):
@@ -1296,9 +1077,5 @@ class DCCRN(BreverBaseModel):
         return self.stft.frame_length + enc_dec*self.stft.hop_length
 
     def _enhance(self, x, use_amp):
-        _AMP['on'] = bool(use_amp)
-        try:
-            with torch.no_grad():
-                return self.forward(x.mean(axis=-2))
-        finally:
-            _AMP['on'] = False
+        with amp(use_amp), torch.no_grad():
+            return self.forward(x.mean(axis=-2))

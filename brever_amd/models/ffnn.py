@@ -23,46 +23,10 @@ import torch.nn as nn
 from .. import hip
 from ..modules.features import FeatureExtractor
 from ..modules.stft import STFT, MelFilterbank
+from ._ops import LinearFunction
 from .base import BreverBaseModel, ModelRegistry
 
 eps = np.finfo(float).eps        # ffnn.py:12
-
-
-def _gemm(a, b, d, batch, M, N, K, lda, ldb, ldd, a_bs, b_bs, d_bs, trans_a=0, trans_b=0,
-          kbatch=1, a_kbs=0, b_kbs=0, bias=None, accumulate=0):
-    hip.call('brv_gemm_f32', a, b, d, batch, M, N, K, lda, ldb, ldd, a_bs, b_bs, d_bs, trans_a, trans_b, kbatch, a_kbs,
-             b_kbs, bias, accumulate, hip.stream())
-
-
-class _LinearFunction(torch.autograd.Function):
-    """y[b] (O, T) = W (O, I) @ x[b] (I, T) + bias[:, None]: nn.Linear on the feature axis
-    of a (B, features, frames) tensor without the two transposes of ffnn.py:167-171."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias):
-        B, I, T = x.shape
-        O = weight.shape[0]
-        x = x.contiguous()
-        y = torch.empty(B, O, T, dtype=torch.float32, device=x.device)
-        _gemm(weight, x, y, B, O, T, I, I, T, T, 0, I*T, O*T, bias=bias)
-        ctx.save_for_backward(x, weight)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, weight = ctx.saved_tensors
-        B, I, T = x.shape
-        O = weight.shape[0]
-        dy = dy.contiguous()
-        dx = None
-        if ctx.needs_input_grad[0]:
-            dx = torch.empty_like(x)                       # W^T (I, O) @ dy[b] (O, T)
-            _gemm(weight, dy, dx, B, I, T, O, I, T, T, 0, O*T, I*T, trans_a=1)
-        dw = torch.empty_like(weight)                      # sum_b dy[b] (O, T) @ x[b]^T (T, I)
-        _gemm(dy, x, dw, 1, O, I, T, T, T, I, 0, 0, 0, trans_b=1, kbatch=B, a_kbs=O*T, b_kbs=I*T)
-        db = torch.empty(O, dtype=torch.float32, device=x.device)
-        hip.call('brv_row_sum', dy, db, B, O, T, hip.stream())
-        return dx, dw, db
 
 
 class _ReluDropoutFunction(torch.autograd.Function):
@@ -127,14 +91,14 @@ class _FFNN(nn.Module):
         x = x.float()
         linears = [m for m in self.module_list if isinstance(m, nn.Linear)]
         for lin in linears[:-1]:
-            x = _LinearFunction.apply(x, lin.weight, lin.bias)
+            x = LinearFunction.apply(x, lin.weight, lin.bias, False)
             mask, scale = None, 1.0
             if self.training and self.dropout > 0:
                 keep = 1.0 - self.dropout
                 mask = torch.empty_like(x).bernoulli_(keep)
                 scale = 1.0/keep
             x = _ReluDropoutFunction.apply(x, mask, scale)
-        x = _LinearFunction.apply(x, linears[-1].weight, linears[-1].bias)
+        x = LinearFunction.apply(x, linears[-1].weight, linears[-1].bias, False)
         return _SigmoidFunction.apply(x)
 
 

@@ -23,6 +23,7 @@ from .. import hip
 from ..modules.resampling import Resample
 from ..modules.stft import STFT
 from ..registry import Registry
+from ._ops import amp
 from .base import BreverBaseModel, ModelRegistry
 
 SDERegistry = Registry('sde')
@@ -1340,12 +1341,8 @@ class SGMSEp(BreverBaseModel):
         sigma = self.sde.sigma(t)
         n = sigma*self._draw_noise(x_0)
         weight = self.model.weight(sigma)
-        from . import sgmse_train
-        sgmse_train.AMP['on'] = bool(use_amp)
-        try:
+        with amp(use_amp):
             d = self.model.forward_train(x_0 - y + n, y, sigma, t)
-        finally:
-            sgmse_train.AMP['on'] = False
         return self.criterion(d, x_0 - y, lengths, weight=weight).mean()
 
     @torch.no_grad()

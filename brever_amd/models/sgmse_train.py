@@ -13,27 +13,7 @@ import os
 import torch
 
 from .. import hip
-
-
-AMP = {'on': False}       # set by SGMSEp.loss around the forward pass (use_amp)
-
-
-def _gemm(a, b, d, batch, M, N, K, lda, ldb, ldd, a_bs, b_bs, d_bs, trans_a=0, trans_b=0,
-          kbatch=1, a_kbs=0, b_kbs=0, bias=None, lowp=False):
-    """``lowp``: bf16 operands with fp32 accumulation (the convolutions under ``use_amp``); a bf16 ``b`` or ``d``
-    tensor (the column matrices of those convolutions) selects ``brv_gemm_bf16_mixed``."""
-    flags = int(b.dtype == torch.bfloat16) | int(d.dtype == torch.bfloat16) << 1
-    if flags:
-        assert lowp
-        hip.call('brv_gemm_bf16_mixed', a, b, d, batch, M, N, K, lda, ldb, ldd, a_bs, b_bs, d_bs, trans_a, trans_b,
-                 kbatch, a_kbs, b_kbs, bias, 0, flags, hip.stream())
-        return
-    if not lowp:
-        hip.gemm_f32(a, b, d, batch, M, N, K, lda, ldb, ldd, a_bs, b_bs, d_bs, trans_a, trans_b, kbatch, a_kbs,
-                     b_kbs, bias, 0)
-        return
-    hip.call('brv_gemm_bf16', a, b, d, batch, M, N, K, lda, ldb, ldd, a_bs, b_bs, d_bs, trans_a, trans_b, kbatch, a_kbs,
-             b_kbs, bias, 0, hip.stream())
+from ._ops import AMP, axpby_raw, col2im, empty, gemm, gemm_conv, im2col, row_sum
 
 
 # use_amp: the explicit column matrices (and the column-matrix gradient) in bf16 -- the products round them to bf16
@@ -47,14 +27,6 @@ _COL_BF16 = os.environ.get('BRV_SGMSE_COL_BF16', '0') == '1'
 _IMPLICIT = os.environ.get('BRV_SGMSE_TRAIN_IMPLICIT', '0') == '1'
 
 
-def _gemm_conv(a, img, d, batch, M, N, K, lda, ldd, a_bs, img_bs, d_bs, C, H, W, k, trans_b=0, kbatch=1, a_kbs=0,
-               img_kbs=0, bias=None):
-    """``_gemm(lowp=True)`` whose B operand is the im2col matrix of ``img`` (C, H, W per item; k x k window,
-    stride 1, padding k//2) -- never written out (``brv_gemm_bf16_conv``)."""
-    hip.call('brv_gemm_bf16_conv', a, img, d, batch, M, N, K, lda, ldd, a_bs, img_bs, d_bs, 0, trans_b, kbatch, a_kbs,
-             img_kbs, bias, 0, 1, C, H, W, k, k, 1, 1, k//2, k//2, H, W, hip.stream())
-
-
 # Column matrices kept from the forward pass for the weight gradient (instead of a second im2col in backward): up to
 # this many bytes per network evaluation -- the device has 288 GB, the default network at 4 x 1 s keeps 9 GB; past
 # the budget (long inputs, large batches) a convolution falls back to rebuilding its column matrix
@@ -62,8 +34,9 @@ _COL_BUDGET = int(float(os.environ.get('BRV_SGMSE_COL_CACHE_GB', '48'))*2**30)
 _col_kept = [0]
 
 
-def _empty(*shape, like):
-    return torch.empty(*shape, dtype=torch.float32, device=like.device)
+def _same(k):
+    """(window, stride, padding) of a k x k stride-1 'same' convolution, as ``im2col`` / ``gemm_conv`` take it."""
+    return (k, k), (1, 1), (k//2, k//2)
 
 
 class ConvFn(torch.autograd.Function):
@@ -75,14 +48,14 @@ class ConvFn(torch.autograd.Function):
         B, Cin, H, W = x.shape
         Cout, _, k, _ = w.shape
         K, HW = Cin*k*k, H*W
-        y = _empty(B, Cout, H, W, like=x)
+        y = empty(B, Cout, H, W, like=x)
         ctx.lowp = AMP['on']
         ctx.save_for_backward(x, w)
         if ctx.lowp and k > 1 and _IMPLICIT:
-            _gemm_conv(w, x, y, B, Cout, HW, K, K, HW, 0, Cin*HW, Cout*HW, Cin, H, W, k, bias=bias)
+            gemm_conv(w, x, y, B, Cout, HW, K, K, HW, 0, Cin*HW, Cout*HW, 1, (Cin, H, W), _same(k), (H, W), bias=bias)
             return y
         col = ConvFn._col(x, k, ctx.lowp)
-        _gemm(w, col, y, B, Cout, HW, K, K, HW, HW, 0, K*HW, Cout*HW, bias=bias, lowp=ctx.lowp)
+        gemm(w, col, y, B, Cout, HW, K, K, HW, HW, 0, K*HW, Cout*HW, bias=bias, lowp=ctx.lowp)
         ctx.col = None
         if k > 1 and any(ctx.needs_input_grad[:2]):
             nbytes = col.numel()*col.element_size()
@@ -93,14 +66,7 @@ class ConvFn(torch.autograd.Function):
 
     @staticmethod
     def _col(x, k, lowp=False):
-        if k == 1:
-            return x
-        B, Cin, H, W = x.shape
-        half = lowp and _COL_BF16
-        col = torch.empty(B, Cin*k*k, H*W, dtype=torch.bfloat16 if half else torch.float32, device=x.device)
-        hip.call('brv_im2col_bf16' if half else 'brv_im2col', x, col, B, Cin, H, W, k, k, 1, 1, k//2, k//2, H, W,
-                 hip.stream())
-        return col
+        return x if k == 1 else im2col(x, _same(k), x.shape[2:], bool(lowp and _COL_BF16))
 
     @staticmethod
     def backward(ctx, dy):
@@ -109,19 +75,19 @@ class ConvFn(torch.autograd.Function):
         B, Cin, H, W = x.shape
         Cout, _, k, _ = w.shape
         K, HW = Cin*k*k, H*W
-        db = _empty(Cout, like=x)
-        hip.call('brv_row_sum', dy, db, B, Cout, HW, hip.stream())
+        db = row_sum(dy, B, Cout, HW)
         if ctx.lowp and k > 1 and _IMPLICIT:
             # both gradients as products with a column matrix read in place: dW = dy @ col(x)^T summed over the
             # batch; dx = the same convolution of dy with the window rotated by 180 degrees and (Cout, Cin) swapped
             dw = torch.empty_like(w)
-            _gemm_conv(dy, x, dw, 1, Cout, K, HW, HW, K, 0, 0, 0, Cin, H, W, k, trans_b=1, kbatch=B,
-                       a_kbs=Cout*HW, img_kbs=Cin*HW)
+            gemm_conv(dy, x, dw, 1, Cout, K, HW, HW, K, 0, 0, 0, 1, (Cin, H, W), _same(k), (H, W), trans_b=1,
+                      kbatch=B, a_kbs=Cout*HW, img_kbs=Cin*HW)
             dx = None
             if ctx.needs_input_grad[0]:
                 wt = w.flip(2, 3).transpose(0, 1).reshape(Cin, Cout*k*k).contiguous()
                 dx = torch.empty_like(x)
-                _gemm_conv(wt, dy, dx, B, Cin, HW, Cout*k*k, Cout*k*k, HW, 0, Cout*HW, Cin*HW, Cout, H, W, k)
+                gemm_conv(wt, dy, dx, B, Cin, HW, Cout*k*k, Cout*k*k, HW, 0, Cout*HW, Cin*HW, 1, (Cout, H, W),
+                          _same(k), (H, W))
             return dx, dw, db
         col = getattr(ctx, 'col', None)
         if col is None:
@@ -129,19 +95,14 @@ class ConvFn(torch.autograd.Function):
         else:
             ctx.col = None                       # (its memory becomes dcol below and is released with this call)
         dw = torch.empty_like(w)
-        _gemm(dy, col, dw, 1, Cout, K, HW, HW, HW, K, 0, 0, 0, trans_b=1, kbatch=B,
-              a_kbs=Cout*HW, b_kbs=K*HW, lowp=ctx.lowp)
+        gemm(dy, col, dw, 1, Cout, K, HW, HW, HW, K, 0, 0, 0, trans_b=1, kbatch=B,
+             a_kbs=Cout*HW, b_kbs=K*HW, lowp=ctx.lowp)
         dx = None
         if ctx.needs_input_grad[0]:
-            dcol = col if k != 1 else _empty(B, K, HW, like=x)
-            _gemm(w, dy, dcol, B, K, HW, Cout, K, HW, HW, 0, Cout*HW, K*HW, trans_a=1,
-                  lowp=ctx.lowp)
-            if k == 1:
-                dx = dcol.view(B, Cin, H, W)
-            else:
-                dx = torch.empty_like(x)
-                hip.call('brv_col2im_bf16' if dcol.dtype == torch.bfloat16 else 'brv_col2im', dcol, None, dx,
-                         B, Cin, H, W, k, k, 1, 1, k//2, k//2, H, W, hip.stream())
+            dcol = col if k != 1 else empty(B, K, HW, like=x)
+            gemm(w, dy, dcol, B, K, HW, Cout, K, HW, HW, 0, Cout*HW, K*HW, trans_a=1,
+                 lowp=ctx.lowp)
+            dx = dcol.view(B, Cin, H, W) if k == 1 else col2im(dcol, None, Cin, (H, W), _same(k), (H, W))
         return dx, dw, db
 
 
@@ -155,7 +116,7 @@ class GroupNormFn(torch.autograd.Function):
         lib = hip.lib()
         scratch = torch.zeros(lib.brv_groupnorm_scratch_bytes(B, groups), dtype=torch.uint8,
                               device=x.device)
-        scale, shift, mu, rstd = (_empty(B, C, like=x) for _ in range(4))
+        scale, shift, mu, rstd = (empty(B, C, like=x) for _ in range(4))
         addc = add.contiguous() if add is not None else None
         hip.call('brv_groupnorm_fold', x, addc, gamma, beta, None, None, scratch, scale, shift, mu, rstd, B, C, H*W,
                  groups, float(eps), hip.stream())
@@ -172,8 +133,8 @@ class GroupNormFn(torch.autograd.Function):
         dy = dy.contiguous()
         B, C, H, W = x.shape
         dx = torch.empty_like(x)
-        s1, s2, dadd = (_empty(B, C, like=x) for _ in range(3))
-        coef = _empty(3*B*C, like=x)
+        s1, s2, dadd = (empty(B, C, like=x) for _ in range(3))
+        coef = empty(3*B*C, like=x)
         hip.call('brv_groupnorm_backward', x, dy, scale, shift, mu, rstd, gamma, dx, s1, s2, dadd, coef, B, C, H*W,
                  groups, int(silu), hip.stream())
         # d gamma / d beta: (B, C) -> (C,), a handful of values
@@ -225,26 +186,20 @@ class SiluFn(torch.autograd.Function):
         return dx
 
 
-def _axpby_raw(a, alpha, b, beta):
-    out = torch.empty_like(a)
-    hip.call('brv_axpby', a, float(alpha), b, float(beta), out, a.numel(), hip.stream())
-    return out
-
-
 class AxpbyFn(torch.autograd.Function):
     """alpha*a + beta*b (b may be None)."""
 
     @staticmethod
     def forward(ctx, a, alpha, b, beta):
         ctx.coef = (float(alpha), float(beta), b is not None)
-        return _axpby_raw(a.contiguous(), alpha, b.contiguous() if b is not None else None, beta)
+        return axpby_raw(a.contiguous(), alpha, b.contiguous() if b is not None else None, beta)
 
     @staticmethod
     def backward(ctx, g):
         alpha, beta, has_b = ctx.coef
         g = g.contiguous()
-        return (_axpby_raw(g, alpha, None, 0.0), None,
-                _axpby_raw(g, beta, None, 0.0) if has_b else None, None)
+        return (axpby_raw(g, alpha, None, 0.0), None,
+                axpby_raw(g, beta, None, 0.0) if has_b else None, None)
 
 
 class ResampleFn(torch.autograd.Function):
@@ -256,7 +211,7 @@ class ResampleFn(torch.autograd.Function):
         x = x.contiguous()
         B, C, H, W = x.shape
         K = kernel.shape[-1]
-        y = _empty(B, C, out_hw[0], out_hw[1], like=x)
+        y = empty(B, C, out_hw[0], out_hw[1], like=x)
         hip.call('brv_fir_resample2d', x, kernel, y, B*C, H, W, out_hw[0], out_hw[1], K, pad[0], pad[1], int(up),
                  4.0 if up else 1.0, hip.stream())
         ctx.save_for_backward(kernel)
@@ -270,7 +225,7 @@ class ResampleFn(torch.autograd.Function):
         dy = dy.contiguous()
         B, C, Ho, Wo = dy.shape
         K = kernel.shape[-1]
-        dx = _empty(B, C, H, W, like=dy)
+        dx = empty(B, C, H, W, like=dy)
         if up:       # adjoint of the transposed convolution with 4*kernel: strided FIR with 4*kernel
             k4 = (4.0*kernel).contiguous()
             hip.call('brv_fir_resample2d', dy, k4, dx, B*C, Ho, Wo, H, W, K, pad[0], pad[1], 0, 1.0, hip.stream())
@@ -287,8 +242,8 @@ class LinearFn(torch.autograd.Function):
         x = x.contiguous()
         N, I = x.shape
         O = w.shape[0]
-        yt = _empty(O, N, like=x)
-        _gemm(w, x, yt, 1, O, N, I, I, I, N, 0, 0, 0, trans_b=1, bias=bias)
+        yt = empty(O, N, like=x)
+        gemm(w, x, yt, 1, O, N, I, I, I, N, 0, 0, 0, trans_b=1, bias=bias)
         ctx.save_for_backward(x, w)
         return yt.t().contiguous()
 
@@ -298,10 +253,10 @@ class LinearFn(torch.autograd.Function):
         dy = dy.contiguous()
         N, I = x.shape
         O = w.shape[0]
-        dx = _empty(N, I, like=x)
-        _gemm(dy, w, dx, 1, N, I, O, O, I, I, 0, 0, 0)
+        dx = empty(N, I, like=x)
+        gemm(dy, w, dx, 1, N, I, O, O, I, I, 0, 0, 0)
         dw = torch.empty_like(w)
-        _gemm(dy, x, dw, 1, O, I, N, O, I, I, 0, 0, 0, trans_a=1)
+        gemm(dy, x, dw, 1, O, I, N, O, I, I, 0, 0, 0, trans_a=1)
         return dx, dw, dy.sum(0)
 
 
@@ -312,13 +267,13 @@ class AttentionCoreFn(torch.autograd.Function):
     def forward(ctx, q, k, v):
         q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
         N, C, L = q.shape
-        w = _empty(N, L, L, like=q)
-        _gemm(q, k, w, N, L, L, C, L, L, L, C*L, C*L, L*L, trans_a=1)
-        w = _axpby_raw(w, 1.0/C**0.5, None, 0.0)
+        w = empty(N, L, L, like=q)
+        gemm(q, k, w, N, L, L, C, L, L, L, C*L, C*L, L*L, trans_a=1)
+        w = axpby_raw(w, 1.0/C**0.5, None, 0.0)
         p = torch.empty_like(w)
         hip.call('brv_softmax_rows', w, p, N*L, L, hip.stream())
-        a = _empty(N, C, L, like=q)
-        _gemm(v, p, a, N, C, L, L, L, L, L, C*L, L*L, C*L, trans_b=1)
+        a = empty(N, C, L, like=q)
+        gemm(v, p, a, N, C, L, L, L, L, L, C*L, L*L, C*L, trans_b=1)
         ctx.save_for_backward(q, k, v, p)
         return a
 
@@ -328,16 +283,16 @@ class AttentionCoreFn(torch.autograd.Function):
         da = da.contiguous()
         N, C, L = q.shape
         dv = torch.empty_like(v)                      # da (C x L) @ P (L x L)
-        _gemm(da, p, dv, N, C, L, L, L, L, L, C*L, L*L, C*L)
+        gemm(da, p, dv, N, C, L, L, L, L, L, C*L, L*L, C*L)
         dp = torch.empty_like(p)                      # da^T (L x C) @ v (C x L)
-        _gemm(da, v, dp, N, L, L, C, L, L, L, C*L, C*L, L*L, trans_a=1)
+        gemm(da, v, dp, N, L, L, C, L, L, L, C*L, C*L, L*L, trans_a=1)
         dw = torch.empty_like(p)
         hip.call('brv_softmax_rows_backward', p, dp, dw, N*L, L, hip.stream())
-        dw = _axpby_raw(dw, 1.0/C**0.5, None, 0.0)
+        dw = axpby_raw(dw, 1.0/C**0.5, None, 0.0)
         dq = torch.empty_like(q)                      # k (C x L) @ dW^T
-        _gemm(k, dw, dq, N, C, L, L, L, L, L, C*L, L*L, C*L, trans_b=1)
+        gemm(k, dw, dq, N, C, L, L, L, L, L, C*L, L*L, C*L, trans_b=1)
         dk = torch.empty_like(k)                      # q (C x L) @ dW
-        _gemm(q, dw, dk, N, C, L, L, L, L, L, C*L, L*L, C*L)
+        gemm(q, dw, dk, N, C, L, L, L, L, L, C*L, L*L, C*L)
         return dq, dk, dv
 
 

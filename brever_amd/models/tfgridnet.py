@@ -14,7 +14,7 @@ operation runs in ``libbrever_hip.so`` through ``torch.autograd.Function`` pairs
   ``LayerNormalization4DCF`` and ``AllHeadPReLULayerNormalization4DCF`` are one row-norm operator
   (``brv_rownorm_*``) on rows laid out so that the normalised axes are contiguous; the
   bidirectional LSTMs run both directions of all sequences concurrently in the register-resident
-  recurrence kernels (``dccrn._LSTMFunction``, two groups: the sequence and its reversal); the
+  recurrence kernels (``_ops.LSTMFunction``, two groups: the sequence and its reversal); the
   linear layers and 1x1 convolutions are MFMA products over the channel axis; the attention is
   two batched products around ``brv_softmax_rows``.
 
@@ -31,8 +31,9 @@ import torch.nn.functional as F
 from .. import hip
 from ..modules.stft import STFT
 from . import sgmse_train as T
+from ._ops import AMP, LSTMFunction, _ParamOnly, amp, axpby_raw, col2im, column_sums, empty, gemm, im2col
+from ._ops import lstm_deinterleave, lstm_interleave, row_sum
 from .base import BreverBaseModel, ModelRegistry
-from .dccrn import _AMP, _LSTMFunction, _ParamOnly
 
 
 class LayerNormalization4DCF(_ParamOnly):
@@ -133,8 +134,7 @@ class _RowNormFn(torch.autograd.Function):
                  hip.stream())
         dslope = None
         if has_slope:                                   # rows are (outer, G, inner)
-            dslope = torch.empty(G, dtype=torch.float32, device=x.device)
-            hip.call('brv_row_sum', rows, dslope, R//(G*inner), G, inner, hip.stream())
+            dslope = row_sum(rows, R//(G*inner), G, inner)
         return dx, dslope, dgain, dbias, None, None
 
 
@@ -164,14 +164,14 @@ class _AttentionFn(torch.autograd.Function):
         q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
         N, L, D = q.shape
         Dv = v.shape[-1]
-        lowp = ctx.lowp = _AMP['on']
-        w = T._empty(N, L, L, like=q)
-        T._gemm(q, k, w, N, L, L, D, D, D, L, L*D, L*D, L*L, trans_b=1, lowp=lowp)
-        w = T._axpby_raw(w, 1.0/D**0.5, None, 0.0)
+        lowp = ctx.lowp = AMP['on']
+        w = empty(N, L, L, like=q)
+        gemm(q, k, w, N, L, L, D, D, D, L, L*D, L*D, L*L, trans_b=1, lowp=lowp)
+        w = axpby_raw(w, 1.0/D**0.5, None, 0.0)
         p = torch.empty_like(w)
         hip.call('brv_softmax_rows', w, p, N*L, L, hip.stream())
-        a = T._empty(N, L, Dv, like=q)
-        T._gemm(p, v, a, N, L, Dv, L, L, Dv, Dv, L*L, L*Dv, L*Dv, lowp=lowp)
+        a = empty(N, L, Dv, like=q)
+        gemm(p, v, a, N, L, Dv, L, L, Dv, Dv, L*L, L*Dv, L*Dv, lowp=lowp)
         ctx.save_for_backward(q, k, v, p)
         return a
 
@@ -183,86 +183,21 @@ class _AttentionFn(torch.autograd.Function):
         Dv = v.shape[-1]
         lowp = ctx.lowp
         dv = torch.empty_like(v)                       # P^T (L x L) @ da (L x Dv)
-        T._gemm(p, da, dv, N, L, Dv, L, L, Dv, Dv, L*L, L*Dv, L*Dv, trans_a=1, lowp=lowp)
+        gemm(p, da, dv, N, L, Dv, L, L, Dv, Dv, L*L, L*Dv, L*Dv, trans_a=1, lowp=lowp)
         dp = torch.empty_like(p)                       # da (L x Dv) @ v^T
-        T._gemm(da, v, dp, N, L, L, Dv, Dv, Dv, L, L*Dv, L*Dv, L*L, trans_b=1, lowp=lowp)
+        gemm(da, v, dp, N, L, L, Dv, Dv, Dv, L, L*Dv, L*Dv, L*L, trans_b=1, lowp=lowp)
         dw = torch.empty_like(p)
         hip.call('brv_softmax_rows_backward', p, dp, dw, N*L, L, hip.stream())
-        dw = T._axpby_raw(dw, 1.0/D**0.5, None, 0.0)
+        dw = axpby_raw(dw, 1.0/D**0.5, None, 0.0)
         dq = torch.empty_like(q)                       # dW (L x L) @ k (L x D)
-        T._gemm(dw, k, dq, N, L, D, L, L, D, D, L*L, L*D, L*D, lowp=lowp)
+        gemm(dw, k, dq, N, L, D, L, L, D, D, L*L, L*D, L*D, lowp=lowp)
         dk = torch.empty_like(k)                       # dW^T @ q
-        T._gemm(dw, q, dk, N, L, D, L, L, D, D, L*L, L*D, L*D, trans_a=1, lowp=lowp)
+        gemm(dw, q, dk, N, L, D, L, L, D, D, L*L, L*D, L*D, trans_a=1, lowp=lowp)
         return dq, dk, dv
 
 
-_SMALL = os.environ.get('BRV_TFG_LINEAR_SMALL', '1') != '0'     # narrow linear layers on brv_linear_small
-_SMALL_SCRATCH = {}
-# NOTE: the two narrow-layer paths below are taken BEFORE ``lowp`` is looked at, so under use_amp the
-# layers with K, N <= 64 (and their weight gradients) run in full fp32 while every other product rounds its operands
-# to bf16: closer to the fp32 oracle than the bf16 emulation assumes, never further (the use_amp tolerances of
-# tests/test_gpu.py are upper bounds on the distance from the fp32 reference). The cut-over is a size rule of the
-# library (`brv_linear_small_supported`), so results change at that size by bf16-rounding level, not more.
-
-
-def _gemm(a, b, d, batch, M, N, K, lda, ldb, ldd, a_bs=0, b_bs=0, d_bs=0, trans_a=0, trans_b=0,
-          kbatch=1, a_kbs=0, b_kbs=0, bias=None, mode=0, lowp=False):
-    """brv_gemm_f32 / brv_gemm_bf16 (bf16 operands, fp32 accumulation: ``use_amp``); ``mode`` 1
-    adds to d, 2 reads ``bias`` per output column; a bf16 ``d`` tensor is written directly."""
-    half = torch.bfloat16
-    flags = int(b.dtype == half) | int(d.dtype == half) << 1 | int(a.dtype == half) << 2
-    if _SMALL and not flags and batch == 1 and kbatch == 1 and not trans_a and (bias is None or mode == 2) \
-            and lda % 4 == 0 and ldd % 4 == 0 and (a.data_ptr() | d.data_ptr()) % 16 == 0 \
-            and hip.lib().brv_linear_small_supported(M, N, K):
-        # narrow layers (K, N <= 64 over ~2.6e5 rows): one thread per row in fp32 instead of a 128 x 128 MFMA tile
-        hip.call('brv_linear_small', a, b, bias, d, M, N, K, lda, ldb, ldd, trans_b, int(mode == 1), hip.stream())
-        return
-    if _SMALL and not flags and batch == 1 and kbatch == 1 and trans_a and not trans_b and bias is None and mode == 0 \
-            and lda % 4 == 0 and ldb % 4 == 0 and (a.data_ptr() | b.data_ptr()) % 16 == 0 \
-            and hip.lib().brv_linear_small_wgrad_supported(K, M, N):
-        # their weight gradients: (rows x M)^T (rows x N) over ~2.6e5 rows, slices added in a fixed order
-        lib = hip.lib()
-        # (one scratch buffer per device and size, not an allocation per call: up to 48 calls per step -- ADVICE r4; the
-        # launches of a stream run in order, so consecutive products may share it)
-        nbytes = lib.brv_linear_small_wgrad_scratch_bytes(M, N)
-        key = (d.device.index, torch.cuda.current_stream(d.device).cuda_stream)
-        scratch = _SMALL_SCRATCH.get(key)
-        if scratch is None or scratch.numel() < nbytes:
-            scratch = _SMALL_SCRATCH[key] = torch.empty(nbytes, dtype=torch.uint8, device=d.device)
-        hip.call('brv_linear_small_wgrad', a, b, d, scratch, K, M, N, lda, ldb, ldd, hip.stream())
-        return
-    if flags:
-        hip.call('brv_gemm_bf16_mixed', a, b, d, batch, M, N, K, lda, ldb, ldd, a_bs, b_bs, d_bs, trans_a, trans_b,
-                 kbatch, a_kbs, b_kbs, bias, mode, flags, hip.stream())
-        return
-    if not lowp:
-        hip.gemm_f32(a, b, d, batch, M, N, K, lda, ldb, ldd, a_bs, b_bs, d_bs, trans_a, trans_b, kbatch, a_kbs,
-                     b_kbs, bias, mode)
-        return
-    hip.call('brv_gemm_bf16', a, b, d, batch, M, N, K, lda, ldb, ldd, a_bs, b_bs, d_bs, trans_a, trans_b, kbatch, a_kbs,
-             b_kbs, bias, mode, hip.stream())
-
-
-def _column_sums(x, rows, cols, batch=1, lowp=False):
-    """(batch, rows, cols) -> (batch, cols). fp32 tensors: ``brv_col_sum`` (fixed order, 16-byte loads: 17 us for
-    258 516 x 32 -- also under ``lowp``, where round 3 used a ones-vector product with split atomics); bf16
-    tensors: a ones-vector product on the bf16 MFMA."""
-    out = torch.empty(batch, cols, dtype=torch.float32, device=x.device)
-    if x.dtype == torch.float32:
-        lib = hip.lib()
-        scratch = torch.empty(lib.brv_col_sum_scratch_bytes(batch, cols), dtype=torch.uint8,
-                              device=x.device)
-        hip.call('brv_col_sum', x, out, scratch, batch, rows, cols, hip.stream())
-        return out
-    if x.dtype == torch.bfloat16 and cols % 8 == 0 and x.data_ptr() % 16 == 0:
-        lib = hip.lib()
-        scratch = torch.empty(lib.brv_col_sum_scratch_bytes(batch, cols), dtype=torch.uint8,
-                              device=x.device)
-        hip.call('brv_col_sum_bf16', x, out, scratch, batch, rows, cols, hip.stream())
-        return out
-    ones = torch.ones(rows, dtype=torch.float32, device=x.device)
-    _gemm(ones, x, out, batch, 1, cols, rows, rows, cols, cols, 0, rows*cols, cols, lowp=True)
-    return out
+# narrow linear layers on brv_linear_small / brv_linear_small_wgrad (``_ops.gemm(small=True)``)
+_SMALL = os.environ.get('BRV_TFG_LINEAR_SMALL', '1') != '0'
 
 
 class _LinearFn(torch.autograd.Function):
@@ -273,9 +208,9 @@ class _LinearFn(torch.autograd.Function):
         x, w = x.contiguous(), w.contiguous()
         N, I = x.shape
         O = w.shape[0]
-        lowp = ctx.lowp = _AMP['on']
-        y = T._empty(N, O, like=x)
-        _gemm(x, w, y, 1, N, O, I, I, I, O, trans_b=1, bias=bias.contiguous(), mode=2, lowp=lowp)
+        lowp = ctx.lowp = AMP['on']
+        y = empty(N, O, like=x)
+        gemm(x, w, y, 1, N, O, I, I, I, O, trans_b=1, bias=bias.contiguous(), mode=2, lowp=lowp, small=_SMALL)
         ctx.save_for_backward(x, w)
         return y
 
@@ -285,11 +220,11 @@ class _LinearFn(torch.autograd.Function):
         dy = dy.contiguous()
         N, I = x.shape
         O = w.shape[0]
-        dx = T._empty(N, I, like=x)
-        _gemm(dy, w, dx, 1, N, I, O, O, I, I, lowp=ctx.lowp)
+        dx = empty(N, I, like=x)
+        gemm(dy, w, dx, 1, N, I, O, O, I, I, lowp=ctx.lowp, small=_SMALL)
         dw = torch.empty_like(w)
-        _gemm(dy, x, dw, 1, O, I, N, O, I, I, trans_a=1, lowp=ctx.lowp)
-        return dx, dw, _column_sums(dy, N, O, lowp=ctx.lowp)[0]
+        gemm(dy, x, dw, 1, O, I, N, O, I, I, trans_a=1, lowp=ctx.lowp, small=_SMALL)
+        return dx, dw, column_sums(dy, N, O)[0]
 
 
 def _linear(x, mod):
@@ -311,16 +246,16 @@ class _BiLSTMFn(torch.autograd.Function):
         x, w_hh = x.contiguous(), w_hh.contiguous()
         N, S, I = x.shape
         H = w_hh.shape[-1]
-        lowp = ctx.lowp = _AMP['on']
-        w_ih = _LSTMFunction._interleave(w_ih.contiguous(), H)
+        lowp = ctx.lowp = AMP['on']
+        w_ih = lstm_interleave(w_ih.contiguous(), H)
         # use_amp: the input projection and the saved gate activations are bf16 tensors (the
         # recurrence kernel is HBM-bound on exactly these two streams)
         io = torch.bfloat16 if lowp else torch.float32
         gates = torch.empty(2, N, S, 4*H, dtype=io, device=x.device)
-        _gemm(x, w_ih, gates, 2, N*S, 4*H, I, I, I, 4*H, 0, 4*H*I, N*S*4*H, trans_b=1, lowp=lowp)
-        bias = T._axpby_raw(b_ih.detach().contiguous(), 1.0, b_hh.detach().contiguous(), 1.0)
-        y = T._empty(N, S, 2*H, like=x)
-        act, cs = torch.empty(2, N, S, 4*H, dtype=io, device=x.device), T._empty(2, N, S, H, like=x)
+        gemm(x, w_ih, gates, 2, N*S, 4*H, I, I, I, 4*H, 0, 4*H*I, N*S*4*H, trans_b=1, lowp=lowp)
+        bias = axpby_raw(b_ih.detach().contiguous(), 1.0, b_hh.detach().contiguous(), 1.0)
+        y = empty(N, S, 2*H, like=x)
+        act, cs = torch.empty(2, N, S, 4*H, dtype=io, device=x.device), empty(2, N, S, H, like=x)
         hip.call('brv_lstm_tile_forward', gates, w_hh, bias, y, act, cs, 2*N, S, H, 2, 2, 2*H, H, 2*int(lowp),
                  hip.stream())
         ctx.save_for_backward(x, w_ih, w_hh, y, act, cs)
@@ -336,19 +271,19 @@ class _BiLSTMFn(torch.autograd.Function):
         dg = torch.empty(2, N, S, 4*H, dtype=act.dtype, device=x.device)     # bf16 under use_amp
         hip.call('brv_lstm_tile_backward', act, cs, w_hh, dy, dg, 2*N, S, H, 2, 2, 2*H, H, 2*int(lowp), hip.stream())
         dx = torch.empty_like(x)                      # sum over both directions: dg_g @ W_ih_g
-        _gemm(dg, w_ih, dx, 1, NS, I, 4*H, 4*H, I, I, kbatch=2, a_kbs=NS*4*H, b_kbs=4*H*I,
-              lowp=lowp)
+        gemm(dg, w_ih, dx, 1, NS, I, 4*H, 4*H, I, I, kbatch=2, a_kbs=NS*4*H, b_kbs=4*H*I,
+             lowp=lowp)
         dw_ih = torch.empty_like(w_ih)                # dg_g^T @ x
-        _gemm(dg, x, dw_ih, 2, 4*H, I, NS, 4*H, I, I, NS*4*H, 0, 4*H*I, trans_a=1, lowp=lowp)
+        gemm(dg, x, dw_ih, 2, 4*H, I, NS, 4*H, I, I, NS*4*H, 0, 4*H*I, trans_a=1, lowp=lowp)
         dw_hh = torch.zeros_like(w_hh) if S == 1 else torch.empty_like(w_hh)
         if S > 1:
             # forward direction: gate gradients of frames 1.. against hidden states of frames 0..;
             # backward direction: frames ..S-2 against hidden states of frames 1.. -- ONE launch: the directions are the
             # batch (from the forward direction's operands the backward one's lie NS 4H - 4H / 3H elements further)
-            _gemm(dg.view(-1)[4*H:], y.view(-1), dw_hh, 2, 4*H, H, S - 1, 4*H, 2*H, H, NS*4*H - 4*H, 3*H, 4*H*H,
-                  trans_a=1, kbatch=N, a_kbs=S*4*H, b_kbs=S*2*H, lowp=lowp)
-        db = _column_sums(dg, NS, 4*H, batch=2)
-        dw_ih, dw_hh, db = (_LSTMFunction._deinterleave(t, H) for t in (dw_ih, dw_hh, db))
+            gemm(dg.view(-1)[4*H:], y.view(-1), dw_hh, 2, 4*H, H, S - 1, 4*H, 2*H, H, NS*4*H - 4*H, 3*H, 4*H*H,
+                 trans_a=1, kbatch=N, a_kbs=S*4*H, b_kbs=S*2*H, lowp=lowp)
+        db = column_sums(dg, NS, 4*H, batch=2)
+        dw_ih, dw_hh, db = (lstm_deinterleave(t, H) for t in (dw_ih, dw_hh, db))
         return dx, dw_ih, dw_hh, db, db.clone()
 
 
@@ -359,23 +294,12 @@ class _WindowFn(torch.autograd.Function):
     ConvTranspose1d does after its channel product)."""
 
     @staticmethod
-    def _geom(C, S, ks, hs):
-        return (C, S, 1, ks, 1, hs, 1, 0, 0, (S - ks)//hs + 1, 1)
-
-    @staticmethod
     def _unfold(x, C, S, ks, hs):
-        N = x.shape[0]
-        n = (S - ks)//hs + 1
-        col = T._empty(N, C*ks, n, like=x)
-        hip.call('brv_im2col', x, col, N, *_WindowFn._geom(C, S, ks, hs), hip.stream())
-        return col
+        return im2col(x.unsqueeze(-1), ((ks, 1), (hs, 1), (0, 0)), ((S - ks)//hs + 1, 1))
 
     @staticmethod
     def _fold(col, bias, C, S, ks, hs):
-        N = col.shape[0]
-        out = T._empty(N, C, S, like=col)
-        hip.call('brv_col2im', col, bias, out, N, *_WindowFn._geom(C, S, ks, hs), hip.stream())
-        return out
+        return col2im(col, bias, C, (S, 1), ((ks, 1), (hs, 1), (0, 0)), ((S - ks)//hs + 1, 1)).squeeze(-1)
 
     @staticmethod
     def forward(ctx, x, bias, C, S, ks, hs, fold):
@@ -391,10 +315,7 @@ class _WindowFn(torch.autograd.Function):
         g = g.contiguous()
         if not fold:
             return _WindowFn._fold(g, None, C, S, ks, hs), None, None, None, None, None, None
-        db = None
-        if has_bias:
-            db = T._empty(C, like=g)
-            hip.call('brv_row_sum', g, db, g.shape[0], C, S, hip.stream())
+        db = row_sum(g, g.shape[0], C, S) if has_bias else None
         return _WindowFn._unfold(g, C, S, ks, hs), db, None, None, None, None, None
 
 
@@ -456,7 +377,7 @@ def _bilstm(x, rnn):
     if hip.lib().brv_lstm_tile_supported(rnn.hidden_size):
         return _BiLSTMFn.apply(x, stack('weight_ih'), stack('weight_hh'), stack('bias_ih'),
                                stack('bias_hh'))
-    y = _LSTMFunction.apply(torch.stack([x, x.flip(1)]), stack('weight_ih'), stack('weight_hh'),
+    y = LSTMFunction.apply(torch.stack([x, x.flip(1)]), stack('weight_ih'), stack('weight_hh'),
                             stack('bias_ih'), stack('bias_hh'))
     return torch.cat([y[0], y[1].flip(1)], dim=-1)
 
@@ -617,21 +538,14 @@ class TFGridNet(BreverBaseModel):
         inputs, labels = batch[:, 0], batch[:, 1:]
         # reference signal: the average of the left and right direct-path signals
         # (tfgridnet.py:135-139)
-        labels = T._axpby_raw(labels[:, :, 0].contiguous(), 0.5, labels[:, :, 1].contiguous(), 0.5)
-        _AMP['on'] = T.AMP['on'] = bool(use_amp)
-        try:
+        labels = axpby_raw(labels[:, :, 0].contiguous(), 0.5, labels[:, :, 1].contiguous(), 0.5)
+        with amp(use_amp):
             outputs = self(inputs)
-        finally:
-            _AMP['on'] = T.AMP['on'] = False
         return self.criterion(outputs, labels, lengths).mean()
 
     def _enhance(self, x, use_amp):
-        _AMP['on'] = T.AMP['on'] = bool(use_amp)
-        try:
-            with torch.no_grad():
-                return self.forward(x)
-        finally:
-            _AMP['on'] = T.AMP['on'] = False
+        with amp(use_amp), torch.no_grad():
+            return self.forward(x)
 
     def update(self, loss, scaler):
         super().update(loss, scaler, grad_clip=self.grad_clip)

@@ -69,11 +69,11 @@ def main():
             xd, Ho, Wo = x.detach(), y.shape[2], y.shape[3]
             if tr:
                 new = timed(lambda: D._cconv_wgrad(xd, dy))
-                old = timed(lambda: D._gemm_conv(xd, dy, dwc, 1, 2*cin, 2*Cw, H*W, H*W, 2*Cw, 0, 0, 0, 1, (2*cout, Ho, Wo),
+                old = timed(lambda: D.gemm_conv(xd, dy, dwc, 1, 2*cin, 2*Cw, H*W, H*W, 2*Cw, 0, 0, 0, 1, (2*cout, Ho, Wo),
                                                  geom, (H, W), trans_b=1, kbatch=B, a_kbs=2*cin*H*W, img_kbs=2*cout*Ho*Wo))
             else:
                 new = timed(lambda: D._cconv_wgrad(dy, xd))
-                old = timed(lambda: D._gemm_conv(dy, xd, dwc, 1, 2*cout, 2*Cw, Ho*Wo, Ho*Wo, 2*Cw, 0, 0, 0, 1, (2*cin, H, W),
+                old = timed(lambda: D.gemm_conv(dy, xd, dwc, 1, 2*cout, 2*Cw, Ho*Wo, Ho*Wo, 2*Cw, 0, 0, 0, 1, (2*cin, H, W),
                                                  geom, (Ho, Wo), trans_b=1, kbatch=B, a_kbs=2*cout*Ho*Wo, img_kbs=2*cin*H*W))
             print(f'{name} wgrad rows {new:7.1f} us ({flops/new/1e6:6.1f} TF/s)   column-matrix {old:7.1f} us', flush=True)
             continue
