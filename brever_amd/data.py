@@ -459,10 +459,11 @@ class BreverDataset(torch.utils.data.Dataset):
     ):
         if dynamic_mixing and _mixture_maker is None:
             raise NotImplementedError(
-                'dynamic_mixing=True needs a mixture maker: the reference synthesises mixtures '
-                'from raw corpora with brever.mixture.RandomMixtureMaker, which is outside this '
-                'build; install a class with the same protocol through '
-                'brever_amd.data.set_mixture_maker (e.g. SyntheticMixtureMaker)')
+                'dynamic_mixing=True needs a mixture maker: install one through '
+                'brever_amd.data.set_mixture_maker. brever_amd.mixture.PoolMixtureMaker synthesises '
+                'every epoch on the GPU from in-memory speech, noise and BRIR pools (the signal '
+                'processing of brever.mixture.RandomMixtureMaker; corpus scanning and file input are '
+                'outside this build); SyntheticMixtureMaker draws white-noise pairs')
         self.path = path
         self.segment_length = round(segment_length*fs)
         self.overlap_length = round(overlap_length*fs)
