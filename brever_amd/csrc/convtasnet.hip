@@ -13,6 +13,7 @@
 
 #include "../../include/brever_hip.h"
 #include "status.h"
+#include "ctn_layout.h"
 #include "gemm_rows.cuh"
 #include "gemm_wgrad.cuh"
 #include "gemm_ws.cuh"
@@ -80,9 +81,7 @@ struct ProfScope {
 };
 inline bool prof_by_dil() { return t_opts->prof && static_cast<Prof*>(t_opts->prof)->by_dil; }
 
-struct BlockOff {
-  long long conv_w, conv_b, dconv_w, dconv_b, res_w, res_b, skip_w, skip_b,
-      n1_g, n1_b, n2_g, n2_b, prelu1, prelu2;
+struct BlockOff : CtnBlockOff {
   long long p_c1_f, p_c1_b, p_rs_f, p_rs_b;     // prepared (bf16 elements)
   long long p_c1_fp, p_rs_fp, p_rs_bp;          // fragment-order copies (persistent GEMMs)
   // lazy second norm (fused forward): [res | skip] weights times gamma_2, always Bnp + Scp rows
@@ -91,13 +90,10 @@ struct BlockOff {
   long long p_rs_g, p_rs_gp, p_lazy;
 };
 
-struct Layout {
-  int N, K, Bn, H, Sc, P, nb, S, hop, causal;
+// parameter offsets: ctn_layout.h; this path adds the padded widths and the prepared bf16 operands
+struct Layout : CtnLayout<BlockOff> {
   int Np, Kfp, Bnp, Hp, Scp;
-  long long enc_w, dec_w, ln_g, ln_b, bott_w, bott_b, tcn_prelu, out_w, out_b, n_params;
   long long p_enc, p_dec_f, p_dec_b, p_bott_f, p_bott_b, p_out_f, p_out_b, p_stamp, n_prepared;
-  std::vector<BlockOff> blk;
-  std::vector<long long> tensor_offsets;
 
   // the fused forward runs for the default widths, non-causal, kernel_size 3 (see brv_ctn_forward);
   // `fusable` is a property of the architecture (it sizes the workspace), `fused_fwd` of the call
@@ -108,39 +104,13 @@ struct Layout {
   // first-conv backward without the stored z1 / dz1 (pw1_bwd.cuh): default widths of that layer
   bool pw1_rc() const { return !causal && Hp == RC_H && Bnp == RC_N && pw1_rc_requested(); }
 
+  static int limits(const brv_ctn_config* c) {
+    return c->kernel_size < 1 || c->kernel_size > 5 ? fail(-2, "kernel_size must be in [1, 5] in the HIP path") : 0;
+  }
   int init(const brv_ctn_config* c) {
-    if (!c) return fail(-1, "null config");
-    if (c->filters < 1 || c->filter_length < 2 || c->bottleneck_channels < 1 ||
-        c->hidden_channels < 1 || c->skip_channels < 1 || c->layers < 1 ||
-        c->repeats < 1 || c->output_sources < 1)
-      return fail(-1, "invalid Conv-TasNet hyper-parameters");
-    if (c->kernel_size < 1 || c->kernel_size > 5)
-      return fail(-2, "kernel_size must be in [1, 5] in the HIP path");
-    N = c->filters; K = c->filter_length; Bn = c->bottleneck_channels;
-    H = c->hidden_channels; Sc = c->skip_channels; P = c->kernel_size;
-    nb = c->layers*c->repeats; S = c->output_sources; hop = K/2; causal = c->causal != 0;
+    if (int r = CtnLayout::init(c, limits)) return r;
     Np = round_up(N, 64); Kfp = round_up(K, 64); Bnp = round_up(Bn, 64);
     Hp = round_up(H, 64); Scp = round_up(Sc, 64);
-    long long o = 0;
-    auto take = [&](long long n) { tensor_offsets.push_back(o); long long r = o; o += n; return r; };
-    enc_w = take((long long)N*K);
-    dec_w = take((long long)N*K);
-    ln_g = take(N); ln_b = take(N);
-    bott_w = take((long long)Bn*N); bott_b = take(Bn);
-    blk.resize(nb);
-    for (int i = 0; i < nb; ++i) {
-      BlockOff& b = blk[i];
-      b.conv_w = take((long long)H*Bn); b.conv_b = take(H);
-      b.dconv_w = take((long long)H*P); b.dconv_b = take(H);
-      if (i < nb - 1) { b.res_w = take((long long)Bn*H); b.res_b = take(Bn); }
-      else { b.res_w = -1; b.res_b = -1; }
-      b.skip_w = take((long long)Sc*H); b.skip_b = take(Sc);
-      b.n1_g = take(H); b.n1_b = take(H); b.n2_g = take(H); b.n2_b = take(H);
-      b.prelu1 = take(1); b.prelu2 = take(1);
-    }
-    tcn_prelu = take(1);
-    out_w = take((long long)S*N*Sc); out_b = take((long long)S*N);
-    n_params = o;
     // prepared bf16 operands
     long long q = 0;
     auto ptake = [&](long long n) { long long r = q; q += align_up(n, 128); return r; };
@@ -167,13 +137,6 @@ struct Layout {
     p_stamp = ptake(128);                              // mode stamp (one int): see mode_stamp()
     n_prepared = q;
     return 0;
-  }
-
-  long long frames(long long L) const {
-    long long pad = ((K - L) % hop + hop) % hop;      // Python modulo
-    long long Lp = L + pad;
-    if (Lp < K) return 0;
-    return (Lp - K)/hop + 1;
   }
 };
 
@@ -244,6 +207,56 @@ struct Workspace {
     }
     total = o;
   }
+};
+
+// Typed views of one call's buffers: the workspace (byte offsets in `ws`), the prepared operands and, for
+// the causal model, the identity operands and cLN tables. Every driver and stage below reads its pointers here.
+struct Views {
+  const Layout& l; Workspace ws; char* base; const bf16_t* prep; int B; long long T;
+  Views(const Layout& l_, void* workspace, const void* prepared, int B_, long long T_)
+      : l(l_), base((char*)workspace), prep((const bf16_t*)prepared), B(B_), T(T_) { ws.init(l, B, T); }
+  double BT() const { return (double)B*(double)T; }
+  int ldg() const { return l.Bnp + l.Scp; }                    // row stride of [g_out | g_skip]
+  bf16_t* bf(long long off) const { return (bf16_t*)(base + off); }
+  float* f32(long long off) const { return (float*)(base + off); }
+  // statistics / backward sums of norm i: 0 = input norm, then (1 + 2 blk, 2 + 2 blk) per block
+  double* stat(int i) const { return (double*)(base + ws.stats) + (long long)i*B*kStatStride; }
+  double* sum(int i) const { return (double*)(base + ws.sums) + (long long)i*B*kStatStride; }
+  bf16_t* w() const { return bf(ws.w); }
+  bf16_t* x(int i) const { return bf(ws.x + ws.x_stride*i); }
+  bf16_t* z1(int i) const { return bf(ws.z1 + ws.z_stride*i); }
+  bf16_t* z2(int i) const { return bf(ws.z2 + ws.z_stride*i); }
+  bf16_t* u(int i) const { return bf(ws.u + ws.u_stride*i); }
+  float* skip() const { return f32(ws.skip); }
+  bf16_t* m() const { return bf(ws.m); }
+  bf16_t* y() const { return bf(ws.y); }
+  bf16_t* dpre() const { return bf(ws.dpre); }
+  bf16_t* dw1() const { return bf(ws.dw1); }
+  bf16_t* gskip() const { return bf(ws.gskip); }
+  bf16_t* gout() const { return bf(ws.gout); }
+  bf16_t* eA() const { return bf(ws.eA); }
+  bf16_t* eB(int i) const { return bf(ws.eB + ws.eB_stride*i); }
+  bf16_t* gcopy(int i) const { return bf(ws.gcopy + ws.gcopy_stride*i); }
+  bf16_t* e0() const { return bf(ws.e0); }
+  bf16_t* dwt() const { return bf(ws.dwt); }
+  // replicated vector-gradient block: [ln gain, bias | per block | PReLU slopes: tcn, then (prelu1, prelu2) per block]
+  float* vg() const { return f32(ws.vg); }
+  float* vslot(int i) const { return vg() + 2LL*l.N + (long long)l.H*(5 + l.P)*i; }     // block i's vector grads
+  float* vslope() const { return vslot(l.nb); }
+  float* vscratch() const { return vslope() + 1 + 2*l.nb; }    // 2*Hp floats per replica, discarded (causal)
+  // causal model only
+  bf16_t* wn() const { return bf(ws.wn); }
+  bf16_t* h1(int i) const { return bf(ws.h1 + ws.z_stride*i); }
+  bf16_t* h2(int i) const { return bf(ws.h2 + ws.z_stride*i); }
+  long long cmax() const { return l.Hp > l.Np ? l.Hp : l.Np; }
+  float* ones() const { return f32(ws.ident); }
+  float* zeros() const { return ones() + cmax(); }
+  float* one() const { return zeros() + cmax(); }
+  double* fake_stats() const { return (double*)(base + ws.fake_stats); }
+  double* scratch_stats() const { return (double*)(base + ws.scratch_stats); }
+  float* cfs() const { return f32(ws.cfs); }
+  float* cbt() const { return f32(ws.cbt); }
+  float* tab(int i) const { return f32(ws.ctab + ws.ctab_stride*i); }
 };
 
 // ---------------------------------------------------------------------------
@@ -710,13 +723,13 @@ __global__ __launch_bounds__(256) void skip_combine_kernel(const SkipCombinePara
 
 // ===========================================================================
 // fold the replicated per-channel gradients into the flat gradient
-int reduce_vector_grads(const Layout& l, const Workspace& ws, const float* vg, float* grads,
-                        hipStream_t st, int blk_lo = 0, int blk_hi = 1 << 30, bool do_ln = true,
-                        bool do_tcn = true) {
+int reduce_vector_grads(const Views& v, float* grads, hipStream_t st, int blk_lo = 0, int blk_hi = 1 << 30,
+                        bool do_ln = true, bool do_tcn = true) {
+  const Layout& l = v.l;
   const long long vper = (long long)l.H*(5 + l.P);
   {
     VgradParams vp; memset(&vp, 0, sizeof(vp));
-    vp.vg = vg; vp.grads = grads; vp.rep_stride = ws.vg_stride;
+    vp.vg = v.vg(); vp.grads = grads; vp.rep_stride = v.ws.vg_stride;
     vp.N = l.N; vp.H = l.H; vp.P = l.P; vp.nb = l.nb;
     vp.ln_g_off = l.ln_g; vp.blk0_off = l.blk[0].conv_w;
     vp.blk_full = l.nb > 1 ? l.blk[1].conv_w - l.blk[0].conv_w : 0;
@@ -754,34 +767,26 @@ __global__ void fill_identity_kernel(float* ones, float* zeros, float* one, int 
   if (i < B) { fake_stats[stat_sum(i)] = 0.0; fake_stats[stat_sq(i)] = sumsq; }
 }
 
-struct CausalCtx {
-  float* ones; float* zeros; float* one; double* fake; double* scratch_stats;
-  float* cfs; float* cbt; char* ctab; long long ctab_stride;
-  float* tab(int i) const { return (float*)(ctab + ctab_stride*i); }
-};
+namespace {
 
-int causal_ctx(const Layout& l, const Workspace& ws, char* base, int B, long long T,
-               hipStream_t st, CausalCtx& c) {
-  const long long cmax = l.Hp > l.Np ? l.Hp : l.Np;
-  c.ones = (float*)(base + ws.ident); c.zeros = c.ones + cmax; c.one = c.zeros + cmax;
-  c.fake = (double*)(base + ws.fake_stats); c.scratch_stats = (double*)(base + ws.scratch_stats);
-  c.cfs = (float*)(base + ws.cfs); c.cbt = (float*)(base + ws.cbt);
-  c.ctab = base + ws.ctab; c.ctab_stride = ws.ctab_stride;
+// identity operands, fake statistics and zeroed scratch statistics of a causal call
+int causal_init(const Views& v, hipStream_t st) {
+  const Layout& l = v.l;
   // fake statistics with mean 0 and rstd 1 for n = T*H elements (var + eps = 1)
-  const double sumsq = (1.0 - (double)1e-8f)*(double)T*(double)l.H;
-  const int n = (int)cmax > B ? (int)cmax : B;
-  hipLaunchKernelGGL(fill_identity_kernel, dim3((n + 255)/256), dim3(256), 0, st, c.ones, c.zeros,
-                     c.one, (int)cmax, c.fake, B, sumsq);
+  const double sumsq = (1.0 - (double)1e-8f)*(double)v.T*(double)l.H;
+  const int cmax = (int)v.cmax(), n = cmax > v.B ? cmax : v.B;
+  hipLaunchKernelGGL(fill_identity_kernel, dim3((n + 255)/256), dim3(256), 0, st, v.ones(), v.zeros(),
+                     v.one(), cmax, v.fake_stats(), v.B, sumsq);
   BRV_HIP_OK(hipGetLastError());
-  BRV_HIP_OK(hipMemsetAsync(c.scratch_stats, 0, (size_t)B*kStatStride*8, st));
+  BRV_HIP_OK(hipMemsetAsync(v.scratch_stats(), 0, (size_t)v.B*kStatStride*8, st));
   return 0;
 }
 
-int cln_forward(const CausalCtx& cx, const bf16_t* z, const float* slope, const float* gain,
+int cln_forward(const Views& v, const bf16_t* z, const float* slope, const float* gain,
                 const float* bias, bf16_t* y, float* table, int B, long long T, int Cp, int C,
                 hipStream_t st) {
   ClnParams p; memset(&p, 0, sizeof(p));
-  p.z = z; p.slope = slope; p.y = y; p.fsum = cx.cfs; p.table = table; p.gain = gain;
+  p.z = z; p.slope = slope; p.y = y; p.fsum = v.cfs(); p.table = table; p.gain = gain;
   p.bias = bias; p.B = B; p.T = (int)T; p.Cp = Cp; p.C = C; p.eps = 1e-8f;
   ProfScope prof("cln_fwd", 0, 6.0*B*T*(double)Cp, st);
   hipLaunchKernelGGL(cln_frame_sums_kernel, dim3(ceil_div((int)T, CLN_FPB)*B), dim3(256), 0, st, p);
@@ -794,12 +799,12 @@ int cln_forward(const CausalCtx& cx, const bf16_t* z, const float* slope, const 
 }
 
 // dz = d(loss)/dz of y = cLN(PReLU(z)); norm-parameter gradients to the replicated block
-int cln_backward(const CausalCtx& cx, const bf16_t* g, const bf16_t* z, const float* slope,
+int cln_backward(const Views& v, const bf16_t* g, const bf16_t* z, const float* slope,
                  const float* gain, const float* fwd_table, bf16_t* dz, const bf16_t* add_in,
                  int n_add, float* dgain, float* dbias, float* dslope, long long rep_stride,
                  int B, long long T, int Cp, int C, hipStream_t st) {
   ClnParams p; memset(&p, 0, sizeof(p));
-  p.z = z; p.slope = slope; p.g = g; p.fsum = cx.cfs; p.table = cx.cbt; p.fwd_table = fwd_table;
+  p.z = z; p.slope = slope; p.g = g; p.fsum = v.cfs(); p.table = v.cbt(); p.fwd_table = fwd_table;
   p.gain = gain; p.B = B; p.T = (int)T; p.Cp = Cp; p.C = C; p.eps = 1e-8f;
   p.dz = dz; p.add_in = add_in; p.n_add = n_add;
   p.dgain = dgain; p.dbias = dbias; p.dslope = dslope; p.rep_stride = rep_stride;
@@ -813,227 +818,754 @@ int cln_backward(const CausalCtx& cx, const bf16_t* g, const bf16_t* z, const fl
   return 0;
 }
 
-int forward_causal(const Layout& l, const brv_ctn_config* cfg, const float* params,
-                   const void* prepared, void* workspace, const float* wave, long long wave_stride,
-                   float* out, int B, long long L, long long T, hipStream_t st) {
-  Workspace ws; ws.init(l, B, T);
-  const double BT = (double)B*(double)T;
-  char* base = (char*)workspace;
-  const bf16_t* prep = (const bf16_t*)prepared;
-  bf16_t* w = (bf16_t*)(base + ws.w);
-  bf16_t* wn = (bf16_t*)(base + ws.wn);
-  auto xbuf = [&](int i) { return (bf16_t*)(base + ws.x + ws.x_stride*i); };
-  auto z1buf = [&](int i) { return (bf16_t*)(base + ws.z1 + ws.z_stride*i); };
-  auto z2buf = [&](int i) { return (bf16_t*)(base + ws.z2 + ws.z_stride*i); };
-  auto h1buf = [&](int i) { return (bf16_t*)(base + ws.h1 + ws.z_stride*i); };
-  auto h2buf = [&](int i) { return (bf16_t*)(base + ws.h2 + ws.z_stride*i); };
-  float* skip = (float*)(base + ws.skip);
-  bf16_t* m = (bf16_t*)(base + ws.m);
-  bf16_t* y = (bf16_t*)(base + ws.y);
-  CausalCtx cx; if (int r = causal_ctx(l, ws, base, B, T, st, cx)) return r;
-  BRV_HIP_OK(hipMemsetAsync(out, 0, (size_t)B*l.S*L*sizeof(float), st));
+// ---- non-causal forward in stages (brv_ctn_forward): encoder and bottleneck, the blocks in the fused or in the
+// three-launch form, mask and decoder
+int forward_encoder(const Views& v, const float* params, const float* wave, long long wave_stride, float* out,
+                    long long L, hipStream_t st) {
+  const Layout& l = v.l; const int B = v.B; const long long T = v.T; const double BT = v.BT();
+  // statistics and output <- 0; operands prepared for the other mode -> NaN statistics (and with them a NaN
+  // output); then this call's mode stamped on the workspace
+  if (int r = launch_call_init(v.stat(0), (long long)(v.ws.stats_bytes/8), out, (long long)B*l.S*L*(long long)sizeof(float),
+                               reinterpret_cast<const int*>(v.prep + l.p_stamp), mode_stamp(l.fused_fwd()),
+                               reinterpret_cast<int*>(v.base + v.ws.stamp), mode_stamp(l.fused_fwd()), st))
+    return fail(r, "forward: call_init launch");
 
   GemmRowsParams g;
-  memset(&g, 0, sizeof(g));                                // encoder
-  g.a = frames_of(wave, L, l.hop, l.K, wave_stride);
-  g.W = prep + l.p_enc; g.T = (int)T; g.Np = l.Np; g.Kp = l.Kfp;
-  g.e.out = w; g.e.ldo = l.Np; g.e.N = l.N;
-  if (int r = launch_gemm_rows<A_FRAMES, E_STORE>(g, B, st, "enc_fwd", 4.0*B*L + 2.0*BT*l.Np)) return r;
-  // cLN of the encoder output, bottleneck conv
-  if (int r = cln_forward(cx, w, nullptr, params + l.ln_g, params + l.ln_b, wn, cx.tab(0), B, T,
-                          l.Np, l.N, st)) return r;
+  // encoder: framed filterbank analysis, statistics for the first gLN
   memset(&g, 0, sizeof(g));
-  g.a = rows_bf16(wn, l.Np, T);
-  g.W = prep + l.p_bott_f; g.T = (int)T; g.Np = l.Bnp; g.Kp = l.Np;
-  g.e.out = xbuf(0); g.e.ldo = l.Bnp; g.e.bias = params + l.bott_b; g.e.N = l.Bn;
+  g.a = frames_of(wave, L, l.hop, l.K, wave_stride);
+  g.W = v.prep + l.p_enc; g.T = (int)T; g.Np = l.Np; g.Kp = l.Kfp;
+  g.e.out = v.w(); g.e.ldo = l.Np; g.e.N = l.N; g.e.stats_out = v.stat(0);
+  if (int r = launch_gemm_rows<A_FRAMES, E_STORE>(g, B, st, "enc_fwd", 4.0*B*L + 2.0*BT*l.Np)) return r;
+  // bottleneck 1x1 conv on gLN(w)
+  memset(&g, 0, sizeof(g));
+  g.a = rows_bf16(v.w(), l.Np, T);
+  set_affine(g.a, v.stat(0), params + l.ln_g, params + l.ln_b, l.N, T);
+  g.W = v.prep + l.p_bott_f; g.T = (int)T; g.Np = l.Bnp; g.Kp = l.Np;
+  g.e.out = v.x(0); g.e.ldo = l.Bnp; g.e.bias = params + l.bott_b; g.e.N = l.Bn;
   if (int r = launch_gemm_rows<A_BF16, E_STORE>(g, B, st, "bottleneck_fwd", 2.0*BT*(l.Np + l.Bnp))) return r;
+  return 0;
+}
 
-  for (int i = 0; i < l.nb; ++i) {
-    const BlockOff& b = l.blk[i];
-    const bool has_res = i < l.nb - 1;
-    const int dil = 1 << (i % cfg->layers);
-    memset(&g, 0, sizeof(g));                              // 1x1 conv Bn -> H
-    g.a = rows_bf16(xbuf(i), l.Bnp, T);
-    g.W = prep + b.p_c1_f; g.T = (int)T; g.Np = l.Hp; g.Kp = l.Bnp;
-    g.e.out = z1buf(i); g.e.ldo = l.Hp; g.e.bias = params + b.conv_b; g.e.N = l.H;
-    if (int r = launch_gemm_rows<A_BF16, E_STORE>(g, B, st, "pw1_fwd", 2.0*BT*(l.Bnp + l.Hp))) return r;
-    if (int r = cln_forward(cx, z1buf(i), params + b.prelu1, params + b.n1_g, params + b.n1_b,
-                            h1buf(i), cx.tab(1 + 2*i), B, T, l.Hp, l.H, st)) return r;
-    // depthwise dilated conv on h1, all padding on the left (convtasnet.py:244-247)
-    DwParams d; memset(&d, 0, sizeof(d));
-    d.z1 = h1buf(i); d.z2 = z2buf(i); d.B = B; d.T = (int)T; d.Cp = l.Hp; d.C = l.H;
-    d.slope1 = cx.one; d.stats1 = cx.fake; d.gamma1 = cx.ones; d.beta1 = cx.zeros;
-    d.inv_n = 1.0/((double)T*l.H); d.eps = 1e-8f;
-    d.taps = params + b.dconv_w; d.bias = params + b.dconv_b;
-    d.dil = dil; d.left = (l.P - 1)*dil;
-    d.stats2 = cx.scratch_stats; d.slope2 = cx.one;
-    if (int r = dispatch_p<DwFwd>(l.P, d, st)) return r;
-    if (int r = cln_forward(cx, z2buf(i), params + b.prelu2, params + b.n2_g, params + b.n2_b,
-                            h2buf(i), cx.tab(2 + 2*i), B, T, l.Hp, l.H, st)) return r;
-    memset(&g, 0, sizeof(g));                              // [res | skip] 1x1 convs
-    g.a = rows_bf16(h2buf(i), l.Hp, T);
-    const int rs0 = has_res ? l.Bnp : 0;
-    g.W = prep + b.p_rs_f; g.T = (int)T; g.Np = rs0 + l.Scp; g.Kp = l.Hp;
-    g.e.out = has_res ? xbuf(i + 1) : nullptr; g.e.ldo = l.Bnp;
-    g.e.bias = has_res ? params + b.res_b : nullptr; g.e.N = has_res ? l.Bn : 0;
-    g.e.Nsplit = rs0; g.e.bias2 = params + b.skip_b; g.e.N2 = l.Sc;
-    g.e.res_in = xbuf(i); g.e.ld_res = l.Bnp;
-    g.e.skip = skip; g.e.ld_skip = l.Scp; g.e.skip_init = (i == 0);
-    if (int r = launch_gemm_rows<A_BF16, E_RES_SKIP>(g, B, st, "pw2_fwd", 2.0*BT*(l.Hp + l.Bnp + rs0) + 4.0*BT*l.Scp*(i == 0 ? 1 : 2))) return r;
+// one block of the fused forward: pw1_fwd (finishes the block input lazily), then dwpw2_fwd
+int forward_block_fused(const Views& v, const float* params, int i, hipStream_t st) {
+  const Layout& l = v.l; const int B = v.B; const long long T = v.T; const double BT = v.BT();
+  const int NPu = l.Bnp + l.Scp;
+  GemmRowsParams g;
+  const BlockOff& b = l.blk[i];
+  const int dil = 1 << (i % l.layers);
+  memset(&g, 0, sizeof(g));
+  g.W = v.prep + b.p_c1_f; g.T = (int)T; g.Np = l.Hp; g.Kp = l.Bnp;
+  g.Wp = v.prep + b.p_c1_fp; g.wp_nsl = 64;
+  g.e.out = v.z1(i); g.e.ldo = l.Hp; g.e.bias = params + b.conv_b; g.e.N = l.H;
+  g.e.stats_out = v.stat(1 + 2*i); g.e.stats_slope = params + b.prelu1;
+  if (i == 0) {
+    g.a = rows_bf16(v.x(0), l.Bnp, T);
+    ProfScope prof("pw1_fwd", 2.0*BT*l.Hp*l.Bnp, 2.0*BT*(l.Bnp + l.Hp), st);
+    if (int r = launch_gemm_ws<128, 64, 1, E_STORE, 0, false, 8>(g, B, st)) return r;
+  } else {
+    const BlockOff& pb = l.blk[i - 1];
+    g.a = rows_bf16(v.x(i - 1), l.Bnp, T);
+    g.a.p1 = v.u(i - 1); g.a.ld1 = NPu; g.a.bs1 = T*NPu;
+    g.a.xout = v.x(i);
+    g.a.stats = v.stat(2 + 2*(i - 1)); g.a.inv_n = 1.0/((double)T*l.H); g.a.eps = 1e-8f;
+    const float* lz = reinterpret_cast<const float*>(v.prep + pb.p_lazy);
+    g.a.lazy_v0 = lz; g.a.lazy_v1 = lz + NPu;
+    ProfScope prof("pw1_fwd", 2.0*BT*l.Hp*l.Bnp, 2.0*BT*(3*l.Bnp + l.Hp), st);
+#ifndef PW1F_NSL
+#define PW1F_NSL 64
+#define PW1F_WM 1
+#endif
+    if (int r = launch_gemm_ws<128, PW1F_NSL, PW1F_WM, E_STORE, 2, false, 8>(g, B, st)) return r;
   }
-  memset(&g, 0, sizeof(g));                                // prelu -> output conv -> mask
-  g.a = rows_bf16(skip, l.Scp, T);
+  memset(&g, 0, sizeof(g));
+  g.a = rows_bf16(v.z1(i), l.Hp, T);
+  g.a.slope = params + b.prelu1; g.a.stats = v.stat(1 + 2*i);
+  g.a.gamma = params + b.n1_g; g.a.beta = params + b.n1_b; g.a.C = l.H;
+  g.a.inv_n = 1.0/((double)T*l.H); g.a.eps = 1e-8f;
+  g.a.z2out = v.z2(i); g.a.taps = params + b.dconv_w; g.a.dbias = params + b.dconv_b;
+  g.a.slope2 = params + b.prelu2; g.a.stats2_out = v.stat(2 + 2*i);
+  g.a.dil = dil; g.a.left = ((l.P - 1)*dil)/2;
+  g.W = v.prep + b.p_rs_g; g.Wp = v.prep + b.p_rs_gp; g.wp_nsl = 32;
+  g.T = (int)T; g.Np = NPu; g.Kp = l.Hp;
+  g.e.out = v.u(i); g.e.ldo = NPu; g.e.N = NPu;
+  {
+    ProfScope prof("dwpw2_fwd", 2.0*BT*l.Hp*(NPu + l.P), 2.0*BT*(2*l.Hp + NPu), st);
+    const bool old_stage = opt(BRV_OPT_DWPW2_WS);         // first version of the stage (gemm_ws.cuh AT == 3)
+    if (old_stage || l.Hp != DP_H || NPu != DP_N) {
+      if (int r = launch_gemm_ws<512, 32, 1, E_STORE, 3, false, 8>(g, B, st)) return r;
+    } else {
+      DwPw2Params dp; memset(&dp, 0, sizeof(dp));
+      dp.z1 = v.z1(i); dp.z2 = v.z2(i); dp.u = v.u(i);
+      dp.Wp = v.prep + b.p_rs_gp;
+      dp.slope1 = params + b.prelu1; dp.slope2 = params + b.prelu2;
+      dp.stats1 = v.stat(1 + 2*i); dp.stats2 = v.stat(2 + 2*i);
+      dp.gamma1 = params + b.n1_g; dp.beta1 = params + b.n1_b;
+      dp.taps = params + b.dconv_w; dp.dbias = params + b.dconv_b;
+      dp.B = B; dp.T = (int)T; dp.dil = dil; dp.left = ((l.P - 1)*dil)/2; dp.C = l.H;
+      dp.inv_n = 1.0/((double)T*l.H); dp.eps = 1e-8f;
+      const int n_tiles = B*(int)((T + DP_TT - 1)/DP_TT);
+      // (a multiple of 8 workgroups: the kernel deals the tiles to the 8 XCDs in equal runs of slots)
+      const int cap = num_cus() >= 8 ? num_cus()/8*8 : 8;
+      // (one workgroup per tile for the half-batch launches of the two-chain step -- 256 tiles on 256 instead of 224
+      // workgroups, so that none walks two tiles -- measured no change: 6.49 ms either way, profiles/r05_dwpw2_ablation.txt)
+      const int n_wg = n_tiles < cap ? (n_tiles + 7)/8*8 : cap;
+      hipLaunchKernelGGL(dwpw2_fused_kernel, dim3(n_wg), dim3(512), 0, st, dp);
+      BRV_HIP_OK(hipGetLastError());
+    }
+  }
+  return 0;
+}
+
+// the skip connections of all blocks of the fused forward, finished in one pass
+int forward_skip_combine(const Views& v, hipStream_t st) {
+  const Layout& l = v.l; const int B = v.B; const long long T = v.T; const double BT = v.BT();
+  SkipCombineParams sc; memset(&sc, 0, sizeof(sc));
+  sc.u = v.u(0); sc.u_stride = v.ws.u_stride/2; sc.stats = v.stat(0); sc.stats_stride = (long long)B*kStatStride;
+  sc.prepared = v.prep; sc.skip = v.skip(); sc.nb = l.nb; sc.B = B; sc.T = (int)T; sc.Bnp = l.Bnp; sc.Scp = l.Scp;
+  sc.inv_n = 1.0/((double)T*l.H); sc.eps = 1e-8f;
+  for (int i = 0; i < l.nb; ++i) sc.lazy_off[i] = l.blk[i].p_lazy;
+  {
+    ProfScope prof("skip_combine", 0, 2.0*BT*l.Scp*l.nb + 4.0*BT*l.Scp, st);
+    int gx = (int)((T*(l.Scp/8) + 255)/256);
+    if (gx > 128) gx = 128;      // (64 / 32 / 16: 136 - 137 us as well, round 5: not the per-workgroup prologue)
+    hipLaunchKernelGGL(skip_combine_kernel, dim3(gx, B), dim3(256), 0, st, sc);
+    BRV_HIP_OK(hipGetLastError());
+  }
+  return 0;
+}
+
+// one block of the three-launch forward
+int forward_block_plain(const Views& v, const float* params, int i, hipStream_t st) {
+  const Layout& l = v.l; const int B = v.B; const long long T = v.T; const double BT = v.BT();
+  GemmRowsParams g;
+  const BlockOff& b = l.blk[i];
+  const bool has_res = i < l.nb - 1;
+  const int dil = 1 << (i % l.layers);
+  // 1x1 conv Bn -> H (+ statistics of prelu_1 output)
+  memset(&g, 0, sizeof(g));
+  g.a = rows_bf16(v.x(i), l.Bnp, T);
+  g.W = v.prep + b.p_c1_f; g.T = (int)T; g.Np = l.Hp; g.Kp = l.Bnp;
+  g.Wp = v.prep + b.p_c1_fp; g.wp_nsl = 64;
+  g.e.out = v.z1(i); g.e.ldo = l.Hp; g.e.bias = params + b.conv_b; g.e.N = l.H;
+  g.e.stats_out = v.stat(1 + 2*i); g.e.stats_slope = params + b.prelu1;
+  if (int r = launch_gemm_rows<A_BF16, E_STORE>(g, B, st, "pw1_fwd", 2.0*BT*(l.Bnp + l.Hp))) return r;
+  // prelu_1 -> gLN -> depthwise dilated conv (+ statistics of prelu_2 output)
+  DwParams d; memset(&d, 0, sizeof(d));
+  d.z1 = v.z1(i); d.z2 = v.z2(i); d.B = B; d.T = (int)T; d.Cp = l.Hp; d.C = l.H;
+  d.slope1 = params + b.prelu1; d.stats1 = v.stat(1 + 2*i);
+  d.gamma1 = params + b.n1_g; d.beta1 = params + b.n1_b;
+  d.inv_n = 1.0/((double)T*l.H); d.eps = 1e-8f;
+  d.taps = params + b.dconv_w; d.bias = params + b.dconv_b;
+  d.dil = dil; d.left = ((l.P - 1)*dil)/2;
+  d.stats2 = v.stat(2 + 2*i); d.slope2 = params + b.prelu2;
+  if (int r = dispatch_p<DwFwd>(l.P, d, st)) return r;
+  // prelu_2 -> gLN -> [res | skip] 1x1 convs, residual add, skip accumulation
+  memset(&g, 0, sizeof(g));
+  g.a = rows_bf16(v.z2(i), l.Hp, T);
+  g.a.slope = params + b.prelu2;
+  set_affine(g.a, v.stat(2 + 2*i), params + b.n2_g, params + b.n2_b, l.H, T);
+  const int rs0 = has_res ? l.Bnp : 0;
+  g.W = v.prep + b.p_rs_f; g.T = (int)T; g.Np = rs0 + l.Scp; g.Kp = l.Hp;
+  g.Wp = v.prep + b.p_rs_fp; g.wp_nsl = 32;
+  g.e.out = has_res ? v.x(i + 1) : nullptr; g.e.ldo = l.Bnp;
+  g.e.bias = has_res ? params + b.res_b : nullptr; g.e.N = has_res ? l.Bn : 0;
+  g.e.Nsplit = rs0; g.e.bias2 = params + b.skip_b; g.e.N2 = l.Sc;
+  g.e.res_in = v.x(i); g.e.ld_res = l.Bnp;
+  g.e.skip = v.skip(); g.e.ld_skip = l.Scp; g.e.skip_init = (i == 0);
+  if (int r = launch_gemm_rows<A_BF16, E_RES_SKIP>(g, B, st, "pw2_fwd", 2.0*BT*(l.Hp + l.Bnp + rs0) + 4.0*BT*l.Scp*(i == 0 ? 1 : 2))) return r;
+  return 0;
+}
+
+int forward_decoder(const Views& v, const float* params, float* out, long long L, hipStream_t st) {
+  const Layout& l = v.l; const int B = v.B; const long long T = v.T; const double BT = v.BT();
+  GemmRowsParams g;
+  // prelu -> output 1x1 conv -> sigmoid -> mask * encoder output
+  memset(&g, 0, sizeof(g));
+  g.a = rows_bf16(v.skip(), l.Scp, T);
   g.a.slope = params + l.tcn_prelu;
-  g.W = prep + l.p_out_f; g.T = (int)T; g.Np = l.S*l.Np; g.Kp = l.Scp;
-  g.e.out = y; g.e.ldo = l.Np; g.e.bias = params + l.out_b; g.e.N = l.N;
-  g.e.w_in = w; g.e.ld_w = l.Np; g.e.m_out = m; g.e.S = l.S; g.e.Np_src = l.Np;
+  g.W = v.prep + l.p_out_f; g.T = (int)T; g.Np = l.S*l.Np; g.Kp = l.Scp;
+  g.e.out = v.y(); g.e.ldo = l.Np; g.e.bias = params + l.out_b; g.e.N = l.N;
+  g.e.w_in = v.w(); g.e.ld_w = l.Np; g.e.m_out = v.m(); g.e.S = l.S; g.e.Np_src = l.Np;
   if (int r = launch_gemm_rows<A_F32, E_MASK>(g, B, st, "mask_fwd", 4.0*BT*l.Scp + 2.0*BT*l.Np*(1 + 2*l.S))) return r;
-  memset(&g, 0, sizeof(g));                                // decoder
-  g.a = rows_bf16(y, l.Np, T);
-  g.W = prep + l.p_dec_f; g.T = (int)T; g.Np = l.Kfp; g.Kp = l.Np;
+  // decoder: synthesis filterbank + overlap-add, cropped to the input length
+  memset(&g, 0, sizeof(g));
+  g.a = rows_bf16(v.y(), l.Np, T);
+  g.W = v.prep + l.p_dec_f; g.T = (int)T; g.Np = l.Kfp; g.Kp = l.Np;
   g.e.wave_out = out; g.e.hop = l.hop; g.e.Kf = l.K; g.e.wave_stride = L;
   g.e.wave_len = (int)L;
   if (int r = launch_gemm_rows<A_BF16, E_OLA>(g, B*l.S, st, "dec_fwd", 2.0*BT*l.S*l.Np + 4.0*B*l.S*L)) return r;
   return 0;
 }
 
-int backward_causal(const Layout& l, const brv_ctn_config* cfg, const float* params,
-                    const void* prepared, void* workspace, const float* wave, long long wave_stride,
-                    const float* d_out, float* grads, int B, long long L, long long T, hipStream_t st) {
-  Workspace ws; ws.init(l, B, T);
-  const double BT = (double)B*(double)T;
-  char* base = (char*)workspace;
-  const bf16_t* prep = (const bf16_t*)prepared;
-  bf16_t* w = (bf16_t*)(base + ws.w);
-  bf16_t* wn = (bf16_t*)(base + ws.wn);
-  auto xbuf = [&](int i) { return (bf16_t*)(base + ws.x + ws.x_stride*i); };
-  auto z1buf = [&](int i) { return (bf16_t*)(base + ws.z1 + ws.z_stride*i); };
-  auto z2buf = [&](int i) { return (bf16_t*)(base + ws.z2 + ws.z_stride*i); };
-  auto h1buf = [&](int i) { return (bf16_t*)(base + ws.h1 + ws.z_stride*i); };
-  auto h2buf = [&](int i) { return (bf16_t*)(base + ws.h2 + ws.z_stride*i); };
-  float* skip = (float*)(base + ws.skip);
-  bf16_t* m = (bf16_t*)(base + ws.m);
-  bf16_t* y = (bf16_t*)(base + ws.y);
-  bf16_t* dpre = (bf16_t*)(base + ws.dpre);
-  bf16_t* dw1 = (bf16_t*)(base + ws.dw1);
-  bf16_t* gskip = (bf16_t*)(base + ws.gskip);
-  bf16_t* gout = (bf16_t*)(base + ws.gout);
-  const int ldg = l.Bnp + l.Scp;
-  bf16_t* eA = (bf16_t*)(base + ws.eA);
-  bf16_t* eB = (bf16_t*)(base + ws.eB);
-  bf16_t* e0 = (bf16_t*)(base + ws.e0);
-  bf16_t* dwt = (bf16_t*)(base + ws.dwt);
-  const int BS = B*l.S;
-  float* vg = (float*)(base + ws.vg);
-  const long long vper = (long long)l.H*(5 + l.P);
-  auto vslot = [&](int i) { return vg + 2LL*l.N + vper*i; };
-  float* vslope = vg + 2LL*l.N + vper*l.nb;
-  float* vscratch = vslope + 1 + 2*l.nb;                   // 2*Hp floats per replica, discarded
-  CausalCtx cx; if (int r = causal_ctx(l, ws, base, B, T, st, cx)) return r;
-  BRV_HIP_OK(hipMemsetAsync(vg, 0, ws.vg_bytes, st));
+int forward_causal(const Views& v, const float* params, const float* wave, long long wave_stride, float* out,
+                   long long L, hipStream_t st) {
+  const Layout& l = v.l; const int B = v.B; const long long T = v.T; const double BT = v.BT();
+  if (int r = causal_init(v, st)) return r;
+  BRV_HIP_OK(hipMemsetAsync(out, 0, (size_t)B*l.S*L*sizeof(float), st));
 
-  GemmRowsParams g; WgradParams wg;
-  memset(&g, 0, sizeof(g));                                // decoder data gradient + mask backward
+  GemmRowsParams g;
+  memset(&g, 0, sizeof(g));                                // encoder
+  g.a = frames_of(wave, L, l.hop, l.K, wave_stride);
+  g.W = v.prep + l.p_enc; g.T = (int)T; g.Np = l.Np; g.Kp = l.Kfp;
+  g.e.out = v.w(); g.e.ldo = l.Np; g.e.N = l.N;
+  if (int r = launch_gemm_rows<A_FRAMES, E_STORE>(g, B, st, "enc_fwd", 4.0*B*L + 2.0*BT*l.Np)) return r;
+  // cLN of the encoder output, bottleneck conv
+  if (int r = cln_forward(v, v.w(), nullptr, params + l.ln_g, params + l.ln_b, v.wn(), v.tab(0), B, T,
+                          l.Np, l.N, st)) return r;
+  memset(&g, 0, sizeof(g));
+  g.a = rows_bf16(v.wn(), l.Np, T);
+  g.W = v.prep + l.p_bott_f; g.T = (int)T; g.Np = l.Bnp; g.Kp = l.Np;
+  g.e.out = v.x(0); g.e.ldo = l.Bnp; g.e.bias = params + l.bott_b; g.e.N = l.Bn;
+  if (int r = launch_gemm_rows<A_BF16, E_STORE>(g, B, st, "bottleneck_fwd", 2.0*BT*(l.Np + l.Bnp))) return r;
+
+  for (int i = 0; i < l.nb; ++i) {
+    const BlockOff& b = l.blk[i];
+    const bool has_res = i < l.nb - 1;
+    const int dil = 1 << (i % l.layers);
+    memset(&g, 0, sizeof(g));                              // 1x1 conv Bn -> H
+    g.a = rows_bf16(v.x(i), l.Bnp, T);
+    g.W = v.prep + b.p_c1_f; g.T = (int)T; g.Np = l.Hp; g.Kp = l.Bnp;
+    g.e.out = v.z1(i); g.e.ldo = l.Hp; g.e.bias = params + b.conv_b; g.e.N = l.H;
+    if (int r = launch_gemm_rows<A_BF16, E_STORE>(g, B, st, "pw1_fwd", 2.0*BT*(l.Bnp + l.Hp))) return r;
+    if (int r = cln_forward(v, v.z1(i), params + b.prelu1, params + b.n1_g, params + b.n1_b,
+                            v.h1(i), v.tab(1 + 2*i), B, T, l.Hp, l.H, st)) return r;
+    // depthwise dilated conv on h1, all padding on the left (convtasnet.py:244-247)
+    DwParams d; memset(&d, 0, sizeof(d));
+    d.z1 = v.h1(i); d.z2 = v.z2(i); d.B = B; d.T = (int)T; d.Cp = l.Hp; d.C = l.H;
+    d.slope1 = v.one(); d.stats1 = v.fake_stats(); d.gamma1 = v.ones(); d.beta1 = v.zeros();
+    d.inv_n = 1.0/((double)T*l.H); d.eps = 1e-8f;
+    d.taps = params + b.dconv_w; d.bias = params + b.dconv_b;
+    d.dil = dil; d.left = (l.P - 1)*dil;
+    d.stats2 = v.scratch_stats(); d.slope2 = v.one();
+    if (int r = dispatch_p<DwFwd>(l.P, d, st)) return r;
+    if (int r = cln_forward(v, v.z2(i), params + b.prelu2, params + b.n2_g, params + b.n2_b,
+                            v.h2(i), v.tab(2 + 2*i), B, T, l.Hp, l.H, st)) return r;
+    memset(&g, 0, sizeof(g));                              // [res | skip] 1x1 convs
+    g.a = rows_bf16(v.h2(i), l.Hp, T);
+    const int rs0 = has_res ? l.Bnp : 0;
+    g.W = v.prep + b.p_rs_f; g.T = (int)T; g.Np = rs0 + l.Scp; g.Kp = l.Hp;
+    g.e.out = has_res ? v.x(i + 1) : nullptr; g.e.ldo = l.Bnp;
+    g.e.bias = has_res ? params + b.res_b : nullptr; g.e.N = has_res ? l.Bn : 0;
+    g.e.Nsplit = rs0; g.e.bias2 = params + b.skip_b; g.e.N2 = l.Sc;
+    g.e.res_in = v.x(i); g.e.ld_res = l.Bnp;
+    g.e.skip = v.skip(); g.e.ld_skip = l.Scp; g.e.skip_init = (i == 0);
+    if (int r = launch_gemm_rows<A_BF16, E_RES_SKIP>(g, B, st, "pw2_fwd", 2.0*BT*(l.Hp + l.Bnp + rs0) + 4.0*BT*l.Scp*(i == 0 ? 1 : 2))) return r;
+  }
+  return forward_decoder(v, params, out, L, st);      // prelu -> output conv -> mask, decoder: as the non-causal model
+}
+
+// ---- deferred weight gradients of blocks [blk_lo, blk_hi] (the data-gradient chain of these blocks has run on
+// a stream this one is ordered after)
+// problem of block i in a [res | skip] launch: G = [g_out_i | g_skip], H = gLN_2(prelu_2(z2_i))
+void wgrad_rs_prob(const Views& v, const float* params, float* grads, int i, WgradProb& pr) {
+  const BlockOff& b = v.l.blk[i];
+  const bool has_res = i < v.l.nb - 1;
+  pr.g0 = has_res ? v.gcopy(i) : nullptr; pr.g1 = v.gskip(); pr.h = v.z2(i);
+  pr.out0 = has_res ? grads + b.res_w : nullptr; pr.out1 = grads + b.skip_w;
+  pr.gbias0 = has_res ? grads + b.res_b : nullptr; pr.gbias1 = grads + b.skip_b;
+  pr.slope = params + b.prelu2; pr.stats = v.stat(2 + 2*i);
+  pr.gamma = params + b.n2_g; pr.beta = params + b.n2_b;
+}
+
+// residual / skip convs of every block in ONE launch (gemm_wgrad_full.cuh)
+int wgrad_rs_full(const Views& v, const float* params, float* grads, int blk_lo, int blk_hi, hipStream_t st) {
+  const Layout& l = v.l; const int B = v.B; const long long T = v.T; const double BT = v.BT();
+  const int ldg = v.ldg();
+  WgradFullParams fp; memset(&fp, 0, sizeof(fp));
+  const int nblk = blk_hi - blk_lo + 1;
+  fp.B = B; fp.T = (int)T; fp.nprob = nblk; fp.n_htiles = l.Hp/W2_BH;
+  fp.ldg0 = l.Bnp; fp.bsg0 = T*l.Bnp; fp.ldg1 = ldg; fp.bsg1 = T*ldg;
+  fp.ldh = l.Hp; fp.bsh = T*l.Hp;
+  fp.N0 = l.Bn; fp.N1 = l.Sc; fp.Kout = l.H; fp.ldo = l.H;
+  fp.inv_n = 1.0/((double)T*l.H); fp.eps = 1e-8f;
+  for (int i = blk_lo; i <= blk_hi; ++i) wgrad_rs_prob(v, params, grads, i, fp.prob[i - blk_lo]);
+  ProfScope prof("pw2_wgrad", 2.0*nblk*BT*(double)(l.Bnp + l.Scp)*l.Hp,
+                 2.0*BT*(l.Bnp + l.Scp + l.Hp)*nblk, st);
+#ifdef BRV_DIAG
+  if (const char* d = getenv("BRV_DBG_WG")) fp.dbg = atoi(d);
+#endif
+  // 24 blocks x 8 H slices = 192 owners would leave a quarter of the CUs idle: the items are
+  // divided over kWgSplit workgroups each (768 = 3 full rounds) when the batch allows
+  fp.n_split = (B >= kWgSplit && !opt(BRV_OPT_NO_WGRAD_SPLIT)) ? kWgSplit : 1;
+  fp.part = reinterpret_cast<float*>(v.base + v.ws.wgpart);
+  const bool wide = !opt(BRV_OPT_NO_WGRAD_128) && l.Hp % W3_BH == 0;
+  if (wide) {
+    // 128 H channels per workgroup: 24 blocks x 4 slices; 8 item splits at the whole batch (768 workgroups), 4
+    // when this call is one of two half-batch chains (384 each)
+    fp.n_htiles = l.Hp/W3_BH;
+    if (fp.n_split > 1 && B >= 4*kWgSplit) fp.n_split = 2*kWgSplit;
+    const int grid = 8*ceil_div(nblk, 8)*fp.n_htiles*fp.n_split;
+    hipLaunchKernelGGL(wgrad_full128_kernel, dim3(grid), dim3(64*W2_NW), 0, st, fp);
+  } else {
+    const int grid = 8*ceil_div(nblk, 8)*fp.n_htiles*fp.n_split;
+    hipLaunchKernelGGL(wgrad_full_kernel, dim3(grid), dim3(64*W2_NW), 0, st, fp);
+  }
+  if (fp.n_split > 1)
+    hipLaunchKernelGGL(wgrad_full_reduce_kernel, dim3(128, (unsigned)nblk), dim3(256), 0, st, fp);
+  BRV_HIP_OK(hipGetLastError());
+  return 0;
+}
+
+// [res | skip] weight gradients of blocks [i0, i0 + n), generic widths
+int wgrad_rs_grouped(const Views& v, const float* params, float* grads, int i0, int n, hipStream_t st) {
+  const Layout& l = v.l; const int B = v.B; const long long T = v.T; const double BT = v.BT();
+  const int ldg = v.ldg(); WgradParams wg;
+  // [res | skip]: G = [g_out_i | g_skip], H = gLN_2(prelu_2(z2_i)); the last block has
+  // no residual conv, so it goes in a launch of its own (different G width)
+  WgradGroupParams gp; memset(&gp, 0, sizeof(gp));
+  WgradParams& q = gp.base;
+  q.g = rows_bf16(nullptr, l.Bnp, T); q.g.K0 = l.Bnp;
+  q.g.ld1 = ldg; q.g.bs1 = T*ldg;
+  q.h = rows_bf16(nullptr, l.Hp, T);
+  set_affine(q.h, nullptr, nullptr, nullptr, l.H, T);
+  q.B = B; q.T = (int)T; q.Gp = l.Bnp + l.Scp; q.Hp = l.Hp;
+  q.G0p = l.Bnp; q.N0 = l.Bn; q.N1 = l.Sc; q.Kout = l.H; q.ldo = l.H;
+  int np = 0;
+  for (int i = i0; i < i0 + n; ++i)
+    if (i != l.nb - 1) wgrad_rs_prob(v, params, grads, i, gp.prob[np++]);
+  gp.nprob = np;
+  if (np > 0)
+    if (int r = launch_wgrad_group<A_BF16>(gp, st, "pw2_wgrad",
+                                           2.0*BT*(l.Bnp + l.Scp + l.Hp))) return r;
+  if (i0 + n == l.nb) {             // last block: skip conv only
+    const BlockOff& b = l.blk[l.nb - 1];
+    memset(&wg, 0, sizeof(wg));
+    wg.g = rows_bf16(v.gskip(), ldg, T);
+    wg.h = rows_bf16(v.z2(l.nb - 1), l.Hp, T); wg.h.slope = params + b.prelu2;
+    set_affine(wg.h, v.stat(2 + 2*(l.nb - 1)), params + b.n2_g, params + b.n2_b, l.H, T);
+    wg.B = B; wg.T = (int)T; wg.Gp = l.Scp; wg.Hp = l.Hp;
+    wg.out1 = grads + b.skip_w; wg.G0p = 0; wg.N0 = 0; wg.N1 = l.Sc;
+    wg.Kout = l.H; wg.ldo = l.H; wg.gbias1 = grads + b.skip_b;
+    if (int r = launch_wgrad<A_BF16>(wg, st, "pw2_wgrad", 2.0*BT*(l.Scp + l.Hp))) return r;
+  }
+  return 0;
+}
+
+// first 1x1 conv weight gradients of blocks [i0, i0 + n): one grouped launch
+int wgrad_pw1(const Views& v, const float* params, float* grads, int i0, int n, hipStream_t st) {
+  const Layout& l = v.l; const int B = v.B; const long long T = v.T; const double BT = v.BT();
+  WgradGroupParams gp;
+  // first 1x1 conv: G = dz1_i, H = x_i
+  memset(&gp, 0, sizeof(gp));
+  WgradParams& q1 = gp.base;
+  q1.g = rows_bf16(nullptr, l.Hp, T); q1.h = rows_bf16(nullptr, l.Bnp, T);
+  q1.B = B; q1.T = (int)T; q1.Gp = l.Hp; q1.Hp = l.Bnp;
+  q1.G0p = l.Hp; q1.N0 = l.H; q1.Kout = l.Bn; q1.ldo = l.Bn;
+  for (int i = i0; i < i0 + n; ++i) {
+    const BlockOff& b = l.blk[i];
+    WgradProb& pr = gp.prob[i - i0];
+    pr.g0 = v.eB(i); pr.h = v.x(i);
+    pr.out0 = grads + b.conv_w; pr.gbias0 = grads + b.conv_b;
+  }
+  gp.nprob = n;
+  if (l.pw1_rc() && pw1_rc_wgrad()) {
+    // dz1 was never written: rebuilt from e1 (kept per block in eB) and x inside the product
+    Pw1WgradRcParams rp; memset(&rp, 0, sizeof(rp));
+    rp.B = B; rp.T = (int)T; rp.nprob = n; rp.C = l.H; rp.Kout = l.Bn; rp.ldo = l.Bn;
+    rp.lde = l.Hp; rp.ldx = l.Bnp; rp.bse = T*l.Hp; rp.bsx = T*l.Bnp;
+    rp.inv_n = 1.0/((double)T*l.H); rp.eps = 1e-8f;
+    for (int i = i0; i < i0 + n; ++i) {
+      const BlockOff& b = l.blk[i];
+      Pw1WgradRcProb& pr = rp.prob[i - i0];
+      pr.e1 = v.eB(i); pr.x = v.x(i); pr.Wfp = v.prep + b.p_c1_fp; pr.bias = params + b.conv_b;
+      pr.out = grads + b.conv_w; pr.gbias = grads + b.conv_b;
+      pr.stats = v.stat(1 + 2*i); pr.sums = v.sum(1 + 2*i); pr.slope = params + b.prelu1;
+    }
+    const int tiles = l.Hp/WG_BG;
+    int ns = B;                                  // item-aligned splits (as the stored-dz1 launch)
+    while (tiles*n*ns > 2048 && ns % 2 == 0) ns /= 2;
+    if (t_opts->wg_target > 0) ns = ceil_div(t_opts->wg_target, tiles*n);
+    const int total = B*ceil_div((int)T, WG_BT);
+    if (ns > total) ns = total;
+    if (ns < 1) ns = 1;
+    rp.nsplit = ns;
+    ProfScope prof("pw1_wgrad", 2.0*n*BT*(double)l.Hp*l.Bnp*2, 2.0*BT*(l.Hp + l.Bnp)*n, st);
+    hipLaunchKernelGGL(pw1_wgrad_rc_kernel, dim3(tiles, ns, n), dim3(256), 0, st, rp);
+    BRV_HIP_OK(hipGetLastError());
+  }
+  // (The owner-computes kernel of the [res | skip] gradient was tried for this product too -- 256 of dz1's channels
+  // as its DMA'd operand, x as the 128-wide one, two launches of 24 problems: 580 us against the 429 us of the
+  // grouped 128 x 128 tiles below: with one item per workgroup its 136 KB zero fill and 128 KB partial tile are
+  // no longer amortised. profiles/r05_wgrad128.txt)
+  else
+  if (int r = launch_wgrad_group<A_BF16>(gp, st, "pw1_wgrad", 2.0*BT*(l.Hp + l.Bnp), -1))
+    return r;
+  return 0;
+}
+
+int deferred_wgrads(const Views& v, const float* params, float* grads, int blk_lo, int blk_hi, hipStream_t st) {
+  const Layout& l = v.l;
+  // residual / skip convs of every block in ONE launch when the padded widths are the
+  // default 128 | 128 (gemm_wgrad_full.cuh); other architectures use the generic path
+  const bool full_rs = l.Bnp == 128 && l.Scp == 128 && l.Hp % W2_BH == 0 && l.nb <= kWgMaxProb &&
+                       !opt(BRV_OPT_NO_WGRAD_FULL);
+  if (full_rs && blk_lo <= blk_hi)
+    if (int r = wgrad_rs_full(v, params, grads, blk_lo, blk_hi, st)) return r;
+  for (int i0 = blk_lo; i0 <= blk_hi; i0 += kWgMaxProb) {
+    const int n = std::min(kWgMaxProb, blk_hi + 1 - i0);
+    if (!full_rs)
+      if (int r = wgrad_rs_grouped(v, params, grads, i0, n, st)) return r;
+    if (int r = wgrad_pw1(v, params, grads, i0, n, st)) return r;
+  }
+  return 0;
+}
+
+// ---- backward in stages (brv_ctn_backward_part): head, blocks from the last to the first, the part's deferred
+// weight gradients, tail. `bwd_fused`: the backward mirror of the fused forward runs.
+// The head serves the causal model too: same launches, its driver zeroes the replica block itself and its
+// two weight gradients keep the default workgroup target.
+int backward_head(const Views& v, const float* params, const float* d_out, float* grads, long long L,
+                  bool bwd_fused, hipStream_t st) {
+  const Layout& l = v.l; const int B = v.B; const long long T = v.T; const double BT = v.BT();
+  const int BS = B*l.S, ldg = v.ldg(); GemmRowsParams g; WgradParams wg;
+  // sums and replica block <- 0; a workspace filled by a forward call in the other mode -> NaN sums (and with
+  // them NaN gradients)
+  if (!l.causal)
+    if (int r = launch_call_init(v.sum(0), (long long)(v.ws.stats_bytes/8), v.vg(), (long long)v.ws.vg_bytes,
+                                 reinterpret_cast<const int*>(v.base + v.ws.stamp), mode_stamp(l.fused_fwd()), nullptr, 0, st))
+      return fail(r, "backward: call_init launch");
+  // decoder data gradient (framing of d_out) fused with the mask backward
+  memset(&g, 0, sizeof(g));
   g.a = frames_of(d_out, L, l.hop, l.K);
-  g.W = prep + l.p_dec_b; g.T = (int)T; g.Np = l.Np; g.Kp = l.Kfp;
-  g.e.out = dpre; g.e.ldo = l.Np; g.e.out2 = dw1; g.e.w_in = w; g.e.ld_w = l.Np;
-  g.e.m_in = m; g.e.S = l.S;
+  g.W = v.prep + l.p_dec_b; g.T = (int)T; g.Np = l.Np; g.Kp = l.Kfp;
+  g.e.out = v.dpre(); g.e.ldo = l.Np; g.e.out2 = v.dw1(); g.e.w_in = v.w(); g.e.ld_w = l.Np;
+  g.e.m_in = v.m(); g.e.S = l.S;
   if (int r = launch_gemm_rows<A_FRAMES, E_MASK_BWD>(g, BS, st, "dec_bwd", 4.0*BS*L + 2.0*BT*l.Np*(1 + 3*l.S))) return r;
-  memset(&wg, 0, sizeof(wg));                              // decoder weight gradient
-  wg.g = rows_bf16(y, l.Np, T); wg.h = frames_of(d_out, L, l.hop, l.K);
+  // decoder weight gradient: y^T * frames(d_out)
+  memset(&wg, 0, sizeof(wg));
+  wg.g = rows_bf16(v.y(), l.Np, T); wg.h = frames_of(d_out, L, l.hop, l.K);
   wg.B = BS; wg.T = (int)T; wg.Gp = l.Np; wg.Hp = l.Kfp;
   wg.out0 = grads + l.dec_w; wg.G0p = l.Np; wg.N0 = l.N; wg.Kout = l.K; wg.ldo = l.K;
-  if (int r = launch_wgrad<A_FRAMES>(wg, st, "wgrad_dec", 2.0*BT*l.S*l.Np + 4.0*BS*L)) return r;
-  memset(&g, 0, sizeof(g));                                // output conv dgrad + PReLU backward
-  g.a = rows_bf16(dpre, l.Np, T); g.a.nsrc = l.S;
-  g.W = prep + l.p_out_b; g.T = (int)T; g.Np = l.Scp; g.Kp = l.S*l.Np;
-  g.e.out = gskip; g.e.ldo = ldg; g.e.src_f32 = skip; g.e.ld_srcf = l.Scp;
-  g.e.src_slope = params + l.tcn_prelu; g.e.dslope = vslope;
-  g.e.rep_stride = ws.vg_stride; g.e.n_rep = kReplicas;
+  if (int r = launch_wgrad<A_FRAMES>(wg, st, "wgrad_dec", 2.0*BT*l.S*l.Np + 4.0*BS*L, l.causal ? 384 : 768)) return r;
+  // output conv data gradient, PReLU backward -> gradient wrt skip_sum
+  memset(&g, 0, sizeof(g));
+  g.a = rows_bf16(v.dpre(), l.Np, T); g.a.nsrc = l.S;
+  g.W = v.prep + l.p_out_b; g.T = (int)T; g.Np = l.Scp; g.Kp = l.S*l.Np;
+  g.e.out = v.gskip(); g.e.ldo = ldg; g.e.src_f32 = v.skip(); g.e.ld_srcf = l.Scp;
+  g.e.src_slope = params + l.tcn_prelu; g.e.dslope = v.vslope();
+  g.e.rep_stride = v.ws.vg_stride; g.e.n_rep = kReplicas;
   if (int r = launch_gemm_rows<A_BF16, E_PRELU_BWD>(g, B, st, "mask_bwd", 2.0*BT*l.S*l.Np + 6.0*BT*l.Scp)) return r;
-  for (int s = 0; s < l.S; ++s) {                          // output conv weight / bias gradients
+  if (bwd_fused) {
+    // fused backward: the layer-norm backward means of the LAST block from g_skip and its stored u
+    // (every other block gets them from the kernel that produces its g_out, E_ADD epilogue below)
+    GuDotsParams gu; memset(&gu, 0, sizeof(gu));
+    gu.g = v.gskip(); gu.ldg = ldg; gu.u = v.u(l.nb - 1) + l.Bnp; gu.ldu = ldg;
+    gu.v1 = reinterpret_cast<const float*>(v.prep + l.blk[l.nb - 1].p_lazy) + ldg + l.Bnp;
+    gu.ncols = l.Scp; gu.B = B; gu.T = (int)T; gu.out = v.sum(2 + 2*(l.nb - 1));
+    ProfScope prof("gu_dots", 0, 4.0*BT*l.Scp, st);
+    int gx = (int)((T*(l.Scp/8) + 255)/256);
+    if (gx > 64) gx = 64;
+    hipLaunchKernelGGL(gu_dots_kernel, dim3(gx, B), dim3(256), 0, st, gu);
+    BRV_HIP_OK(hipGetLastError());
+  }
+  // output conv weight / bias gradients, one source at a time
+  for (int s = 0; s < l.S; ++s) {
     memset(&wg, 0, sizeof(wg));
-    wg.g = rows_bf16(dpre + (long long)s*T*l.Np, l.Np, T); wg.g.bs0 = (long long)l.S*T*l.Np;
-    wg.h = rows_bf16(skip, l.Scp, T); wg.h.slope = params + l.tcn_prelu;
+    wg.g = rows_bf16(v.dpre() + (long long)s*T*l.Np, l.Np, T); wg.g.bs0 = (long long)l.S*T*l.Np;
+    wg.h = rows_bf16(v.skip(), l.Scp, T); wg.h.slope = params + l.tcn_prelu;
     wg.B = B; wg.T = (int)T; wg.Gp = l.Np; wg.Hp = l.Scp;
     wg.out0 = grads + l.out_w + (long long)s*l.N*l.Sc; wg.G0p = l.Np; wg.N0 = l.N;
     wg.Kout = l.Sc; wg.ldo = l.Sc; wg.gbias0 = grads + l.out_b + (long long)s*l.N;
-    if (int r = launch_wgrad<A_F32>(wg, st, "wgrad_out", 2.0*BT*l.Np + 4.0*BT*l.Scp)) return r;
+    if (int r = launch_wgrad<A_F32>(wg, st, "wgrad_out", 2.0*BT*l.Np + 4.0*BT*l.Scp, l.causal ? 384 : 256)) return r;
   }
+  return 0;
+}
 
-  for (int i = l.nb - 1; i >= 0; --i) {
-    const BlockOff& b = l.blk[i];
-    const bool has_res = i < l.nb - 1;
-    const int dil = 1 << (i % cfg->layers);
-    const int rs0 = has_res ? l.Bnp : 0;
-    // [res | skip] weight / bias gradients: G = [g_out | g_skip], H = h2 (materialised)
-    memset(&wg, 0, sizeof(wg));
-    wg.g = rows_bf16(has_res ? gout : gskip, ldg, T);
-    wg.h = rows_bf16(h2buf(i), l.Hp, T);
-    wg.B = B; wg.T = (int)T; wg.Gp = rs0 + l.Scp; wg.Hp = l.Hp;
-    wg.out0 = has_res ? grads + b.res_w : nullptr; wg.out1 = grads + b.skip_w;
-    wg.G0p = rs0; wg.N0 = has_res ? l.Bn : 0; wg.N1 = l.Sc; wg.Kout = l.H; wg.ldo = l.H;
-    wg.gbias0 = has_res ? grads + b.res_b : nullptr; wg.gbias1 = grads + b.skip_b;
-    if (int r = launch_wgrad<A_BF16>(wg, st, "pw2_wgrad", 2.0*BT*(rs0 + l.Scp + l.Hp))) return r;
-    // [res | skip] data gradient -> gradient wrt h2
+// block i up to the gradient wrt the first norm's output (e1, kept per block in eB)
+int backward_block_dw(const Views& v, const float* params, int i, bool bwd_fused, hipStream_t st) {
+  const Layout& l = v.l; const int B = v.B; const long long T = v.T; const double BT = v.BT();
+  const int ldg = v.ldg(); GemmRowsParams g;
+  const BlockOff& b = l.blk[i];
+  const bool has_res = i < l.nb - 1;
+  const int dil = 1 << (i % l.layers);
+  const int rs0 = has_res ? l.Bnp : 0;
+  const bool blk_fused = bwd_fused && (((l.P - 1)*dil)/2) % dil == 0;
+  if (!blk_fused) {
+    // [res | skip] data gradient + gLN_2 backward partials
     memset(&g, 0, sizeof(g));
-    g.a = rows_bf16(has_res ? gout : gskip, ldg, T);
-    g.W = prep + b.p_rs_b; g.T = (int)T; g.Np = l.Hp; g.Kp = rs0 + l.Scp;
-    g.e.out = eA; g.e.ldo = l.Hp; g.e.N = l.H;
-    if (int r = launch_gemm_rows<A_BF16, E_STORE>(g, B, st, "pw2_dgrad", 2.0*BT*(rs0 + l.Scp + l.Hp))) return r;
-    // cLN_2 + PReLU_2 backward -> dz2 (in place over eA is not possible: g is read twice)
-    if (int r = cln_backward(cx, eA, z2buf(i), params + b.prelu2, params + b.n2_g,
-                             cx.tab(2 + 2*i), eB, nullptr, 0, vslot(i) + 2*l.H, vslot(i) + 3*l.H,
-                             vslope + 2 + 2*i, ws.vg_stride, B, T, l.Hp, l.H, st)) return r;
-    // depthwise conv backward on h1 (identity operands: plain transposed convolution)
-    DwParams d; memset(&d, 0, sizeof(d));
-    d.z1 = h1buf(i); d.dz2 = eB; d.e1 = eA; d.B = B; d.T = (int)T; d.Cp = l.Hp; d.C = l.H;
-    d.slope1 = cx.one; d.stats1 = cx.fake; d.gamma1 = cx.ones; d.beta1 = cx.zeros;
-    d.inv_n = 1.0/((double)T*l.H); d.eps = 1e-8f;
-    d.taps = params + b.dconv_w; d.dil = dil; d.left = (l.P - 1)*dil;
-    d.dgamma1 = vscratch; d.dbeta1 = vscratch + l.Hp;
-    d.dtaps = vslot(i) + 4*l.H; d.dbias = vslot(i) + 4*l.H + (long long)l.H*l.P;
-    d.rep_stride = ws.vg_stride; d.sums1 = cx.scratch_stats;
-    if (int r = dispatch_p<DwBwd>(l.P, d, st)) return r;
-    // cLN_1 + PReLU_1 backward -> dz1
-    if (int r = cln_backward(cx, eA, z1buf(i), params + b.prelu1, params + b.n1_g,
-                             cx.tab(1 + 2*i), eB, nullptr, 0, vslot(i), vslot(i) + l.H,
-                             vslope + 1 + 2*i, ws.vg_stride, B, T, l.Hp, l.H, st)) return r;
-    // first 1x1 conv: weight / bias gradients, then data gradient + residual path
-    memset(&wg, 0, sizeof(wg));
-    wg.g = rows_bf16(eB, l.Hp, T); wg.h = rows_bf16(xbuf(i), l.Bnp, T);
-    wg.B = B; wg.T = (int)T; wg.Gp = l.Hp; wg.Hp = l.Bnp;
-    wg.out0 = grads + b.conv_w; wg.G0p = l.Hp; wg.N0 = l.H; wg.Kout = l.Bn; wg.ldo = l.Bn;
-    wg.gbias0 = grads + b.conv_b;
-    if (int r = launch_wgrad<A_BF16>(wg, st, "pw1_wgrad", 2.0*BT*(l.Hp + l.Bnp))) return r;
-    memset(&g, 0, sizeof(g));
-    g.a = rows_bf16(eB, l.Hp, T);
-    g.W = prep + b.p_c1_b; g.T = (int)T; g.Np = l.Bnp; g.Kp = l.Hp;
-    g.e.out = gout; g.e.ldo = ldg; g.e.add_in = has_res ? gout : nullptr; g.e.ld_add = ldg;
-    if (int r = launch_gemm_rows<A_BF16, E_ADD>(g, B, st, "pw1_dgrad", 2.0*BT*(l.Hp + l.Bnp*(has_res ? 2 : 1)))) return r;
+    g.a = rows_bf16(has_res ? v.gout() : v.gskip(), ldg, T);
+    g.W = v.prep + b.p_rs_b; g.T = (int)T; g.Np = l.Hp; g.Kp = rs0 + l.Scp;
+    g.Wp = v.prep + b.p_rs_bp; g.wp_nsl = 32;
+    g.e.out = v.eA(); g.e.ldo = l.Hp; g.e.N = l.H;
+    g.e.src = v.z2(i); g.e.ld_src = l.Hp; g.e.src_slope = params + b.prelu2;
+    g.e.src_stats = v.stat(2 + 2*i); g.e.inv_n = 1.0/((double)T*l.H); g.e.eps = 1e-8f;
+    g.e.gamma = params + b.n2_g;
+    g.e.dgamma = v.vslot(i) + 2*l.H; g.e.dbeta = v.vslot(i) + 3*l.H;
+    g.e.rep_stride = v.ws.vg_stride; g.e.n_rep = kReplicas;
+    g.e.sums_out = v.sum(2 + 2*i);
+    if (int r = launch_gemm_rows<A_BF16, E_GLN_BWD>(g, B, st, "pw2_dgrad", 2.0*BT*(rs0 + l.Scp + 2*l.Hp))) return r;
   }
+  // gLN_2 + prelu_2 backward: fused into the depthwise backward below when its LDS window
+  // (tile + halo rows) fits -- dz2 is then built once per element in LDS and never written
+  // (dwconv_bwd_halo_kernel). BRV_NO_DZ_FUSE keeps the separate pass.
+  const bool fuse_dz2 = blk_fused || (!opt(BRV_OPT_NO_DZ_FUSE) && l.Hp % HL_CG == 0 &&
+                        (((l.P - 1)*dil)/2) % dil == 0 && hl_window_rows(dil, l.P) <= HL_MAXROWS);
+  DzParams dz; memset(&dz, 0, sizeof(dz));
+  if (!fuse_dz2) {
+    dz.e = v.eA(); dz.z = v.z2(i); dz.B = B; dz.T = (int)T; dz.Cp = l.Hp; dz.C = l.H;
+    dz.slope = params + b.prelu2; dz.stats = v.stat(2 + 2*i); dz.sums = v.sum(2 + 2*i);
+    dz.inv_n = 1.0/((double)T*l.H); dz.eps = 1e-8f; dz.dslope = v.vslope() + 2 + 2*i; dz.rep_stride = v.ws.vg_stride;
+    if (int r = launch_dz(dz, st)) return r;
+  }
+  // depthwise conv backward (data, taps, bias) + gLN_1 partials
+  DwParams d; memset(&d, 0, sizeof(d));
+  bf16_t* eB = v.eB(i);
+  d.z1 = v.z1(i); d.dz2 = v.eA(); d.e1 = eB; d.B = B; d.T = (int)T; d.Cp = l.Hp; d.C = l.H;
+  d.slope1 = params + b.prelu1; d.stats1 = v.stat(1 + 2*i);
+  d.gamma1 = params + b.n1_g; d.beta1 = params + b.n1_b;
+  d.inv_n = 1.0/((double)T*l.H); d.eps = 1e-8f;
+  d.taps = params + b.dconv_w; d.dil = dil; d.left = ((l.P - 1)*dil)/2;
+  d.dgamma1 = v.vslot(i); d.dbeta1 = v.vslot(i) + l.H;
+  d.dtaps = v.vslot(i) + 4*l.H; d.dbias = v.vslot(i) + 4*l.H + (long long)l.H*l.P;
+  d.rep_stride = v.ws.vg_stride; d.sums1 = v.sum(1 + 2*i);
+  if (fuse_dz2) {
+    d.z2in = v.z2(i); d.stats2 = v.stat(2 + 2*i); d.sums2 = v.sum(2 + 2*i);
+    d.slope2 = params + b.prelu2; d.dslope2 = v.vslope() + 2 + 2*i;
+  }
+  if (blk_fused) {
+    BwdFusedParams bf; memset(&bf, 0, sizeof(bf));
+    bf.d = d; bf.d.dz2 = nullptr;
+    bf.g = has_res ? v.gout() : v.gskip(); bf.ldg = ldg; bf.Kg = rs0 + l.Scp;
+    bf.Wp = v.prep + b.p_rs_bp; bf.gamma2 = params + b.n2_g;
+    bf.dgamma2 = v.vslot(i) + 2*l.H; bf.dbeta2 = v.vslot(i) + 3*l.H;
+    if (int r = DwBwdFused<3>::run(bf, st)) return r;      // (fused_fwd() implies kernel_size 3)
+  } else
+  if (int r = dispatch_p<DwBwd>(l.P, d, st)) return r;
+  return 0;
+}
+
+// first 1x1 conv data gradient of block i without the stored z1 / dz1 (pw1_bwd.cuh); `e`: the E_ADD epilogue
+int backward_block_pw1_rc(const Views& v, const float* params, int i, const EpiSpec& e, bool bwd_fused,
+                          hipStream_t st) {
+  const Layout& l = v.l; const int B = v.B; const long long T = v.T; const double BT = v.BT();
+  const BlockOff& b = l.blk[i];
+  const bool has_res = i < l.nb - 1;
+  bf16_t* eB = v.eB(i);
+  Pw1DgradRcParams rp; memset(&rp, 0, sizeof(rp));
+  rp.e1 = eB; rp.lde = l.Hp; rp.bse = T*l.Hp;
+  rp.x = v.x(i); rp.ldx = l.Bnp; rp.bsx = T*l.Bnp;
+  rp.Wfp = v.prep + b.p_c1_fp; rp.bias = params + b.conv_b; rp.Wb = v.prep + b.p_c1_b;
+  rp.stats = v.stat(1 + 2*i); rp.sums = v.sum(1 + 2*i); rp.slope = params + b.prelu1;
+  rp.inv_n = 1.0/((double)T*l.H); rp.eps = 1e-8f; rp.C = l.H;
+  rp.T = (int)T; rp.n_ttiles = ceil_div((int)T, RC_BM); rp.batch = B;
+  rp.e = e;
+  rp.e.dslope = v.vslope() + 1 + 2*i; rp.e.rep_stride = v.ws.vg_stride; rp.e.n_rep = kReplicas;
+  if (opt(BRV_OPT_PW1_RC_TILES)) {        // first form: one tile per workgroup, weights re-read per tile
+    ProfScope prof("pw1_dgrad", 2.0*BT*(double)l.Hp*l.Bnp*2,
+                   2.0*BT*(l.Hp + l.Bnp*(has_res ? 3 : 2)), st);
+    hipLaunchKernelGGL(pw1_dgrad_rc_kernel, dim3(rp.n_ttiles*B), dim3(256), 0, st, rp);
+  } else {
+    Pw1DgradWsParams wp; wp.r = rp;
+    wp.dz_out = pw1_rc_wgrad() ? nullptr : eB;      // stored-dz1 weight gradient: dz1 over e1, in place
+    wp.dbg = nullptr;
+#ifdef WSD_STAMP
+    wp.dbg = debug_buffer();
+#endif
+    // algorithmic bytes: e1 and x in (+ the residual g_out), dz1 and the new g_out out -- and the companions the
+    // row-wise epilogue streams: the copy of g_out kept for block i - 1's weight gradient and, for that block's
+    // layer-norm backward means, its u ([res | skip] wide) and g_skip rows (the line understated
+    // the kernel by 2 BT 384; PMC 244.8 MB per launch = this count)
+    const double companions = (i > 0 ? l.Bnp : 0) + (bwd_fused && i > 0 ? (double)l.Bnp + 2.0*l.Scp : 0.0);
+    ProfScope prof("pw1_dgrad", 2.0*BT*(double)l.Hp*l.Bnp*2,
+                   2.0*BT*(l.Hp*(wp.dz_out ? 2 : 1) + l.Bnp*(has_res ? 3 : 2) + companions), st);
+    int grid = num_cus();
+    const int total = ceil_div((int)T, WSD_TF)*B;
+    if (grid > total) grid = total;
+    if (l.H == RC_H) hipLaunchKernelGGL(pw1_dgrad_ws_kernel<true>, dim3(grid), dim3(512), 0, st, wp);
+    else hipLaunchKernelGGL(pw1_dgrad_ws_kernel<false>, dim3(grid), dim3(512), 0, st, wp);
+  }
+  BRV_HIP_OK(hipGetLastError());
+  return 0;
+}
+
+// block i from e1 to the gradient wrt the block input (gout)
+int backward_block_pw1(const Views& v, const float* params, int i, bool bwd_fused, hipStream_t st) {
+  const Layout& l = v.l; const int B = v.B; const long long T = v.T; const double BT = v.BT();
+  const BlockOff& b = l.blk[i];
+  const bool has_res = i < l.nb - 1;
+  const int ldg = v.ldg(); bf16_t* eB = v.eB(i); GemmRowsParams g; DzParams dz;
+  // gLN_1 + prelu_1 backward -> dz1: fused into the A staging of the data-gradient GEMM
+  // below (A_DZ: dz1 is computed from e1 and z1 on load and written back over e1 for the
+  // deferred weight gradient); BRV_NO_DZ1_FUSE keeps the separate pass
+  // (needs one n-tile: the workgroup that stages an A element must be its only reader)
+  const bool fuse_dz1 = !opt(BRV_OPT_NO_DZ1_FUSE) && (l.Bnp == 128 || l.Bnp == 64);
+  if (!fuse_dz1) {
+    memset(&dz, 0, sizeof(dz));
+    dz.e = eB; dz.z = v.z1(i); dz.B = B; dz.T = (int)T; dz.Cp = l.Hp; dz.C = l.H;
+    dz.slope = params + b.prelu1; dz.stats = v.stat(1 + 2*i); dz.sums = v.sum(1 + 2*i);
+    dz.inv_n = 1.0/((double)T*l.H); dz.eps = 1e-8f; dz.dslope = v.vslope() + 1 + 2*i; dz.rep_stride = v.ws.vg_stride;
+    if (int r = launch_dz(dz, st)) return r;
+  }
+  // first 1x1 conv: data gradient + residual path -> gradient wrt block input
+  memset(&g, 0, sizeof(g));
+  g.a = rows_bf16(eB, l.Hp, T);
+  g.W = v.prep + b.p_c1_b; g.T = (int)T; g.Np = l.Bnp; g.Kp = l.Hp;
+  g.e.out = v.gout(); g.e.ldo = ldg; g.e.add_in = has_res ? v.gout() : nullptr; g.e.ld_add = ldg;
+  // block i-1's deferred [res | skip] weight gradient needs this g_out after gout is
+  // overwritten again: keep a copy (16 MB per block at the BASELINE size)
+  g.e.out2 = i > 0 ? v.gcopy(i - 1) : nullptr; g.e.ld_srcf = l.Bnp;
+  if (bwd_fused && i > 0) {        // block i - 1's layer-norm backward means, from its g and u
+    g.e.gu_u = v.u(i - 1); g.e.ld_gu = ldg; g.e.gu_gskip = v.gskip(); g.e.ld_gs = ldg;
+    g.e.gu_v1 = reinterpret_cast<const float*>(v.prep + l.blk[i - 1].p_lazy) + ldg;
+    g.e.gu_out = v.sum(2 + 2*(i - 1));
+  }
+  if (fuse_dz1 && l.pw1_rc()) return backward_block_pw1_rc(v, params, i, g.e, bwd_fused, st);
+  if (fuse_dz1) {
+    g.a.p1 = v.z1(i); g.a.ld1 = l.Hp; g.a.bs1 = T*l.Hp;
+    g.a.slope = params + b.prelu1; g.a.stats = v.stat(1 + 2*i); g.a.sums = v.sum(1 + 2*i);
+    g.a.inv_n = 1.0/((double)T*l.H); g.a.eps = 1e-8f; g.a.C = l.H;
+    g.e.dslope = v.vslope() + 1 + 2*i; g.e.rep_stride = v.ws.vg_stride; g.e.n_rep = kReplicas;
+    return launch_gemm_rows<A_DZ, E_ADD>(g, B, st, "pw1_dgrad", 2.0*BT*(3*l.Hp + l.Bnp*(has_res ? 2 : 1)));
+  }
+  return launch_gemm_rows<A_BF16, E_ADD>(g, B, st, "pw1_dgrad", 2.0*BT*(l.Hp + l.Bnp*(has_res ? 2 : 1)));
+}
+
+int backward_block(const Views& v, const float* params, int i, bool bwd_fused, hipStream_t st) {
+  if (int r = backward_block_dw(v, params, i, bwd_fused, st)) return r;
+  return backward_block_pw1(v, params, i, bwd_fused, st);
+}
+
+int backward_tail(const Views& v, const float* params, const float* wave, long long wave_stride, float* grads,
+                  long long L, hipStream_t st) {
+  const Layout& l = v.l; const int B = v.B; const long long T = v.T; const double BT = v.BT();
+  const int ldg = v.ldg(); GemmRowsParams g; WgradParams wg;
+  // bottleneck conv: data gradient + first gLN backward partials
+  memset(&g, 0, sizeof(g));
+  g.a = rows_bf16(v.gout(), ldg, T);
+  g.W = v.prep + l.p_bott_b; g.T = (int)T; g.Np = l.Np; g.Kp = l.Bnp;
+  g.e.out = v.e0(); g.e.ldo = l.Np; g.e.N = l.N;
+  g.e.src = v.w(); g.e.ld_src = l.Np; g.e.src_stats = v.stat(0);
+  g.e.inv_n = 1.0/((double)T*l.N); g.e.eps = 1e-8f;
+  g.e.gamma = params + l.ln_g; g.e.dgamma = v.vg(); g.e.dbeta = v.vg() + l.N;
+  g.e.rep_stride = v.ws.vg_stride; g.e.n_rep = kReplicas;
+  g.e.sums_out = v.sum(0);
+  if (int r = launch_gemm_rows<A_BF16, E_GLN_BWD>(g, B, st, "bottleneck_dgrad", 2.0*BT*(l.Bnp + 2*l.Np))) return r;
+  // bottleneck conv: weight / bias gradients against gLN(w)
+  memset(&wg, 0, sizeof(wg));
+  wg.g = rows_bf16(v.gout(), ldg, T); wg.h = rows_bf16(v.w(), l.Np, T);
+  set_affine(wg.h, v.stat(0), params + l.ln_g, params + l.ln_b, l.N, T);
+  wg.B = B; wg.T = (int)T; wg.Gp = l.Bnp; wg.Hp = l.Np;
+  wg.out0 = grads + l.bott_w; wg.G0p = l.Bnp; wg.N0 = l.Bn; wg.Kout = l.N; wg.ldo = l.N;
+  wg.gbias0 = grads + l.bott_b;
+  if (int r = launch_wgrad<A_BF16>(wg, st, "bottleneck_wgrad", 2.0*BT*(l.Bnp + l.Np), 256)) return r;
+  // total gradient wrt the encoder output
+  CombineParams cb; memset(&cb, 0, sizeof(cb));
+  cb.e0 = v.e0(); cb.w = v.w(); cb.dw1 = v.dw1(); cb.dw = v.dwt(); cb.B = B; cb.T = (int)T;
+  cb.Cp = l.Np; cb.C = l.N; cb.S = l.S; cb.stats = v.stat(0); cb.sums = v.sum(0);
+  cb.inv_n = 1.0/((double)T*l.N); cb.eps = 1e-8f;
+  {
+    const long long per_item = T*(l.Np/8);
+    int gx = (int)((per_item + 1023)/1024);
+    if (gx > 2048) gx = 2048;
+    if (gx < 1) gx = 1;
+    ProfScope prof("gln0_bwd", 0, 2.0*BT*l.Np*(3 + l.S), st);
+    hipLaunchKernelGGL(gln0_bwd_combine_kernel, dim3(gx, B), dim3(256), 0, st, cb);
+    BRV_HIP_OK(hipGetLastError());
+  }
+  // encoder weight gradient: dw^T * frames(wave)
+  memset(&wg, 0, sizeof(wg));
+  wg.g = rows_bf16(v.dwt(), l.Np, T); wg.h = frames_of(wave, L, l.hop, l.K, wave_stride);
+  wg.B = B; wg.T = (int)T; wg.Gp = l.Np; wg.Hp = l.Kfp;
+  wg.out0 = grads + l.enc_w; wg.G0p = l.Np; wg.N0 = l.N; wg.Kout = l.K; wg.ldo = l.K;
+  if (int r = launch_wgrad<A_FRAMES>(wg, st, "wgrad_enc", 2.0*BT*l.Np + 4.0*B*L, 768)) return r;
+  return 0;
+}
+
+// ---- causal backward: the head above, then materialised cLN tensors block by block
+int backward_causal_block(const Views& v, const float* params, float* grads, int i, hipStream_t st) {
+  const Layout& l = v.l; const int B = v.B; const long long T = v.T; const double BT = v.BT();
+  const int ldg = v.ldg(); GemmRowsParams g; WgradParams wg;
+  const BlockOff& b = l.blk[i];
+  const bool has_res = i < l.nb - 1;
+  const int dil = 1 << (i % l.layers);
+  const int rs0 = has_res ? l.Bnp : 0;
+  // [res | skip] weight / bias gradients: G = [g_out | g_skip], H = h2 (materialised)
+  memset(&wg, 0, sizeof(wg));
+  wg.g = rows_bf16(has_res ? v.gout() : v.gskip(), ldg, T);
+  wg.h = rows_bf16(v.h2(i), l.Hp, T);
+  wg.B = B; wg.T = (int)T; wg.Gp = rs0 + l.Scp; wg.Hp = l.Hp;
+  wg.out0 = has_res ? grads + b.res_w : nullptr; wg.out1 = grads + b.skip_w;
+  wg.G0p = rs0; wg.N0 = has_res ? l.Bn : 0; wg.N1 = l.Sc; wg.Kout = l.H; wg.ldo = l.H;
+  wg.gbias0 = has_res ? grads + b.res_b : nullptr; wg.gbias1 = grads + b.skip_b;
+  if (int r = launch_wgrad<A_BF16>(wg, st, "pw2_wgrad", 2.0*BT*(rs0 + l.Scp + l.Hp))) return r;
+  // [res | skip] data gradient -> gradient wrt h2
+  memset(&g, 0, sizeof(g));
+  g.a = rows_bf16(has_res ? v.gout() : v.gskip(), ldg, T);
+  g.W = v.prep + b.p_rs_b; g.T = (int)T; g.Np = l.Hp; g.Kp = rs0 + l.Scp;
+  g.e.out = v.eA(); g.e.ldo = l.Hp; g.e.N = l.H;
+  if (int r = launch_gemm_rows<A_BF16, E_STORE>(g, B, st, "pw2_dgrad", 2.0*BT*(rs0 + l.Scp + l.Hp))) return r;
+  // cLN_2 + PReLU_2 backward -> dz2 (in place over eA is not possible: g is read twice)
+  if (int r = cln_backward(v, v.eA(), v.z2(i), params + b.prelu2, params + b.n2_g,
+                           v.tab(2 + 2*i), v.eB(0), nullptr, 0, v.vslot(i) + 2*l.H, v.vslot(i) + 3*l.H,
+                           v.vslope() + 2 + 2*i, v.ws.vg_stride, B, T, l.Hp, l.H, st)) return r;
+  // depthwise conv backward on h1 (identity operands: plain transposed convolution)
+  DwParams d; memset(&d, 0, sizeof(d));
+  d.z1 = v.h1(i); d.dz2 = v.eB(0); d.e1 = v.eA(); d.B = B; d.T = (int)T; d.Cp = l.Hp; d.C = l.H;
+  d.slope1 = v.one(); d.stats1 = v.fake_stats(); d.gamma1 = v.ones(); d.beta1 = v.zeros();
+  d.inv_n = 1.0/((double)T*l.H); d.eps = 1e-8f;
+  d.taps = params + b.dconv_w; d.dil = dil; d.left = (l.P - 1)*dil;
+  d.dgamma1 = v.vscratch(); d.dbeta1 = v.vscratch() + l.Hp;
+  d.dtaps = v.vslot(i) + 4*l.H; d.dbias = v.vslot(i) + 4*l.H + (long long)l.H*l.P;
+  d.rep_stride = v.ws.vg_stride; d.sums1 = v.scratch_stats();
+  if (int r = dispatch_p<DwBwd>(l.P, d, st)) return r;
+  // cLN_1 + PReLU_1 backward -> dz1
+  if (int r = cln_backward(v, v.eA(), v.z1(i), params + b.prelu1, params + b.n1_g,
+                           v.tab(1 + 2*i), v.eB(0), nullptr, 0, v.vslot(i), v.vslot(i) + l.H,
+                           v.vslope() + 1 + 2*i, v.ws.vg_stride, B, T, l.Hp, l.H, st)) return r;
+  // first 1x1 conv: weight / bias gradients, then data gradient + residual path
+  memset(&wg, 0, sizeof(wg));
+  wg.g = rows_bf16(v.eB(0), l.Hp, T); wg.h = rows_bf16(v.x(i), l.Bnp, T);
+  wg.B = B; wg.T = (int)T; wg.Gp = l.Hp; wg.Hp = l.Bnp;
+  wg.out0 = grads + b.conv_w; wg.G0p = l.Hp; wg.N0 = l.H; wg.Kout = l.Bn; wg.ldo = l.Bn;
+  wg.gbias0 = grads + b.conv_b;
+  if (int r = launch_wgrad<A_BF16>(wg, st, "pw1_wgrad", 2.0*BT*(l.Hp + l.Bnp))) return r;
+  memset(&g, 0, sizeof(g));
+  g.a = rows_bf16(v.eB(0), l.Hp, T);
+  g.W = v.prep + b.p_c1_b; g.T = (int)T; g.Np = l.Bnp; g.Kp = l.Hp;
+  g.e.out = v.gout(); g.e.ldo = ldg; g.e.add_in = has_res ? v.gout() : nullptr; g.e.ld_add = ldg;
+  if (int r = launch_gemm_rows<A_BF16, E_ADD>(g, B, st, "pw1_dgrad", 2.0*BT*(l.Hp + l.Bnp*(has_res ? 2 : 1)))) return r;
+  return 0;
+}
+
+int backward_causal_tail(const Views& v, const float* params, const float* wave, long long wave_stride,
+                         float* grads, long long L, hipStream_t st) {
+  const Layout& l = v.l; const int B = v.B; const long long T = v.T; const double BT = v.BT();
+  const int ldg = v.ldg(); GemmRowsParams g; WgradParams wg;
   // bottleneck conv: weight gradient (H = cLN(w), materialised), data gradient, cLN backward
   memset(&wg, 0, sizeof(wg));
-  wg.g = rows_bf16(gout, ldg, T); wg.h = rows_bf16(wn, l.Np, T);
+  wg.g = rows_bf16(v.gout(), ldg, T); wg.h = rows_bf16(v.wn(), l.Np, T);
   wg.B = B; wg.T = (int)T; wg.Gp = l.Bnp; wg.Hp = l.Np;
   wg.out0 = grads + l.bott_w; wg.G0p = l.Bnp; wg.N0 = l.Bn; wg.Kout = l.N; wg.ldo = l.N;
   wg.gbias0 = grads + l.bott_b;
   if (int r = launch_wgrad<A_BF16>(wg, st, "bottleneck_wgrad", 2.0*BT*(l.Bnp + l.Np))) return r;
   memset(&g, 0, sizeof(g));
-  g.a = rows_bf16(gout, ldg, T);
-  g.W = prep + l.p_bott_b; g.T = (int)T; g.Np = l.Np; g.Kp = l.Bnp;
-  g.e.out = e0; g.e.ldo = l.Np; g.e.N = l.N;
+  g.a = rows_bf16(v.gout(), ldg, T);
+  g.W = v.prep + l.p_bott_b; g.T = (int)T; g.Np = l.Np; g.Kp = l.Bnp;
+  g.e.out = v.e0(); g.e.ldo = l.Np; g.e.N = l.N;
   if (int r = launch_gemm_rows<A_BF16, E_STORE>(g, B, st, "bottleneck_dgrad", 2.0*BT*(l.Bnp + l.Np))) return r;
   // total gradient wrt the encoder output: cLN backward + the S mask-path terms
-  if (int r = cln_backward(cx, e0, w, nullptr, params + l.ln_g, cx.tab(0), dwt, dw1, l.S, vg,
-                           vg + l.N, nullptr, ws.vg_stride, B, T, l.Np, l.N, st)) return r;
+  if (int r = cln_backward(v, v.e0(), v.w(), nullptr, params + l.ln_g, v.tab(0), v.dwt(), v.dw1(), l.S, v.vg(),
+                           v.vg() + l.N, nullptr, v.ws.vg_stride, B, T, l.Np, l.N, st)) return r;
   memset(&wg, 0, sizeof(wg));                              // encoder weight gradient
-  wg.g = rows_bf16(dwt, l.Np, T); wg.h = frames_of(wave, L, l.hop, l.K, wave_stride);
+  wg.g = rows_bf16(v.dwt(), l.Np, T); wg.h = frames_of(wave, L, l.hop, l.K, wave_stride);
   wg.B = B; wg.T = (int)T; wg.Gp = l.Np; wg.Hp = l.Kfp;
   wg.out0 = grads + l.enc_w; wg.G0p = l.Np; wg.N0 = l.N; wg.Kout = l.K; wg.ldo = l.K;
   if (int r = launch_wgrad<A_FRAMES>(wg, st, "wgrad_enc", 2.0*BT*l.Np + 4.0*B*L)) return r;
-  return reduce_vector_grads(l, ws, vg, grads, st);
+  return reduce_vector_grads(v, grads, st);
 }
+
+int backward_causal(const Views& v, const float* params, const float* wave, long long wave_stride,
+                    const float* d_out, float* grads, long long L, hipStream_t st) {
+  if (int r = causal_init(v, st)) return r;
+  BRV_HIP_OK(hipMemsetAsync(v.vg(), 0, v.ws.vg_bytes, st));
+  if (int r = backward_head(v, params, d_out, grads, L, false, st)) return r;
+  for (int i = v.l.nb - 1; i >= 0; --i)
+    if (int r = backward_causal_block(v, params, grads, i, st)) return r;
+  return backward_causal_tail(v, params, wave, wave_stride, grads, L, st);
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -1248,42 +1780,9 @@ int brv_ctn_forward(const brv_ctn_config* cfg, const float* params, const void* 
   const int B = (int)batch; const long long L = length;
   const long long T = l.frames(L);
   if (B < 1 || T < 1) return fail(-1, "empty batch or input shorter than one frame");
-  if (l.causal) return forward_causal(l, cfg, params, prepared, workspace, wave, wave_stride, out, B, L, T, st);
-  Workspace ws; ws.init(l, B, T);
-  const double BT = (double)B*(double)T;
-  char* base = (char*)workspace;
-  const bf16_t* prep = (const bf16_t*)prepared;
-  double* stats = (double*)(base + ws.stats);
-  auto stat = [&](int i) { return stats + (long long)i*B*kStatStride; };
-  bf16_t* w = (bf16_t*)(base + ws.w);
-  auto xbuf = [&](int i) { return (bf16_t*)(base + ws.x + ws.x_stride*i); };
-  auto z1buf = [&](int i) { return (bf16_t*)(base + ws.z1 + ws.z_stride*i); };
-  auto z2buf = [&](int i) { return (bf16_t*)(base + ws.z2 + ws.z_stride*i); };
-  float* skip = (float*)(base + ws.skip);
-  bf16_t* m = (bf16_t*)(base + ws.m);
-  bf16_t* y = (bf16_t*)(base + ws.y);
-
-  // statistics and output <- 0; operands prepared for the other mode -> NaN statistics (and with them a NaN
-  // output); then this call's mode stamped on the workspace
-  if (int r = launch_call_init(stats, (long long)(ws.stats_bytes/8), out, (long long)B*l.S*L*(long long)sizeof(float),
-                               reinterpret_cast<const int*>(prep + l.p_stamp), mode_stamp(l.fused_fwd()),
-                               reinterpret_cast<int*>(base + ws.stamp), mode_stamp(l.fused_fwd()), st))
-    return fail(r, "forward: call_init launch");
-
-  GemmRowsParams g;
-  // encoder: framed filterbank analysis, statistics for the first gLN
-  memset(&g, 0, sizeof(g));
-  g.a = frames_of(wave, L, l.hop, l.K, wave_stride);
-  g.W = prep + l.p_enc; g.T = (int)T; g.Np = l.Np; g.Kp = l.Kfp;
-  g.e.out = w; g.e.ldo = l.Np; g.e.N = l.N; g.e.stats_out = stat(0);
-  if (int r = launch_gemm_rows<A_FRAMES, E_STORE>(g, B, st, "enc_fwd", 4.0*B*L + 2.0*BT*l.Np)) return r;
-  // bottleneck 1x1 conv on gLN(w)
-  memset(&g, 0, sizeof(g));
-  g.a = rows_bf16(w, l.Np, T);
-  set_affine(g.a, stat(0), params + l.ln_g, params + l.ln_b, l.N, T);
-  g.W = prep + l.p_bott_f; g.T = (int)T; g.Np = l.Bnp; g.Kp = l.Np;
-  g.e.out = xbuf(0); g.e.ldo = l.Bnp; g.e.bias = params + l.bott_b; g.e.N = l.Bn;
-  if (int r = launch_gemm_rows<A_BF16, E_STORE>(g, B, st, "bottleneck_fwd", 2.0*BT*(l.Np + l.Bnp))) return r;
+  const Views v(l, workspace, prepared, B, T);
+  if (l.causal) return forward_causal(v, params, wave, wave_stride, out, L, st);
+  if (int r = forward_encoder(v, params, wave, wave_stride, out, L, st)) return r;
 
   // Fused forward (default widths, non-causal, kernel_size 3; BRV_FWD_FUSE=0 selects the three-launch
   // sequence below): two launches per block instead of three. pw1_fwd
@@ -1292,140 +1791,15 @@ int brv_ctn_forward(const brv_ctn_config* cfg, const float* params, const void* 
   // second norm to the consumers. z2 never comes back from HBM in the forward pass and the fp32
   // skip accumulation (read + write of 4 B x 128 channels per frame and block) becomes one bf16
   // write per block and one pass at the end.
-  const bool fused_fwd = l.fused_fwd();
-  auto ubuf = [&](int i) { return (bf16_t*)(base + ws.u + ws.u_stride*i); };
-  const int NPu = l.Bnp + l.Scp;
-  if (fused_fwd) {
-    for (int i = 0; i < l.nb; ++i) {
-      const BlockOff& b = l.blk[i];
-      const int dil = 1 << (i % cfg->layers);
-      memset(&g, 0, sizeof(g));
-      g.W = prep + b.p_c1_f; g.T = (int)T; g.Np = l.Hp; g.Kp = l.Bnp;
-      g.Wp = prep + b.p_c1_fp; g.wp_nsl = 64;
-      g.e.out = z1buf(i); g.e.ldo = l.Hp; g.e.bias = params + b.conv_b; g.e.N = l.H;
-      g.e.stats_out = stat(1 + 2*i); g.e.stats_slope = params + b.prelu1;
-      if (i == 0) {
-        g.a = rows_bf16(xbuf(0), l.Bnp, T);
-        ProfScope prof("pw1_fwd", 2.0*BT*l.Hp*l.Bnp, 2.0*BT*(l.Bnp + l.Hp), st);
-        if (int r = launch_gemm_ws<128, 64, 1, E_STORE, 0, false, 8>(g, B, st)) return r;
-      } else {
-        const BlockOff& pb = l.blk[i - 1];
-        g.a = rows_bf16(xbuf(i - 1), l.Bnp, T);
-        g.a.p1 = ubuf(i - 1); g.a.ld1 = NPu; g.a.bs1 = T*NPu;
-        g.a.xout = xbuf(i);
-        g.a.stats = stat(2 + 2*(i - 1)); g.a.inv_n = 1.0/((double)T*l.H); g.a.eps = 1e-8f;
-        const float* lz = reinterpret_cast<const float*>(prep + pb.p_lazy);
-        g.a.lazy_v0 = lz; g.a.lazy_v1 = lz + NPu;
-        ProfScope prof("pw1_fwd", 2.0*BT*l.Hp*l.Bnp, 2.0*BT*(3*l.Bnp + l.Hp), st);
-#ifndef PW1F_NSL
-#define PW1F_NSL 64
-#define PW1F_WM 1
-#endif
-        if (int r = launch_gemm_ws<128, PW1F_NSL, PW1F_WM, E_STORE, 2, false, 8>(g, B, st)) return r;
-      }
-      memset(&g, 0, sizeof(g));
-      g.a = rows_bf16(z1buf(i), l.Hp, T);
-      g.a.slope = params + b.prelu1; g.a.stats = stat(1 + 2*i);
-      g.a.gamma = params + b.n1_g; g.a.beta = params + b.n1_b; g.a.C = l.H;
-      g.a.inv_n = 1.0/((double)T*l.H); g.a.eps = 1e-8f;
-      g.a.z2out = z2buf(i); g.a.taps = params + b.dconv_w; g.a.dbias = params + b.dconv_b;
-      g.a.slope2 = params + b.prelu2; g.a.stats2_out = stat(2 + 2*i);
-      g.a.dil = dil; g.a.left = ((l.P - 1)*dil)/2;
-      g.W = prep + b.p_rs_g; g.Wp = prep + b.p_rs_gp; g.wp_nsl = 32;
-      g.T = (int)T; g.Np = NPu; g.Kp = l.Hp;
-      g.e.out = ubuf(i); g.e.ldo = NPu; g.e.N = NPu;
-      {
-        ProfScope prof("dwpw2_fwd", 2.0*BT*l.Hp*(NPu + l.P), 2.0*BT*(2*l.Hp + NPu), st);
-        const bool old_stage = opt(BRV_OPT_DWPW2_WS);         // first version of the stage (gemm_ws.cuh AT == 3)
-        if (old_stage || l.Hp != DP_H || NPu != DP_N) {
-          if (int r = launch_gemm_ws<512, 32, 1, E_STORE, 3, false, 8>(g, B, st)) return r;
-        } else {
-          DwPw2Params dp; memset(&dp, 0, sizeof(dp));
-          dp.z1 = z1buf(i); dp.z2 = z2buf(i); dp.u = ubuf(i);
-          dp.Wp = prep + b.p_rs_gp;
-          dp.slope1 = params + b.prelu1; dp.slope2 = params + b.prelu2;
-          dp.stats1 = stat(1 + 2*i); dp.stats2 = stat(2 + 2*i);
-          dp.gamma1 = params + b.n1_g; dp.beta1 = params + b.n1_b;
-          dp.taps = params + b.dconv_w; dp.dbias = params + b.dconv_b;
-          dp.B = B; dp.T = (int)T; dp.dil = dil; dp.left = ((l.P - 1)*dil)/2; dp.C = l.H;
-          dp.inv_n = 1.0/((double)T*l.H); dp.eps = 1e-8f;
-          const int n_tiles = B*(int)((T + DP_TT - 1)/DP_TT);
-          // (a multiple of 8 workgroups: the kernel deals the tiles to the 8 XCDs in equal runs of slots)
-          const int cap = num_cus() >= 8 ? num_cus()/8*8 : 8;
-          // (one workgroup per tile for the half-batch launches of the two-chain step -- 256 tiles on 256 instead of 224
-          // workgroups, so that none walks two tiles -- measured no change: 6.49 ms either way, profiles/r05_dwpw2_ablation.txt)
-          const int n_wg = n_tiles < cap ? (n_tiles + 7)/8*8 : cap;
-          hipLaunchKernelGGL(dwpw2_fused_kernel, dim3(n_wg), dim3(512), 0, st, dp);
-          BRV_HIP_OK(hipGetLastError());
-        }
-      }
-    }
-    SkipCombineParams sc; memset(&sc, 0, sizeof(sc));
-    sc.u = ubuf(0); sc.u_stride = ws.u_stride/2; sc.stats = stats; sc.stats_stride = (long long)B*kStatStride;
-    sc.prepared = prep; sc.skip = skip; sc.nb = l.nb; sc.B = B; sc.T = (int)T; sc.Bnp = l.Bnp; sc.Scp = l.Scp;
-    sc.inv_n = 1.0/((double)T*l.H); sc.eps = 1e-8f;
-    for (int i = 0; i < l.nb; ++i) sc.lazy_off[i] = l.blk[i].p_lazy;
-    {
-      ProfScope prof("skip_combine", 0, 2.0*BT*l.Scp*l.nb + 4.0*BT*l.Scp, st);
-      int gx = (int)((T*(l.Scp/8) + 255)/256);
-      if (gx > 128) gx = 128;      // (64 / 32 / 16: 136 - 137 us as well, round 5: not the per-workgroup prologue)
-      hipLaunchKernelGGL(skip_combine_kernel, dim3(gx, B), dim3(256), 0, st, sc);
-      BRV_HIP_OK(hipGetLastError());
-    }
-  } else
-  for (int i = 0; i < l.nb; ++i) {
-    const BlockOff& b = l.blk[i];
-    const bool has_res = i < l.nb - 1;
-    const int dil = 1 << (i % cfg->layers);
-    // 1x1 conv Bn -> H (+ statistics of prelu_1 output)
-    memset(&g, 0, sizeof(g));
-    g.a = rows_bf16(xbuf(i), l.Bnp, T);
-    g.W = prep + b.p_c1_f; g.T = (int)T; g.Np = l.Hp; g.Kp = l.Bnp;
-    g.Wp = prep + b.p_c1_fp; g.wp_nsl = 64;
-    g.e.out = z1buf(i); g.e.ldo = l.Hp; g.e.bias = params + b.conv_b; g.e.N = l.H;
-    g.e.stats_out = stat(1 + 2*i); g.e.stats_slope = params + b.prelu1;
-    if (int r = launch_gemm_rows<A_BF16, E_STORE>(g, B, st, "pw1_fwd", 2.0*BT*(l.Bnp + l.Hp))) return r;
-    // prelu_1 -> gLN -> depthwise dilated conv (+ statistics of prelu_2 output)
-    DwParams d; memset(&d, 0, sizeof(d));
-    d.z1 = z1buf(i); d.z2 = z2buf(i); d.B = B; d.T = (int)T; d.Cp = l.Hp; d.C = l.H;
-    d.slope1 = params + b.prelu1; d.stats1 = stat(1 + 2*i);
-    d.gamma1 = params + b.n1_g; d.beta1 = params + b.n1_b;
-    d.inv_n = 1.0/((double)T*l.H); d.eps = 1e-8f;
-    d.taps = params + b.dconv_w; d.bias = params + b.dconv_b;
-    d.dil = dil; d.left = ((l.P - 1)*dil)/2;
-    d.stats2 = stat(2 + 2*i); d.slope2 = params + b.prelu2;
-    if (int r = dispatch_p<DwFwd>(l.P, d, st)) return r;
-    // prelu_2 -> gLN -> [res | skip] 1x1 convs, residual add, skip accumulation
-    memset(&g, 0, sizeof(g));
-    g.a = rows_bf16(z2buf(i), l.Hp, T);
-    g.a.slope = params + b.prelu2;
-    set_affine(g.a, stat(2 + 2*i), params + b.n2_g, params + b.n2_b, l.H, T);
-    const int rs0 = has_res ? l.Bnp : 0;
-    g.W = prep + b.p_rs_f; g.T = (int)T; g.Np = rs0 + l.Scp; g.Kp = l.Hp;
-    g.Wp = prep + b.p_rs_fp; g.wp_nsl = 32;
-    g.e.out = has_res ? xbuf(i + 1) : nullptr; g.e.ldo = l.Bnp;
-    g.e.bias = has_res ? params + b.res_b : nullptr; g.e.N = has_res ? l.Bn : 0;
-    g.e.Nsplit = rs0; g.e.bias2 = params + b.skip_b; g.e.N2 = l.Sc;
-    g.e.res_in = xbuf(i); g.e.ld_res = l.Bnp;
-    g.e.skip = skip; g.e.ld_skip = l.Scp; g.e.skip_init = (i == 0);
-    if (int r = launch_gemm_rows<A_BF16, E_RES_SKIP>(g, B, st, "pw2_fwd", 2.0*BT*(l.Hp + l.Bnp + rs0) + 4.0*BT*l.Scp*(i == 0 ? 1 : 2))) return r;
+  if (l.fused_fwd()) {
+    for (int i = 0; i < l.nb; ++i)
+      if (int r = forward_block_fused(v, params, i, st)) return r;
+    if (int r = forward_skip_combine(v, st)) return r;
+  } else {
+    for (int i = 0; i < l.nb; ++i)
+      if (int r = forward_block_plain(v, params, i, st)) return r;
   }
-  // prelu -> output 1x1 conv -> sigmoid -> mask * encoder output
-  memset(&g, 0, sizeof(g));
-  g.a = rows_bf16(skip, l.Scp, T);
-  g.a.slope = params + l.tcn_prelu;
-  g.W = prep + l.p_out_f; g.T = (int)T; g.Np = l.S*l.Np; g.Kp = l.Scp;
-  g.e.out = y; g.e.ldo = l.Np; g.e.bias = params + l.out_b; g.e.N = l.N;
-  g.e.w_in = w; g.e.ld_w = l.Np; g.e.m_out = m; g.e.S = l.S; g.e.Np_src = l.Np;
-  if (int r = launch_gemm_rows<A_F32, E_MASK>(g, B, st, "mask_fwd", 4.0*BT*l.Scp + 2.0*BT*l.Np*(1 + 2*l.S))) return r;
-  // decoder: synthesis filterbank + overlap-add, cropped to the input length
-  memset(&g, 0, sizeof(g));
-  g.a = rows_bf16(y, l.Np, T);
-  g.W = prep + l.p_dec_f; g.T = (int)T; g.Np = l.Kfp; g.Kp = l.Np;
-  g.e.wave_out = out; g.e.hop = l.hop; g.e.Kf = l.K; g.e.wave_stride = L;
-  g.e.wave_len = (int)L;
-  if (int r = launch_gemm_rows<A_BF16, E_OLA>(g, B*l.S, st, "dec_fwd", 2.0*BT*l.S*l.Np + 4.0*B*l.S*L)) return r;
-  return 0;
+  return forward_decoder(v, params, out, L, st);
 }
 
 // Block range of part `part` of `nparts`: the backward pass walks the blocks from the last to
@@ -1459,159 +1833,6 @@ int brv_ctn_grad_bucket(const brv_ctn_config* cfg, int32_t part, int32_t nparts,
   return 0;
 }
 
-}  // extern "C"
-
-// Deferred weight gradients of blocks [blk_lo, blk_hi] (the data-gradient chain of these blocks has
-// run on a stream this one is ordered after): two grouped launches.
-static int deferred_wgrads(const Layout& l, const Workspace& ws, char* base, const bf16_t* prep,
-                           const float* params, float* grads, double* stats, double* sums, int B, long long T,
-                           int blk_lo, int blk_hi, hipStream_t st) {
-  const double BT = (double)B*(double)T;
-  auto stat = [&](int i) { return stats + (long long)i*B*kStatStride; };
-  auto xbuf = [&](int i) { return (bf16_t*)(base + ws.x + ws.x_stride*i); };
-  auto z2buf = [&](int i) { return (bf16_t*)(base + ws.z2 + ws.z_stride*i); };
-  auto eBbuf = [&](int i) { return (bf16_t*)(base + ws.eB + ws.eB_stride*i); };
-  auto gcopy = [&](int i) { return (bf16_t*)(base + ws.gcopy + ws.gcopy_stride*i); };
-  bf16_t* gskip = (bf16_t*)(base + ws.gskip);
-  const int ldg = l.Bnp + l.Scp;
-  WgradParams wg;
-  // deferred weight gradients of this part's blocks: two grouped launches
-  // residual / skip convs of every block in ONE launch when the padded widths are the
-  // default 128 | 128 (gemm_wgrad_full.cuh); other architectures use the generic path
-  const bool full_rs = l.Bnp == 128 && l.Scp == 128 && l.Hp % W2_BH == 0 && l.nb <= kWgMaxProb &&
-                       !opt(BRV_OPT_NO_WGRAD_FULL);
-  if (full_rs && blk_lo <= blk_hi) {
-    WgradFullParams fp; memset(&fp, 0, sizeof(fp));
-    const int nblk = blk_hi - blk_lo + 1;
-    fp.B = B; fp.T = (int)T; fp.nprob = nblk; fp.n_htiles = l.Hp/W2_BH;
-    fp.ldg0 = l.Bnp; fp.bsg0 = T*l.Bnp; fp.ldg1 = ldg; fp.bsg1 = T*ldg;
-    fp.ldh = l.Hp; fp.bsh = T*l.Hp;
-    fp.N0 = l.Bn; fp.N1 = l.Sc; fp.Kout = l.H; fp.ldo = l.H;
-    fp.inv_n = 1.0/((double)T*l.H); fp.eps = 1e-8f;
-    for (int i = blk_lo; i <= blk_hi; ++i) {
-      const BlockOff& b = l.blk[i];
-      WgradProb& pr = fp.prob[i - blk_lo];
-      const bool has_res = i < l.nb - 1;
-      pr.g0 = has_res ? gcopy(i) : nullptr; pr.g1 = gskip; pr.h = z2buf(i);
-      pr.out0 = has_res ? grads + b.res_w : nullptr; pr.out1 = grads + b.skip_w;
-      pr.gbias0 = has_res ? grads + b.res_b : nullptr; pr.gbias1 = grads + b.skip_b;
-      pr.slope = params + b.prelu2; pr.stats = stat(2 + 2*i);
-      pr.gamma = params + b.n2_g; pr.beta = params + b.n2_b;
-    }
-    ProfScope prof("pw2_wgrad", 2.0*nblk*BT*(double)(l.Bnp + l.Scp)*l.Hp,
-                   2.0*BT*(l.Bnp + l.Scp + l.Hp)*nblk, st);
-#ifdef BRV_DIAG
-    if (const char* d = getenv("BRV_DBG_WG")) fp.dbg = atoi(d);
-#endif
-    // 24 blocks x 8 H slices = 192 owners would leave a quarter of the CUs idle: the items are
-    // divided over kWgSplit workgroups each (768 = 3 full rounds) when the batch allows
-    fp.n_split = (B >= kWgSplit && !opt(BRV_OPT_NO_WGRAD_SPLIT)) ? kWgSplit : 1;
-    fp.part = reinterpret_cast<float*>(base + ws.wgpart);
-    const bool wide = !opt(BRV_OPT_NO_WGRAD_128) && l.Hp % W3_BH == 0;
-    if (wide) {
-      // 128 H channels per workgroup: 24 blocks x 4 slices; 8 item splits at the whole batch (768 workgroups), 4
-      // when this call is one of two half-batch chains (384 each)
-      fp.n_htiles = l.Hp/W3_BH;
-      if (fp.n_split > 1 && B >= 4*kWgSplit) fp.n_split = 2*kWgSplit;
-      const int grid = 8*ceil_div(nblk, 8)*fp.n_htiles*fp.n_split;
-      hipLaunchKernelGGL(wgrad_full128_kernel, dim3(grid), dim3(64*W2_NW), 0, st, fp);
-    } else {
-      const int grid = 8*ceil_div(nblk, 8)*fp.n_htiles*fp.n_split;
-      hipLaunchKernelGGL(wgrad_full_kernel, dim3(grid), dim3(64*W2_NW), 0, st, fp);
-    }
-    if (fp.n_split > 1)
-      hipLaunchKernelGGL(wgrad_full_reduce_kernel, dim3(128, (unsigned)nblk), dim3(256), 0, st, fp);
-    BRV_HIP_OK(hipGetLastError());
-  }
-  for (int i0 = blk_lo; i0 <= blk_hi; i0 += kWgMaxProb) {
-    const int n = std::min(kWgMaxProb, blk_hi + 1 - i0);
-    // [res | skip]: G = [g_out_i | g_skip], H = gLN_2(prelu_2(z2_i)); the last block has
-    // no residual conv, so it goes in a launch of its own (different G width)
-    WgradGroupParams gp; memset(&gp, 0, sizeof(gp));
-    WgradParams& q = gp.base;
-    q.g = rows_bf16(nullptr, l.Bnp, T); q.g.K0 = l.Bnp;
-    q.g.ld1 = ldg; q.g.bs1 = T*ldg;
-    q.h = rows_bf16(nullptr, l.Hp, T);
-    set_affine(q.h, nullptr, nullptr, nullptr, l.H, T);
-    q.B = B; q.T = (int)T; q.Gp = l.Bnp + l.Scp; q.Hp = l.Hp;
-    q.G0p = l.Bnp; q.N0 = l.Bn; q.N1 = l.Sc; q.Kout = l.H; q.ldo = l.H;
-    int np = 0;
-    for (int i = i0; i < i0 + n; ++i) {
-      if (i == l.nb - 1) continue;
-      const BlockOff& b = l.blk[i];
-      WgradProb& pr = gp.prob[np++];
-      pr.g0 = gcopy(i); pr.g1 = gskip; pr.h = z2buf(i);
-      pr.out0 = grads + b.res_w; pr.out1 = grads + b.skip_w;
-      pr.gbias0 = grads + b.res_b; pr.gbias1 = grads + b.skip_b;
-      pr.slope = params + b.prelu2; pr.stats = stat(2 + 2*i);
-      pr.gamma = params + b.n2_g; pr.beta = params + b.n2_b;
-    }
-    gp.nprob = np;
-    if (np > 0 && !full_rs)
-      if (int r = launch_wgrad_group<A_BF16>(gp, st, "pw2_wgrad",
-                                             2.0*BT*(l.Bnp + l.Scp + l.Hp))) return r;
-    if (i0 + n == l.nb && !full_rs) {             // last block: skip conv only
-      const BlockOff& b = l.blk[l.nb - 1];
-      memset(&wg, 0, sizeof(wg));
-      wg.g = rows_bf16(gskip, ldg, T);
-      wg.h = rows_bf16(z2buf(l.nb - 1), l.Hp, T); wg.h.slope = params + b.prelu2;
-      set_affine(wg.h, stat(2 + 2*(l.nb - 1)), params + b.n2_g, params + b.n2_b, l.H, T);
-      wg.B = B; wg.T = (int)T; wg.Gp = l.Scp; wg.Hp = l.Hp;
-      wg.out1 = grads + b.skip_w; wg.G0p = 0; wg.N0 = 0; wg.N1 = l.Sc;
-      wg.Kout = l.H; wg.ldo = l.H; wg.gbias1 = grads + b.skip_b;
-      if (int r = launch_wgrad<A_BF16>(wg, st, "pw2_wgrad", 2.0*BT*(l.Scp + l.Hp))) return r;
-    }
-    // first 1x1 conv: G = dz1_i, H = x_i
-    memset(&gp, 0, sizeof(gp));
-    WgradParams& q1 = gp.base;
-    q1.g = rows_bf16(nullptr, l.Hp, T); q1.h = rows_bf16(nullptr, l.Bnp, T);
-    q1.B = B; q1.T = (int)T; q1.Gp = l.Hp; q1.Hp = l.Bnp;
-    q1.G0p = l.Hp; q1.N0 = l.H; q1.Kout = l.Bn; q1.ldo = l.Bn;
-    for (int i = i0; i < i0 + n; ++i) {
-      const BlockOff& b = l.blk[i];
-      WgradProb& pr = gp.prob[i - i0];
-      pr.g0 = eBbuf(i); pr.h = xbuf(i);
-      pr.out0 = grads + b.conv_w; pr.gbias0 = grads + b.conv_b;
-    }
-    gp.nprob = n;
-    if (l.pw1_rc() && pw1_rc_wgrad()) {
-      // dz1 was never written: rebuilt from e1 (kept per block in eB) and x inside the product
-      Pw1WgradRcParams rp; memset(&rp, 0, sizeof(rp));
-      rp.B = B; rp.T = (int)T; rp.nprob = n; rp.C = l.H; rp.Kout = l.Bn; rp.ldo = l.Bn;
-      rp.lde = l.Hp; rp.ldx = l.Bnp; rp.bse = T*l.Hp; rp.bsx = T*l.Bnp;
-      rp.inv_n = 1.0/((double)T*l.H); rp.eps = 1e-8f;
-      for (int i = i0; i < i0 + n; ++i) {
-        const BlockOff& b = l.blk[i];
-        Pw1WgradRcProb& pr = rp.prob[i - i0];
-        pr.e1 = eBbuf(i); pr.x = xbuf(i); pr.Wfp = prep + b.p_c1_fp; pr.bias = params + b.conv_b;
-        pr.out = grads + b.conv_w; pr.gbias = grads + b.conv_b;
-        pr.stats = stat(1 + 2*i); pr.sums = sums + (long long)(1 + 2*i)*B*kStatStride; pr.slope = params + b.prelu1;
-      }
-      const int tiles = l.Hp/WG_BG;
-      int ns = B;                                  // item-aligned splits (as the stored-dz1 launch)
-      while (tiles*n*ns > 2048 && ns % 2 == 0) ns /= 2;
-      if (t_opts->wg_target > 0) ns = ceil_div(t_opts->wg_target, tiles*n);
-      const int total = B*ceil_div((int)T, WG_BT);
-      if (ns > total) ns = total;
-      if (ns < 1) ns = 1;
-      rp.nsplit = ns;
-      ProfScope prof("pw1_wgrad", 2.0*n*BT*(double)l.Hp*l.Bnp*2, 2.0*BT*(l.Hp + l.Bnp)*n, st);
-      hipLaunchKernelGGL(pw1_wgrad_rc_kernel, dim3(tiles, ns, n), dim3(256), 0, st, rp);
-      BRV_HIP_OK(hipGetLastError());
-    }
-    // (The owner-computes kernel of the [res | skip] gradient was tried for this product too -- 256 of dz1's channels
-    // as its DMA'd operand, x as the 128-wide one, two launches of 24 problems: 580 us against the 429 us of the
-    // grouped 128 x 128 tiles below: with one item per workgroup its 136 KB zero fill and 128 KB partial tile are
-    // no longer amortised. profiles/r05_wgrad128.txt)
-    else
-    if (int r = launch_wgrad_group<A_BF16>(gp, st, "pw1_wgrad", 2.0*BT*(l.Hp + l.Bnp), -1))
-      return r;
-  }
-  return 0;
-}
-
-extern "C" {
-
 int brv_ctn_backward(const brv_ctn_config* cfg, const float* params, const void* prepared,
                      void* workspace, const float* wave, int64_t wave_stride, const float* d_out,
                      float* grads, int64_t batch, int64_t length, const brv_launch_opts* opts,
@@ -1633,286 +1854,28 @@ int brv_ctn_backward_part(const brv_ctn_config* cfg, const float* params, const 
   const long long T = l.frames(L);
   if (B < 1 || T < 1) return fail(-1, "empty batch or input shorter than one frame");
   if (nparts < 1 || part < 0 || part >= nparts) return fail(-1, "bad part");
+  const Views v(l, workspace, prepared, B, T);
   if (l.causal) {
     if (part != nparts - 1) return 0;
-    return backward_causal(l, cfg, params, prepared, workspace, wave, wave_stride, d_out, grads, B, L, T, st);
+    return backward_causal(v, params, wave, wave_stride, d_out, grads, L, st);
   }
   int blk_lo, blk_hi; part_range(l.nb, part, nparts, blk_lo, blk_hi);
   const bool head = part == 0, tail = part == nparts - 1;
-  Workspace ws; ws.init(l, B, T);
-  const double BT = (double)B*(double)T;
-  char* base = (char*)workspace;
-  const bf16_t* prep = (const bf16_t*)prepared;
-  double* stats = (double*)(base + ws.stats);
-  double* sums = (double*)(base + ws.sums);
-  auto stat = [&](int i) { return stats + (long long)i*B*kStatStride; };
-  auto sum = [&](int i) { return sums + (long long)i*B*kStatStride; };
-  bf16_t* w = (bf16_t*)(base + ws.w);
-  auto xbuf = [&](int i) { return (bf16_t*)(base + ws.x + ws.x_stride*i); };
-  auto z1buf = [&](int i) { return (bf16_t*)(base + ws.z1 + ws.z_stride*i); };
-  auto z2buf = [&](int i) { return (bf16_t*)(base + ws.z2 + ws.z_stride*i); };
-  float* skip = (float*)(base + ws.skip);
-  bf16_t* m = (bf16_t*)(base + ws.m);
-  bf16_t* y = (bf16_t*)(base + ws.y);
-  bf16_t* dpre = (bf16_t*)(base + ws.dpre);
-  bf16_t* dw1 = (bf16_t*)(base + ws.dw1);
-  bf16_t* gskip = (bf16_t*)(base + ws.gskip);
-  bf16_t* gout = (bf16_t*)(base + ws.gout);
-  const int ldg = l.Bnp + l.Scp;           // row stride of [g_out | g_skip]
-  bf16_t* eA = (bf16_t*)(base + ws.eA);
-  auto eBbuf = [&](int i) { return (bf16_t*)(base + ws.eB + ws.eB_stride*i); };
-  auto gcopy = [&](int i) { return (bf16_t*)(base + ws.gcopy + ws.gcopy_stride*i); };
-  bf16_t* e0 = (bf16_t*)(base + ws.e0);
-  bf16_t* dwt = (bf16_t*)(base + ws.dwt);
-  const int BS = B*l.S;
-  float* vg = (float*)(base + ws.vg);
-  const long long vper = (long long)l.H*(5 + l.P);
-  auto vslot = [&](int i) { return vg + 2LL*l.N + vper*i; };   // block i's vector grads
-  float* vslope = vg + 2LL*l.N + vper*l.nb;    // PReLU slope grads: tcn, then (prelu1, prelu2) per block
-
-  auto ubuf = [&](int i) { return (bf16_t*)(base + ws.u + ws.u_stride*i); };
   // Backward mirror of the fused forward (bwd_fused.cuh; BRV_BWD_FUSE=0: three launches per block):
   // needs the u tensors the fused forward stored and the default widths
   const bool bwd_fused = l.fused_fwd() && bwd_fuse_requested() && l.Bnp == 128 && l.Scp == 128 &&
                          l.Hp % HL_CG == 0 && !opt(BRV_OPT_NO_DZ_FUSE) && bf_frames_ok(T);
-
-  GemmRowsParams g; WgradParams wg;
-  if (head) {
-  // sums and replica block <- 0; a workspace filled by a forward call in the other mode -> NaN sums (and with
-  // them NaN gradients)
-  if (int r = launch_call_init(sums, (long long)(ws.stats_bytes/8), vg, (long long)ws.vg_bytes,
-                               reinterpret_cast<const int*>(base + ws.stamp), mode_stamp(l.fused_fwd()), nullptr, 0, st))
-    return fail(r, "backward: call_init launch");
-  // decoder data gradient (framing of d_out) fused with the mask backward
-  memset(&g, 0, sizeof(g));
-  g.a = frames_of(d_out, L, l.hop, l.K);
-  g.W = prep + l.p_dec_b; g.T = (int)T; g.Np = l.Np; g.Kp = l.Kfp;
-  g.e.out = dpre; g.e.ldo = l.Np; g.e.out2 = dw1; g.e.w_in = w; g.e.ld_w = l.Np;
-  g.e.m_in = m; g.e.S = l.S;
-  if (int r = launch_gemm_rows<A_FRAMES, E_MASK_BWD>(g, BS, st, "dec_bwd", 4.0*BS*L + 2.0*BT*l.Np*(1 + 3*l.S))) return r;
-  // decoder weight gradient: y^T * frames(d_out)
-  memset(&wg, 0, sizeof(wg));
-  wg.g = rows_bf16(y, l.Np, T); wg.h = frames_of(d_out, L, l.hop, l.K);
-  wg.B = BS; wg.T = (int)T; wg.Gp = l.Np; wg.Hp = l.Kfp;
-  wg.out0 = grads + l.dec_w; wg.G0p = l.Np; wg.N0 = l.N; wg.Kout = l.K; wg.ldo = l.K;
-  if (int r = launch_wgrad<A_FRAMES>(wg, st, "wgrad_dec", 2.0*BT*l.S*l.Np + 4.0*BS*L, 768)) return r;
-  // output conv data gradient, PReLU backward -> gradient wrt skip_sum
-  memset(&g, 0, sizeof(g));
-  g.a = rows_bf16(dpre, l.Np, T); g.a.nsrc = l.S;
-  g.W = prep + l.p_out_b; g.T = (int)T; g.Np = l.Scp; g.Kp = l.S*l.Np;
-  g.e.out = gskip; g.e.ldo = ldg; g.e.src_f32 = skip; g.e.ld_srcf = l.Scp;
-  g.e.src_slope = params + l.tcn_prelu; g.e.dslope = vslope;
-  g.e.rep_stride = ws.vg_stride; g.e.n_rep = kReplicas;
-  if (int r = launch_gemm_rows<A_BF16, E_PRELU_BWD>(g, B, st, "mask_bwd", 2.0*BT*l.S*l.Np + 6.0*BT*l.Scp)) return r;
-  if (bwd_fused) {
-    // fused backward: the layer-norm backward means of the LAST block from g_skip and its stored u
-    // (every other block gets them from the kernel that produces its g_out, E_ADD epilogue below)
-    GuDotsParams gu; memset(&gu, 0, sizeof(gu));
-    gu.g = gskip; gu.ldg = ldg; gu.u = ubuf(l.nb - 1) + l.Bnp; gu.ldu = ldg;
-    gu.v1 = reinterpret_cast<const float*>(prep + l.blk[l.nb - 1].p_lazy) + ldg + l.Bnp;
-    gu.ncols = l.Scp; gu.B = B; gu.T = (int)T; gu.out = sum(2 + 2*(l.nb - 1));
-    ProfScope prof("gu_dots", 0, 4.0*BT*l.Scp, st);
-    int gx = (int)((T*(l.Scp/8) + 255)/256);
-    if (gx > 64) gx = 64;
-    hipLaunchKernelGGL(gu_dots_kernel, dim3(gx, B), dim3(256), 0, st, gu);
-    BRV_HIP_OK(hipGetLastError());
-  }
-  // output conv weight / bias gradients, one source at a time
-  for (int s = 0; s < l.S; ++s) {
-    memset(&wg, 0, sizeof(wg));
-    wg.g = rows_bf16(dpre + (long long)s*T*l.Np, l.Np, T); wg.g.bs0 = (long long)l.S*T*l.Np;
-    wg.h = rows_bf16(skip, l.Scp, T); wg.h.slope = params + l.tcn_prelu;
-    wg.B = B; wg.T = (int)T; wg.Gp = l.Np; wg.Hp = l.Scp;
-    wg.out0 = grads + l.out_w + (long long)s*l.N*l.Sc; wg.G0p = l.Np; wg.N0 = l.N;
-    wg.Kout = l.Sc; wg.ldo = l.Sc; wg.gbias0 = grads + l.out_b + (long long)s*l.N;
-    if (int r = launch_wgrad<A_F32>(wg, st, "wgrad_out", 2.0*BT*l.Np + 4.0*BT*l.Scp, 256)) return r;
-  }
-  }   // head
-
+  if (head)
+    if (int r = backward_head(v, params, d_out, grads, L, bwd_fused, st)) return r;
   // (Running the deferred weight gradients of block chunks on a side stream next to the data-gradient
   // chain was measured slower at every chunk count -- DESIGN.md 5g -- and is gone.)
-  const int n_chunks = 1;
-  auto wgrads = [&](int blk_lo, int blk_hi, hipStream_t st) -> int {
-    return deferred_wgrads(l, ws, base, prep, params, grads, stats, sums, B, T, blk_lo, blk_hi, st);
-  };
-  const int n_blk_call = blk_hi - blk_lo + 1;
-  for (int ch = n_chunks - 1; ch >= 0; --ch) {
-  const int c_lo = blk_lo + (int)((long long)n_blk_call*ch/n_chunks);
-  const int c_hi = blk_lo + (int)((long long)n_blk_call*(ch + 1)/n_chunks) - 1;
-  for (int i = c_hi; i >= c_lo; --i) {
-    const BlockOff& b = l.blk[i];
-    const bool has_res = i < l.nb - 1;
-    const int dil = 1 << (i % cfg->layers);
-    const int rs0 = has_res ? l.Bnp : 0;
-    const bool blk_fused = bwd_fused && (((l.P - 1)*dil)/2) % dil == 0;
-    if (!blk_fused) {
-    // [res | skip] data gradient + gLN_2 backward partials
-    memset(&g, 0, sizeof(g));
-    g.a = rows_bf16(has_res ? gout : gskip, ldg, T);
-    g.W = prep + b.p_rs_b; g.T = (int)T; g.Np = l.Hp; g.Kp = rs0 + l.Scp;
-    g.Wp = prep + b.p_rs_bp; g.wp_nsl = 32;
-    g.e.out = eA; g.e.ldo = l.Hp; g.e.N = l.H;
-    g.e.src = z2buf(i); g.e.ld_src = l.Hp; g.e.src_slope = params + b.prelu2;
-    g.e.src_stats = stat(2 + 2*i); g.e.inv_n = 1.0/((double)T*l.H); g.e.eps = 1e-8f;
-    g.e.gamma = params + b.n2_g;
-    g.e.dgamma = vslot(i) + 2*l.H; g.e.dbeta = vslot(i) + 3*l.H;
-    g.e.rep_stride = ws.vg_stride; g.e.n_rep = kReplicas;
-    g.e.sums_out = sum(2 + 2*i);
-    if (int r = launch_gemm_rows<A_BF16, E_GLN_BWD>(g, B, st, "pw2_dgrad", 2.0*BT*(rs0 + l.Scp + 2*l.Hp))) return r;
-    }
-    // gLN_2 + prelu_2 backward: fused into the depthwise backward below when its LDS window
-    // (tile + halo rows) fits -- dz2 is then built once per element in LDS and never written
-    // (dwconv_bwd_halo_kernel). BRV_NO_DZ_FUSE keeps the separate pass.
-    const bool fuse_dz2 = blk_fused || (!opt(BRV_OPT_NO_DZ_FUSE) && l.Hp % HL_CG == 0 &&
-                          (((l.P - 1)*dil)/2) % dil == 0 && hl_window_rows(dil, l.P) <= HL_MAXROWS);
-    DzParams dz; memset(&dz, 0, sizeof(dz));
-    if (!fuse_dz2) {
-      dz.e = eA; dz.z = z2buf(i); dz.B = B; dz.T = (int)T; dz.Cp = l.Hp; dz.C = l.H;
-      dz.slope = params + b.prelu2; dz.stats = stat(2 + 2*i); dz.sums = sum(2 + 2*i);
-      dz.inv_n = 1.0/((double)T*l.H); dz.eps = 1e-8f; dz.dslope = vslope + 2 + 2*i; dz.rep_stride = ws.vg_stride;
-      if (int r = launch_dz(dz, st)) return r;
-    }
-    // depthwise conv backward (data, taps, bias) + gLN_1 partials
-    DwParams d; memset(&d, 0, sizeof(d));
-    bf16_t* eB = eBbuf(i);
-    d.z1 = z1buf(i); d.dz2 = eA; d.e1 = eB; d.B = B; d.T = (int)T; d.Cp = l.Hp; d.C = l.H;
-    d.slope1 = params + b.prelu1; d.stats1 = stat(1 + 2*i);
-    d.gamma1 = params + b.n1_g; d.beta1 = params + b.n1_b;
-    d.inv_n = 1.0/((double)T*l.H); d.eps = 1e-8f;
-    d.taps = params + b.dconv_w; d.dil = dil; d.left = ((l.P - 1)*dil)/2;
-    d.dgamma1 = vslot(i); d.dbeta1 = vslot(i) + l.H;
-    d.dtaps = vslot(i) + 4*l.H; d.dbias = vslot(i) + 4*l.H + (long long)l.H*l.P;
-    d.rep_stride = ws.vg_stride; d.sums1 = sum(1 + 2*i);
-    if (fuse_dz2) {
-      d.z2in = z2buf(i); d.stats2 = stat(2 + 2*i); d.sums2 = sum(2 + 2*i);
-      d.slope2 = params + b.prelu2; d.dslope2 = vslope + 2 + 2*i;
-    }
-    if (blk_fused) {
-      BwdFusedParams bf; memset(&bf, 0, sizeof(bf));
-      bf.d = d; bf.d.dz2 = nullptr;
-      bf.g = has_res ? gout : gskip; bf.ldg = ldg; bf.Kg = rs0 + l.Scp;
-      bf.Wp = prep + b.p_rs_bp; bf.gamma2 = params + b.n2_g;
-      bf.dgamma2 = vslot(i) + 2*l.H; bf.dbeta2 = vslot(i) + 3*l.H;
-      if (int r = DwBwdFused<3>::run(bf, st)) return r;      // (fused_fwd() implies kernel_size 3)
-    } else
-    if (int r = dispatch_p<DwBwd>(l.P, d, st)) return r;
-    // gLN_1 + prelu_1 backward -> dz1: fused into the A staging of the data-gradient GEMM
-    // below (A_DZ: dz1 is computed from e1 and z1 on load and written back over e1 for the
-    // deferred weight gradient); BRV_NO_DZ1_FUSE keeps the separate pass
-    // (needs one n-tile: the workgroup that stages an A element must be its only reader)
-    const bool fuse_dz1 = !opt(BRV_OPT_NO_DZ1_FUSE) && (l.Bnp == 128 || l.Bnp == 64);
-    if (!fuse_dz1) {
-      memset(&dz, 0, sizeof(dz));
-      dz.e = eB; dz.z = z1buf(i); dz.B = B; dz.T = (int)T; dz.Cp = l.Hp; dz.C = l.H;
-      dz.slope = params + b.prelu1; dz.stats = stat(1 + 2*i); dz.sums = sum(1 + 2*i);
-      dz.inv_n = 1.0/((double)T*l.H); dz.eps = 1e-8f; dz.dslope = vslope + 1 + 2*i; dz.rep_stride = ws.vg_stride;
-      if (int r = launch_dz(dz, st)) return r;
-    }
-    // first 1x1 conv: data gradient + residual path -> gradient wrt block input
-    memset(&g, 0, sizeof(g));
-    g.a = rows_bf16(eB, l.Hp, T);
-    g.W = prep + b.p_c1_b; g.T = (int)T; g.Np = l.Bnp; g.Kp = l.Hp;
-    g.e.out = gout; g.e.ldo = ldg; g.e.add_in = has_res ? gout : nullptr; g.e.ld_add = ldg;
-    // block i-1's deferred [res | skip] weight gradient needs this g_out after gout is
-    // overwritten again: keep a copy (16 MB per block at the BASELINE size)
-    g.e.out2 = i > 0 ? gcopy(i - 1) : nullptr; g.e.ld_srcf = l.Bnp;
-    if (bwd_fused && i > 0) {        // block i - 1's layer-norm backward means, from its g and u
-      g.e.gu_u = ubuf(i - 1); g.e.ld_gu = ldg; g.e.gu_gskip = gskip; g.e.ld_gs = ldg;
-      g.e.gu_v1 = reinterpret_cast<const float*>(prep + l.blk[i - 1].p_lazy) + ldg;
-      g.e.gu_out = sum(2 + 2*(i - 1));
-    }
-    if (fuse_dz1 && l.pw1_rc()) {
-      Pw1DgradRcParams rp; memset(&rp, 0, sizeof(rp));
-      rp.e1 = eB; rp.lde = l.Hp; rp.bse = T*l.Hp;
-      rp.x = xbuf(i); rp.ldx = l.Bnp; rp.bsx = T*l.Bnp;
-      rp.Wfp = prep + b.p_c1_fp; rp.bias = params + b.conv_b; rp.Wb = prep + b.p_c1_b;
-      rp.stats = stat(1 + 2*i); rp.sums = sum(1 + 2*i); rp.slope = params + b.prelu1;
-      rp.inv_n = 1.0/((double)T*l.H); rp.eps = 1e-8f; rp.C = l.H;
-      rp.T = (int)T; rp.n_ttiles = ceil_div((int)T, RC_BM); rp.batch = B;
-      rp.e = g.e;
-      rp.e.dslope = vslope + 1 + 2*i; rp.e.rep_stride = ws.vg_stride; rp.e.n_rep = kReplicas;
-      if (opt(BRV_OPT_PW1_RC_TILES)) {        // first form: one tile per workgroup, weights re-read per tile
-        ProfScope prof("pw1_dgrad", 2.0*BT*(double)l.Hp*l.Bnp*2,
-                       2.0*BT*(l.Hp + l.Bnp*(has_res ? 3 : 2)), st);
-        hipLaunchKernelGGL(pw1_dgrad_rc_kernel, dim3(rp.n_ttiles*B), dim3(256), 0, st, rp);
-      } else {
-        Pw1DgradWsParams wp; wp.r = rp;
-        wp.dz_out = pw1_rc_wgrad() ? nullptr : eB;      // stored-dz1 weight gradient: dz1 over e1, in place
-        wp.dbg = nullptr;
-#ifdef WSD_STAMP
-        wp.dbg = debug_buffer();
-#endif
-        // algorithmic bytes: e1 and x in (+ the residual g_out), dz1 and the new g_out out -- and the companions the
-        // row-wise epilogue streams: the copy of g_out kept for block i - 1's weight gradient and, for that block's
-        // layer-norm backward means, its u ([res | skip] wide) and g_skip rows (the line understated
-        // the kernel by 2 BT 384; PMC 244.8 MB per launch = this count)
-        const double companions = (i > 0 ? l.Bnp : 0) + (bwd_fused && i > 0 ? (double)l.Bnp + 2.0*l.Scp : 0.0);
-        ProfScope prof("pw1_dgrad", 2.0*BT*(double)l.Hp*l.Bnp*2,
-                       2.0*BT*(l.Hp*(wp.dz_out ? 2 : 1) + l.Bnp*(has_res ? 3 : 2) + companions), st);
-        int grid = num_cus();
-        const int total = ceil_div((int)T, WSD_TF)*B;
-        if (grid > total) grid = total;
-        if (l.H == RC_H) hipLaunchKernelGGL(pw1_dgrad_ws_kernel<true>, dim3(grid), dim3(512), 0, st, wp);
-        else hipLaunchKernelGGL(pw1_dgrad_ws_kernel<false>, dim3(grid), dim3(512), 0, st, wp);
-      }
-      BRV_HIP_OK(hipGetLastError());
-      continue;
-    }
-    if (fuse_dz1) {
-      g.a.p1 = z1buf(i); g.a.ld1 = l.Hp; g.a.bs1 = T*l.Hp;
-      g.a.slope = params + b.prelu1; g.a.stats = stat(1 + 2*i); g.a.sums = sum(1 + 2*i);
-      g.a.inv_n = 1.0/((double)T*l.H); g.a.eps = 1e-8f; g.a.C = l.H;
-      g.e.dslope = vslope + 1 + 2*i; g.e.rep_stride = ws.vg_stride; g.e.n_rep = kReplicas;
-      if (int r = launch_gemm_rows<A_DZ, E_ADD>(g, B, st, "pw1_dgrad", 2.0*BT*(3*l.Hp + l.Bnp*(has_res ? 2 : 1)))) return r;
-      continue;
-    }
-    if (int r = launch_gemm_rows<A_BF16, E_ADD>(g, B, st, "pw1_dgrad", 2.0*BT*(l.Hp + l.Bnp*(has_res ? 2 : 1)))) return r;
-  }
-    if (int r = wgrads(c_lo, c_hi, st)) return r;
-  }   // chunks
-  if (tail) {
-  // bottleneck conv: data gradient + first gLN backward partials
-  memset(&g, 0, sizeof(g));
-  g.a = rows_bf16(gout, ldg, T);
-  g.W = prep + l.p_bott_b; g.T = (int)T; g.Np = l.Np; g.Kp = l.Bnp;
-  g.e.out = e0; g.e.ldo = l.Np; g.e.N = l.N;
-  g.e.src = w; g.e.ld_src = l.Np; g.e.src_stats = stat(0);
-  g.e.inv_n = 1.0/((double)T*l.N); g.e.eps = 1e-8f;
-  g.e.gamma = params + l.ln_g; g.e.dgamma = vg; g.e.dbeta = vg + l.N;
-  g.e.rep_stride = ws.vg_stride; g.e.n_rep = kReplicas;
-  g.e.sums_out = sum(0);
-  if (int r = launch_gemm_rows<A_BF16, E_GLN_BWD>(g, B, st, "bottleneck_dgrad", 2.0*BT*(l.Bnp + 2*l.Np))) return r;
-  // bottleneck conv: weight / bias gradients against gLN(w)
-  memset(&wg, 0, sizeof(wg));
-  wg.g = rows_bf16(gout, ldg, T); wg.h = rows_bf16(w, l.Np, T);
-  set_affine(wg.h, stat(0), params + l.ln_g, params + l.ln_b, l.N, T);
-  wg.B = B; wg.T = (int)T; wg.Gp = l.Bnp; wg.Hp = l.Np;
-  wg.out0 = grads + l.bott_w; wg.G0p = l.Bnp; wg.N0 = l.Bn; wg.Kout = l.N; wg.ldo = l.N;
-  wg.gbias0 = grads + l.bott_b;
-  if (int r = launch_wgrad<A_BF16>(wg, st, "bottleneck_wgrad", 2.0*BT*(l.Bnp + l.Np), 256)) return r;
-  // total gradient wrt the encoder output
-  CombineParams cb; memset(&cb, 0, sizeof(cb));
-  cb.e0 = e0; cb.w = w; cb.dw1 = dw1; cb.dw = dwt; cb.B = B; cb.T = (int)T;
-  cb.Cp = l.Np; cb.C = l.N; cb.S = l.S; cb.stats = stat(0); cb.sums = sum(0);
-  cb.inv_n = 1.0/((double)T*l.N); cb.eps = 1e-8f;
-  {
-    const long long per_item = T*(l.Np/8);
-    int gx = (int)((per_item + 1023)/1024);
-    if (gx > 2048) gx = 2048;
-    if (gx < 1) gx = 1;
-    ProfScope prof("gln0_bwd", 0, 2.0*BT*l.Np*(3 + l.S), st);
-    hipLaunchKernelGGL(gln0_bwd_combine_kernel, dim3(gx, B), dim3(256), 0, st, cb);
-    BRV_HIP_OK(hipGetLastError());
-  }
-  // encoder weight gradient: dw^T * frames(wave)
-  memset(&wg, 0, sizeof(wg));
-  wg.g = rows_bf16(dwt, l.Np, T); wg.h = frames_of(wave, L, l.hop, l.K, wave_stride);
-  wg.B = B; wg.T = (int)T; wg.Gp = l.Np; wg.Hp = l.Kfp;
-  wg.out0 = grads + l.enc_w; wg.G0p = l.Np; wg.N0 = l.N; wg.Kout = l.K; wg.ldo = l.K;
-  if (int r = launch_wgrad<A_FRAMES>(wg, st, "wgrad_enc", 2.0*BT*l.Np + 4.0*B*L, 768)) return r;
-  }   // tail
+  for (int i = blk_hi; i >= blk_lo; --i)
+    if (int r = backward_block(v, params, i, bwd_fused, st)) return r;
+  if (int r = deferred_wgrads(v, params, grads, blk_lo, blk_hi, st)) return r;
+  if (tail)
+    if (int r = backward_tail(v, params, wave, wave_stride, grads, L, st)) return r;
   // per-channel / slope gradients of this part: fold the replicas into the flat gradient
-  return reduce_vector_grads(l, ws, vg, grads, st, blk_lo, blk_hi, tail, head);
+  return reduce_vector_grads(v, grads, st, blk_lo, blk_hi, tail, head);
 }
 
 }  // extern "C"

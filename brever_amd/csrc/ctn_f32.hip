@@ -28,6 +28,7 @@
 #include "../../include/brever_hip.h"
 #include "common.cuh"
 #include "status.h"
+#include "ctn_layout.h"
 #include "gemm_f32_big.h"
 
 using namespace brv;
@@ -38,50 +39,13 @@ namespace {
 
 inline long long up(long long x, long long a) { return (x + a - 1)/a*a; }
 
-struct Blk32 {
-  long long conv_w, conv_b, dconv_w, dconv_b, res_w, res_b, skip_w, skip_b,
-      n1_g, n1_b, n2_g, n2_b, prelu1, prelu2;
-};
-// parameter offsets in ConvTasNet.parameters() order (identical to the bf16 path)
-struct Lay32 {
-  int N, K, Bn, H, Sc, P, nb, S, hop, causal, layers;
-  long long enc_w, dec_w, ln_g, ln_b, bott_w, bott_b, tcn_prelu, out_w, out_b, n_params;
-  std::vector<Blk32> blk;
+// parameter offsets: ctn_layout.h; this path's own limit is the kernel size
+struct Lay32 : CtnLayout<CtnBlockOff> {
   int init(const brv_ctn_config* c) {
-    if (!c) return fail(-1, "null config");
-    if (c->filters < 1 || c->filter_length < 2 || c->bottleneck_channels < 1 ||
-        c->hidden_channels < 1 || c->skip_channels < 1 || c->layers < 1 || c->repeats < 1 ||
-        c->output_sources < 1 || c->kernel_size < 1)
-      return fail(-1, "invalid Conv-TasNet hyper-parameters");
-    if (c->kernel_size > 7) return fail(-2, "kernel_size must be <= 7 in the fp32 HIP path");
-    N = c->filters; K = c->filter_length; Bn = c->bottleneck_channels; H = c->hidden_channels;
-    Sc = c->skip_channels; P = c->kernel_size; layers = c->layers; nb = c->layers*c->repeats;
-    S = c->output_sources; hop = K/2; causal = c->causal != 0;
-    long long o = 0;
-    auto take = [&](long long n) { long long r = o; o += n; return r; };
-    enc_w = take((long long)N*K); dec_w = take((long long)N*K);
-    ln_g = take(N); ln_b = take(N);
-    bott_w = take((long long)Bn*N); bott_b = take(Bn);
-    blk.resize(nb);
-    for (int i = 0; i < nb; ++i) {
-      Blk32& b = blk[i];
-      b.conv_w = take((long long)H*Bn); b.conv_b = take(H);
-      b.dconv_w = take((long long)H*P); b.dconv_b = take(H);
-      if (i < nb - 1) { b.res_w = take((long long)Bn*H); b.res_b = take(Bn); }
-      else { b.res_w = -1; b.res_b = -1; }
-      b.skip_w = take((long long)Sc*H); b.skip_b = take(Sc);
-      b.n1_g = take(H); b.n1_b = take(H); b.n2_g = take(H); b.n2_b = take(H);
-      b.prelu1 = take(1); b.prelu2 = take(1);
-    }
-    tcn_prelu = take(1);
-    out_w = take((long long)S*N*Sc); out_b = take((long long)S*N);
-    n_params = o;
-    return 0;
-  }
-  long long frames(long long L) const {
-    const long long pad = ((K - L) % hop + hop) % hop;     // Python modulo (convtasnet.py:115-120)
-    const long long Lp = L + pad;
-    return Lp < K ? 0 : (Lp - K)/hop + 1;
+    return CtnLayout::init(c, [](const brv_ctn_config* c) {
+      if (int r = ctn_kernel_size_positive(c)) return r;
+      return c->kernel_size > 7 ? fail(-2, "kernel_size must be <= 7 in the fp32 HIP path") : 0;
+    });
   }
 };
 
@@ -903,7 +867,7 @@ int brv_ctn_f32_forward(const brv_ctn_config* cfg, const float* params, void* wo
     OK32(conv1x1(c, wn, l.N, params + l.bott_w, l.Bn, l.N, c.xb(0), l.Bn, params + l.bott_b, 2));
   }
   for (int i = 0; i < l.nb; ++i) {
-    const Blk32& b = l.blk[i];
+    const CtnBlockOff& b = l.blk[i];
     const bool has_res = i < l.nb - 1;
     const int dil = 1 << (i % l.layers);
     const int total = (l.P - 1)*dil;
@@ -1039,7 +1003,7 @@ int brv_ctn_f32_backward_part(const brv_ctn_config* cfg, const float* params, vo
   OK32(col_sum(c, G + l.Bn, ldg, l.Sc, c.f(ws.skipb)));
   }   // head
   for (int i = blk_hi; i >= blk_lo; --i) {
-    const Blk32& b = l.blk[i];
+    const CtnBlockOff& b = l.blk[i];
     const bool has_res = i < l.nb - 1;
     const int dil = 1 << (i % l.layers);
     const int total = (l.P - 1)*dil;

@@ -30,6 +30,7 @@
 #include "../../include/brever_hip.h"
 #include "common.cuh"
 #include "status.h"
+#include "ctn_layout.h"
 
 using namespace brv;
 
@@ -44,53 +45,36 @@ constexpr int kTileC = 16;         // columns per workgroup of a product
 constexpr int kDwCols = 4;         // columns per workgroup of the depthwise kernel
 constexpr float kEps = 1e-8f;      // cumulative layer norm (modules/normalization.py)
 
-struct BlkS { long long conv_w, conv_b, dconv_w, dconv_b, res_w, res_b, skip_w, skip_b, n1_g, n1_b, n2_g, n2_b,
-                        prelu1, prelu2; long long ring; int dil, R; };
+struct BlkS : CtnBlockOff { long long ring; int dil, R; };
 
-// parameter offsets in ConvTasNet.parameters() order (identical to ctn_f32.hip) + the state layout
-struct LayS {
-  int N, K, Bn, H, Sc, P, nb, S, hop, layers, norms, gmax;
-  long long enc_w, dec_w, ln_g, ln_b, bott_w, bott_b, tcn_prelu, out_w, out_b;
+// parameter offsets (ctn_layout.h) + this path's limits and the state layout
+struct LayS : CtnLayout<BlkS> {
+  int norms, gmax;
   long long st_stats, st_carry, st_tail, st_ring, st_bytes;     // bytes
-  BlkS blk[64];
-  int init(const brv_ctn_config* c) {
-    if (!c) return fail(-1, "null config");
-    if (c->filters < 1 || c->filter_length < 2 || c->bottleneck_channels < 1 || c->hidden_channels < 1 ||
-        c->skip_channels < 1 || c->layers < 1 || c->repeats < 1 || c->output_sources < 1 || c->kernel_size < 1)
-      return fail(-1, "invalid Conv-TasNet hyper-parameters");
+  static int limits(const brv_ctn_config* c) {
+    if (int r = ctn_kernel_size_positive(c)) return r;
     if (!c->causal) return fail(-3, "streaming needs a causal Conv-TasNet (the global layer norm is not streamable)");
     if (c->kernel_size > kMaxP) return fail(-2, "streaming: kernel_size must be <= 8");
     if (c->layers*c->repeats > 64 || c->layers > 24) return fail(-2, "streaming: at most 64 blocks, 24 layers");
     if (c->filter_length % 2) return fail(-2, "streaming: filter_length must be even (hop = filter_length/2)");
-    N = c->filters; K = c->filter_length; Bn = c->bottleneck_channels; H = c->hidden_channels;
-    Sc = c->skip_channels; P = c->kernel_size; layers = c->layers; nb = c->layers*c->repeats;
-    S = c->output_sources; hop = K/2; norms = 1 + 2*nb;
-    const int widest = N > H ? N : H;
-    if (upS(widest, 32) > kMaxKp || upS(Bn, 32) > kMaxKp || upS(Sc, 32) > kMaxKp || upS(K, 32) > kMaxKp)
+    const int widest = c->filters > c->hidden_channels ? c->filters : c->hidden_channels;
+    if (upS(widest, 32) > kMaxKp || upS(c->bottleneck_channels, 32) > kMaxKp || upS(c->skip_channels, 32) > kMaxKp ||
+        upS(c->filter_length, 32) > kMaxKp)
       return fail(-2, "streaming: channel counts must be <= 960");
-    gmax = (widest + kTileM - 1)/kTileM;
-    long long o = 0;
-    auto take = [&](long long n) { long long r = o; o += n; return r; };
-    enc_w = take((long long)N*K); dec_w = take((long long)N*K);
-    ln_g = take(N); ln_b = take(N);
-    bott_w = take((long long)Bn*N); bott_b = take(Bn);
+    return 0;
+  }
+  int init(const brv_ctn_config* c) {
+    if (int r = CtnLayout::init(c, limits)) return r;
+    norms = 1 + 2*nb;
+    gmax = ((N > H ? N : H) + kTileM - 1)/kTileM;
     long long ring_frames = 0;
     for (int i = 0; i < nb; ++i) {
       BlkS& b = blk[i];
-      b.conv_w = take((long long)H*Bn); b.conv_b = take(H);
-      b.dconv_w = take((long long)H*P); b.dconv_b = take(H);
-      if (i < nb - 1) { b.res_w = take((long long)Bn*H); b.res_b = take(Bn); }
-      else { b.res_w = -1; b.res_b = -1; }
-      b.skip_w = take((long long)Sc*H); b.skip_b = take(Sc);
-      b.n1_g = take(H); b.n1_b = take(H); b.n2_g = take(H); b.n2_b = take(H);
-      b.prelu1 = take(1); b.prelu2 = take(1);
       b.dil = 1 << (i % layers);
       b.R = (P - 1)*b.dil;
       b.ring = ring_frames;
       ring_frames += b.R;
     }
-    tcn_prelu = take(1);
-    out_w = take((long long)S*N*Sc); out_b = take((long long)S*N);
     // state slot: [int64 hops, int64 reserved][fp64 stats (norms x 2)][carry hop][tail S x hop][rings]
     st_stats = 16;
     st_carry = st_stats + 16LL*norms;

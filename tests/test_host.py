@@ -258,6 +258,33 @@ def test_call_and_query_raise_with_the_librarys_message():
         hip.call('brv_combine', t, t, t, 4.5, 1.0, None)      # a float where the header says int64_t
 
 
+def _assert_offsets_follow_parameters(net):
+    """The library's flat layout (csrc/ctn_layout.h) is the running sum of numel() over parameters()."""
+    lib = hip.lib()
+    cfg = ctypes.byref(net.cfg)
+    params = list(net.parameters())
+    assert lib.brv_ctn_param_tensors(cfg) == len(params)
+    off = 0
+    for i, p in enumerate(params):
+        assert lib.brv_ctn_param_offset(cfg, i) == off, i
+        off += p.numel()
+    assert lib.brv_ctn_param_count(cfg) == off
+    assert lib.brv_ctn_param_offset(cfg, len(params)) == -1          # one past the last tensor: refused
+
+
+@pytest.mark.parametrize('cfg', [
+    dict(),                                                                          # default widths
+    dict(filters=72, filter_length=20, bottleneck_channels=40, hidden_channels=88, skip_channels=24,
+         layers=3, repeats=2, output_sources=2),                                     # odd widths, S = 2
+    dict(filters=16, bottleneck_channels=8, hidden_channels=16, skip_channels=8, layers=1, repeats=1),  # one block
+    dict(filters=64, bottleneck_channels=32, hidden_channels=64, skip_channels=32, kernel_size=5,
+         layers=2, repeats=2, causal=True),                                          # causal, P = 5
+], ids=['default', 'odd_widths_two_sources', 'one_block', 'causal_p5'])
+def test_param_layout_follows_parameters_order(cfg):
+    from brever_amd.models import ConvTasNet
+    _assert_offsets_follow_parameters(ConvTasNet(**cfg))
+
+
 def test_layout_queries_match_reference_constants():
     from brever_amd.models import ConvTasNet, count_params
     net = ConvTasNet()
@@ -267,11 +294,7 @@ def test_layout_queries_match_reference_constants():
     cfg = ctypes.byref(net.cfg)
     assert lib.brv_ctn_param_count(cfg) == 4_935_217
     assert lib.brv_ctn_param_tensors(cfg) == 343
-    # offsets follow parameters() order
-    off = 0
-    for i, p in enumerate(net.parameters()):
-        assert lib.brv_ctn_param_offset(cfg, i) == off
-        off += p.numel()
+    _assert_offsets_follow_parameters(net)
     # Encoder.pad arithmetic (convtasnet.py:115-120), bit-exact
     for L in [1, 15, 16, 31, 32, 33, 47, 48, 63999, 64000, 64001]:
         pad = (32 - L) % 16
