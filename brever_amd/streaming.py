@@ -375,25 +375,242 @@ class DCCRNStreamer(_StreamSlots):
         return y
 
 
+class FFNNStreamer(_StreamSlots):
+    """Many concurrent streams of one :class:`~brever_amd.models.FFNN` on its device, at the model's own latency:
+    the output lags the input by ``lag = frame_length - hop_length`` samples (the first ``lag`` are zeros), the
+    look-ahead of the centred STFT. A stream keeps all its ``channels``: the features are the channel mean of
+    the power, the mask is applied to the channel-mean spectrum. Dropout is never applied (the model in eval
+    mode, whatever ``model.training`` says). Weights, biases and the static normaliser's ``mean`` / ``std`` are
+    read where they live at every call. fp32 only, as the offline model."""
+
+    def __init__(self, model, max_streams=64, channels=2):
+        from . import ffnn_stream as ffs
+        self.lag = self.lag_for(model)           # (validates the model)
+        if int(max_streams) < 1:
+            raise ValueError(f'max_streams must be >= 1, got {max_streams}')
+        if int(channels) < 1:
+            raise ValueError(f'channels must be >= 1, got {channels}')
+        self._ffs = ffs
+        self.model = model
+        self.channels = int(channels)
+        try:
+            nbytes = ffs.query('brv_ffs_state_bytes', ctypes.byref(self._geometry(model, self.channels)))
+        except RuntimeError:
+            raise ValueError(f'this FFNN cannot stream: {ffs.last_error()}') from None
+        device = next(model.parameters()).device
+        hip.require_device(next(model.parameters()))
+        self.max_streams = int(max_streams)
+        self.hop = model.stft.hop_length
+        self.state_bytes = int(nbytes)
+        self._state = torch.zeros(self.max_streams*self.state_bytes, dtype=torch.uint8, device=device)
+        self._open = [False]*self.max_streams
+        self._hops = [0]*self.max_streams          # hops received per slot
+        self._ended = [False]*self.max_streams     # flushed: reset or close before the next process
+        self._ws = None
+        self._ids_cache = None
+        self._mel = None
+        self._bufs = {}
+
+    # ---- configuration --------------------------------------------------------------------------
+    @staticmethod
+    def lag_for(model):
+        """Output lag of an FFNN stream in samples (``frame_length - hop_length``); ``ValueError`` naming the
+        cause for a model the streaming kernels do not take."""
+        from .models.ffnn import FFNN
+        from .modules.features import FeatureExtractor
+        if not isinstance(model, FFNN):
+            raise ValueError(f'streaming needs an FFNN, got {type(model).__name__}')
+        family = FeatureExtractor._fbe_family
+        for f in model.feature_extractor.features:
+            if f in ('ild', 'ipd', 'ic'):
+                raise ValueError(f"FFNN streaming does not take the binaural cue feature '{f}'")
+            if family[f][2]:
+                raise ValueError(f"FFNN streaming does not take the DCT feature '{f}': its delta rows are "
+                                 'differences along the frames')
+        stft = model.stft
+        if stft.frame_length % (2*stft.hop_length):
+            raise ValueError('FFNN streaming needs frame_length to be a multiple of 2 hop (the centre padding '
+                             f'in whole hops), got {stft.frame_length} and hop {stft.hop_length}')
+        if not (stft.n_fft == stft.frame_length and stft.center and stft.pad_mode == 'constant' and stft.normalized
+                and stft.onesided and stft.compression_factor == 1 and stft.scale_factor == 1):
+            raise ValueError('FFNN streaming needs the STFT settings FFNN builds')
+        hidden = sum(isinstance(m, torch.nn.Linear) for m in model.ffnn.module_list) - 1
+        from .ffnn_stream import MAX_HIDDEN
+        if hidden > MAX_HIDDEN:
+            raise ValueError(f'FFNN streaming takes at most {MAX_HIDDEN} hidden layers, got {hidden}')
+        return stft.frame_length - stft.hop_length
+
+    @staticmethod
+    def _linears(model):
+        return [m for m in model.ffnn.module_list if isinstance(m, torch.nn.Linear)]
+
+    @staticmethod
+    def _geometry(model, channels=2):
+        """``brv_ffs_config`` with the geometry only (addresses unset)."""
+        from . import ffnn_stream as ffs
+        from .models.ffnn import CumulativeNormalizer
+        from .modules.features import FeatureExtractor, eps
+        stft, fe = model.stft, model.feature_extractor
+        cfg = ffs.FfsConfig()
+        cfg.n_fft, cfg.frame_length, cfg.hop, cfg.channels = stft.n_fft, stft.frame_length, stft.hop_length, channels
+        cfg.center, cfg.pad_constant = int(bool(stft.center)), int(stft.pad_mode == 'constant')
+        cfg.normalized, cfg.onesided = int(bool(stft.normalized)), int(bool(stft.onesided))
+        cfg.compression, cfg.scale = float(stft.compression_factor), float(stft.scale_factor)
+        cfg.mel, cfg.stacks, cfg.features = model.mel_fb.n_filters, model.stacks, len(fe.features)
+        for i, f in enumerate(fe.features[:ffs.MAX_FEATURES]):
+            cfg.feat_norm[i], cfg.feat_comp[i], _ = (int(v) for v in FeatureExtractor._fbe_family[f])
+        cumulative = isinstance(model.normalization, CumulativeNormalizer)
+        cfg.norm = int(cumulative)
+        cfg.eps_feat = float(eps)
+        cfg.eps_norm = float(model.normalization.eps) if cumulative else 0.0
+        linears = FFNNStreamer._linears(model)
+        cfg.hidden = len(linears) - 1
+        for i, lin in enumerate(linears[:ffs.MAX_HIDDEN + 1]):
+            cfg.widths[i] = lin.out_features
+        return cfg
+
+    def _config(self):
+        """The config of one call: geometry and the current addresses of every value the kernels read."""
+        model = self.model
+        cfg = self._geometry(model, self.channels)
+        tensors = []
+        for i, lin in enumerate(self._linears(model)):
+            cfg.weight[i], cfg.bias[i] = lin.weight.data_ptr(), lin.bias.data_ptr()
+            tensors += [lin.weight, lin.bias]
+        if not cfg.norm:
+            norm = model.normalization
+            cfg.mean, cfg.std = norm.mean.data_ptr(), norm.std.data_ptr()
+            tensors += [norm.mean, norm.std]
+        for t in tensors:
+            hip.require_device(t)
+            if t.device != self.device:
+                raise RuntimeError(f'the model moved to {t.device}; the streams live on {self.device}')
+            if t.dtype != torch.float32 or not t.is_contiguous():
+                raise RuntimeError('the weights, biases and statistics must be contiguous fp32 tensors')
+        if self._mel is None:
+            fb = model.mel_fb
+            self._mel = (fb.filters.float().to(self.device).contiguous(),
+                         fb.inverse_filters.float().to(self.device).contiguous())
+        cfg.mel_fwd, cfg.mel_inv = self._mel[0].data_ptr(), self._mel[1].data_ptr()
+        return cfg
+
+    def _reset(self, ids):
+        t = self._ids_tensor(ids)
+        cfg = self._geometry(self.model, self.channels)
+        self._ffs.call('brv_ffs_reset', ctypes.byref(cfg), self._state, self.max_streams, t, len(ids), hip.stream())
+        for i in ids:
+            self._hops[i] = 0
+            self._ended[i] = False
+
+    def _input(self, x, n, what='input'):
+        hip.require_device(x)
+        if x.dim() == 2:
+            raise ValueError(f'FFNN needs its channels: {what} must be (n, channels, samples) with '
+                             f'{self.channels} channels, got {tuple(x.shape)} (the features are the channel mean of '
+                             'the power, so the channels cannot be averaged first)')
+        if x.dim() != 3 or x.shape[0] != n or x.shape[1] != self.channels:
+            raise ValueError(f'{what} must be (n, channels, samples) with n = {n} streams and {self.channels} '
+                             f'channels, got {tuple(x.shape)}')
+        return x.float().contiguous()
+
+    def _run(self, ids, n, x, hops, rest, y):
+        """The launch sequence of one call: frames, DFT, network, synthesis, overlap-add + commit."""
+        ffs, stft = self._ffs, self.model.stft
+        cfg = self._config()
+        c = ctypes.byref(cfg)
+        nbytes = ffs.query('brv_ffs_workspace_bytes', c, n, hops)
+        if self._ws is None or self._ws.numel() < nbytes:
+            self._ws = None
+            self._ws = torch.empty(int(nbytes), dtype=torch.uint8, device=self.device)
+        C, N, hop, bins = self.channels, stft.n_fft, self.hop, stft.bins
+        if (n, hops) not in self._bufs:
+            if len(self._bufs) >= 16:
+                self._bufs.clear()
+            f32 = dict(dtype=torch.float32, device=self.device)
+            self._bufs[(n, hops)] = (torch.empty(n*C, self.lag + hops*hop, **f32),
+                                     torch.empty(n*C, bins, hops, 2, **f32), torch.empty(n, bins, hops, 2, **f32),
+                                     torch.empty(n, hops, N, **f32))
+        xin, spec, mspec, frames = self._bufs[(n, hops)]
+        tb = stft._tables(self.device)
+        t, st, ws = self._ids_tensor(ids), hip.stream(), self._ws
+        ffs.call('brv_ffs_step_frames', c, self._state, self.max_streams, t, n, x, hops, rest, xin, st)
+        hip.call('brv_dft64_forward', xin, tb['basis'], spec, n*C, self.lag + hops*hop, N, hop, 0, hops, bins, 1.0,
+                 1.0, st)
+        ffs.call('brv_ffs_step_net', c, self._state, self.max_streams, t, n, hops, rest, spec, mspec, ws, ws.numel(),
+                 st)
+        hip.call('brv_dft64_synthesis', mspec, tb['synthesis'], frames, n, hops, N, bins, 1.0, 1.0, st)
+        ffs.call('brv_ffs_step_emit', c, tb['window'], self._state, self.max_streams, t, n, hops, rest, xin, frames,
+                 y, ws, ws.numel(), st)
+
+    # ---- compute --------------------------------------------------------------------------------
+    def process(self, x, ids):
+        """Advance the streams ``ids`` by the chunk ``x`` (``(n, channels, k hop)``): returns ``(n, k hop)``,
+        ``lag`` samples behind the input."""
+        ids = self._check_ids(ids)
+        n = len(ids)
+        x = self._input(x, n)
+        L = x.shape[-1]
+        if L == 0 or L % self.hop:
+            raise ValueError(f'a chunk must be a positive multiple of hop = {self.hop} samples, got {L}')
+        for i in ids:
+            if self._ended[i]:
+                raise ValueError(f'stream {i} was flushed; reset or close it first')
+        hops = L//self.hop
+        y = torch.empty(n, L, dtype=torch.float32, device=self.device)
+        self._run(ids, n, x, hops, -1, y)
+        for i in ids:
+            self._hops[i] += hops
+        return y
+
+    def flush(self, ids, rest=None):
+        """End the streams ``ids``: ``rest`` is their last ``r < hop`` input samples (``(n, channels, r)``, or
+        None). Runs the frames of the zero-padded end and returns the ``(n, lag + r)`` output samples still
+        owed. Reset or close the streams afterwards."""
+        ids = self._check_ids(ids)
+        n = len(ids)
+        r = 0
+        if rest is not None:
+            rest = self._input(rest, n, 'rest')
+            r = rest.shape[-1]
+            if r >= self.hop:
+                raise ValueError(f'rest must be shorter than hop = {self.hop} samples, got {r}; '
+                                 'process the whole hops first')
+        for i in ids:
+            if self._ended[i]:
+                raise ValueError(f'stream {i} was flushed already; reset or close it first')
+        y = torch.empty(n, self.lag + r, dtype=torch.float32, device=self.device)
+        self._run(ids, n, rest if r else None, self.model.stft.n_fft//self.hop, r, y)
+        for i in ids:
+            self._ended[i] = True
+        return y
+
+
 def enhance_streaming(model, x, chunk_samples, use_amp=False):
-    """``model.enhance(x, use_amp)`` computed chunk by chunk through a :class:`ConvTasNetStreamer` or, for a
-    DCCRN, a :class:`DCCRNStreamer` (same shapes as ``model.enhance``). ``chunk_samples`` is rounded down to
-    whole hops (at least one)."""
+    """``model.enhance(x, use_amp)`` computed chunk by chunk through a :class:`ConvTasNetStreamer`, for a DCCRN a
+    :class:`DCCRNStreamer`, for an FFNN an :class:`FFNNStreamer` (same shapes as ``model.enhance``).
+    ``chunk_samples`` is rounded down to whole hops (at least one). An FFNN is fed every channel of ``x`` and, as
+    its ``enhance``, has no reduced-precision mode: ``use_amp`` changes nothing for it."""
     if x.ndim == 2:
         return enhance_streaming(model, x.unsqueeze(0), chunk_samples, use_amp).squeeze(0)
     if x.ndim != 3:
         raise ValueError(f'input must be 2 or 3 dimensional, got {x.ndim}')
     B, L = x.shape[0], x.shape[-1]
     from .models.dccrn import DCCRN
-    cls = DCCRNStreamer if isinstance(model, DCCRN) else ConvTasNetStreamer
-    s = cls(model, max_streams=B, use_amp=use_amp)
-    hip.require_device(x)
+    from .models.ffnn import FFNN
+    if isinstance(model, FFNN):
+        s = FFNNStreamer(model, max_streams=B, channels=x.shape[-2])
+        hip.require_device(x)
+        feed = x.float()
+    else:
+        cls = DCCRNStreamer if isinstance(model, DCCRN) else ConvTasNetStreamer
+        s = cls(model, max_streams=B, use_amp=use_amp)
+        hip.require_device(x)
+        feed = x.float().mean(axis=-2)
     hop = s.hop
     chunk = max(1, int(chunk_samples)//hop)*hop
-    mono = x.float().mean(axis=-2)
     ids = s.open(B)
     whole = L//hop*hop
-    outs = [s.process(mono[:, i:i + chunk], ids) if i + chunk <= whole else
-            s.process(mono[:, i:whole], ids) for i in range(0, whole, chunk)]
-    outs.append(s.flush(ids, mono[:, whole:] if L > whole else None))
+    outs = [s.process(feed[..., i:i + chunk], ids) if i + chunk <= whole else
+            s.process(feed[..., i:whole], ids) for i in range(0, whole, chunk)]
+    outs.append(s.flush(ids, feed[..., whole:] if L > whole else None))
     return torch.cat(outs, dim=-1)[..., s.lag:]

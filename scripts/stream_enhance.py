@@ -1,6 +1,7 @@
-"""Enhance a WAV or FLAC file chunk by chunk through a trained causal Conv-TasNet or DCCRN, as a live
+"""Enhance a WAV or FLAC file chunk by chunk through a trained causal Conv-TasNet, DCCRN or FFNN, as a live
 stream would arrive (brever_amd.streaming): the output is written as 16-bit FLAC through the native encoder
-and the real-time factor (compute time / audio time) is printed.
+and the real-time factor (compute time / audio time) is printed. An FFNN is fed both channels of the file (a
+mono file is duplicated, as scripts/test_model.py feeds it); the other two models get the channel mean.
 
     python scripts/stream_enhance.py -i models/<id> input.flac output.flac [--chunk-ms 16] [--use-amp]
 """
@@ -17,22 +18,24 @@ from brever_amd.models import ModelRegistry
 
 
 def main():
-    p = argparse.ArgumentParser(description='stream a file through a causal Conv-TasNet or a DCCRN')
+    p = argparse.ArgumentParser(description='stream a file through a causal Conv-TasNet, a DCCRN or an FFNN')
     p.add_argument('-i', '--input', required=True, help='model directory (or a .ckpt file in it)')
-    p.add_argument('audio', help='input WAV or FLAC file (channels are averaged, as enhance does)')
+    p.add_argument('audio', help='input WAV or FLAC file (channels are averaged, as enhance does; an FFNN keeps them)')
     p.add_argument('output', help='output FLAC file (the first source)')
     p.add_argument('--chunk-ms', type=float, default=16.0, help='chunk length, rounded down to whole hops')
-    p.add_argument('--use-amp', action='store_true', help='bf16 operands (fp32 accumulation and state)')
+    p.add_argument('--use-amp', action='store_true', help='bf16 operands (fp32 accumulation and state); not for an FFNN')
     args = p.parse_args()
 
-    from brever_amd.streaming import ConvTasNetStreamer, DCCRNStreamer
+    from brever_amd.streaming import ConvTasNetStreamer, DCCRNStreamer, FFNNStreamer
     if args.input.endswith('.ckpt'):
         model_dir, ckpt = os.path.dirname(os.path.dirname(args.input)), args.input
     else:
         model_dir, ckpt = args.input, os.path.join(args.input, 'checkpoints', 'last.ckpt')
     cfg = get_config(os.path.join(model_dir, 'config.yaml'))
-    if cfg.arch not in ('convtasnet', 'dccrn'):
-        raise SystemExit(f'{model_dir}: streaming needs a convtasnet or dccrn model, got {cfg.arch}')
+    if cfg.arch not in ('convtasnet', 'dccrn', 'ffnn'):
+        raise SystemExit(f'{model_dir}: streaming needs a convtasnet, dccrn or ffnn model, got {cfg.arch}')
+    if cfg.arch == 'ffnn' and args.use_amp:
+        raise SystemExit('--use-amp: FFNN has no reduced-precision mode')
     model = ModelRegistry.get(cfg.arch)(**cfg.model.to_dict()).cuda()
     state = torch.load(ckpt, map_location='cuda', weights_only=False)
     model.load_state_dict(state['model'])
@@ -46,23 +49,28 @@ def main():
     with open(args.audio, 'rb') as f:
         x, fs = audio_read(f, args.audio)
     x = torch.as_tensor(x, dtype=torch.float32)
-    x = (x.mean(dim=1) if x.dim() == 2 else x).cuda()
-    s = (DCCRNStreamer if cfg.arch == 'dccrn' else ConvTasNetStreamer)(model, max_streams=1, use_amp=args.use_amp)
+    if cfg.arch == 'ffnn':
+        x = (x.T if x.dim() == 2 else x.repeat(2, 1)).contiguous().cuda()      # (channels, samples)
+        s = FFNNStreamer(model, max_streams=1, channels=x.shape[0])
+    else:
+        x = (x.mean(dim=1) if x.dim() == 2 else x).cuda()
+        s = (DCCRNStreamer if cfg.arch == 'dccrn' else ConvTasNetStreamer)(model, max_streams=1,
+                                                                           use_amp=args.use_amp)
     hop = s.hop
     chunk = max(1, int(args.chunk_ms*fs/1000)//hop)*hop
     ids = s.open(1)
-    L = x.numel()
+    L = x.shape[-1]
     whole = L//hop*hop
     outs = []
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(0, whole, chunk):
-        outs.append(s.process(x[None, i:min(i + chunk, whole)], ids))
-    outs.append(s.flush(ids, x[None, whole:] if L > whole else None))
+        outs.append(s.process(x[None, ..., i:min(i + chunk, whole)], ids))
+    outs.append(s.flush(ids, x[None, ..., whole:] if L > whole else None))
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     y = torch.cat(outs, dim=-1)[0]
-    y = (y[s.lag:] if cfg.arch == 'dccrn' else y[0, s.lag:]).cpu().numpy()     # (the first source)
+    y = (y[0, s.lag:] if cfg.arch == 'convtasnet' else y[s.lag:]).cpu().numpy()     # (the first source)
     write_flac(args.output, y, fs)
     print(f'{args.audio}: {L/fs:.2f} s in chunks of {1e3*chunk/fs:.1f} ms, {elapsed:.3f} s, '
           f'real-time factor {elapsed/(L/fs):.4f}')

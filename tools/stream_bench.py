@@ -1,9 +1,9 @@
-"""Step time of the streaming Conv-TasNet or DCCRN (brever_amd.streaming) on one GPU: one JSON line per
+"""Step time of the streaming Conv-TasNet, DCCRN or FFNN (brever_amd.streaming) on one GPU: one JSON line per
 (precision, n streams, F hops per call) with the median and p90 of the synchronised step time, the
 real-time factor (step time / audio time of a chunk), the streams one GPU keeps in real time at that
 chunk size (n / real-time factor, rounded down) and the launches per step.
 
-    python tools/stream_bench.py [--model {convtasnet,dccrn}] [--n 1 16 64 256] [--hops 1 16] [--steps 50]
+    python tools/stream_bench.py [--model {convtasnet,dccrn,ffnn}] [--n 1 16 64 256] [--hops 1 16] [--steps 50]
                                  [--warmup 10]
 """
 import argparse
@@ -19,7 +19,7 @@ if ROOT not in sys.path:
 
 def main():
     p = argparse.ArgumentParser(description=__doc__.split('\n\n')[0])
-    p.add_argument('--model', choices=['convtasnet', 'dccrn'], default='convtasnet')
+    p.add_argument('--model', choices=['convtasnet', 'dccrn', 'ffnn'], default='convtasnet')
     p.add_argument('--n', type=int, nargs='+', default=[1, 16, 64, 256])
     p.add_argument('--hops', type=int, nargs='+', default=[1, 16])
     p.add_argument('--amp', type=int, nargs='+', default=[0, 1])
@@ -29,11 +29,21 @@ def main():
     args = p.parse_args()
 
     import torch
-    from brever_amd.models import DCCRN, ConvTasNet
-    from brever_amd.streaming import ConvTasNetStreamer, DCCRNStreamer
+    from brever_amd.models import DCCRN, FFNN, ConvTasNet
+    from brever_amd.streaming import ConvTasNetStreamer, DCCRNStreamer, FFNNStreamer
 
     torch.manual_seed(0)
-    if args.model == 'dccrn':
+    channels = ()
+    if args.model == 'ffnn':
+        model = FFNN().cuda()                       # default widths: 384 -> 1024 -> 1024 -> 64, log-mel, 5 stacks
+
+        def Streamer(model, max_streams, use_amp):  # fp32 only
+            return FFNNStreamer(model, max_streams=max_streams)
+        args.amp = [0]
+        launches = 8 + len(FFNNStreamer._linears(model))
+        hop = model.stft.hop_length
+        channels = (2,)
+    elif args.model == 'dccrn':
         model = DCCRN().cuda()                      # default widths: 16 .. 128 channels, 6 levels, LSTM 2 x 128
         Streamer = DCCRNStreamer
         launches = 5 + 2*len(model.mask_net.encoder) + 2*len(model.mask_net.lstm.lstm.layers)
@@ -50,7 +60,7 @@ def main():
             ids = s.open(n)
             for F in args.hops:
                 s.reset(ids)
-                x = 0.1*torch.randn(n, F*hop, device='cuda')
+                x = 0.1*torch.randn(n, *channels, F*hop, device='cuda')
                 times = []
                 for i in range(args.warmup + args.steps):
                     torch.cuda.synchronize()
