@@ -1,11 +1,17 @@
 """Throughput of the batched mixture engine: one JSON line of mixtures/s.
 
     python tools/mix_bench.py [--batch 64] [--seconds 4] [--brir-seconds 1] [--noises 3] [--steps 10] [--warmup 2]
+                              [--diffuse-color COLOUR] [--ltas-eq] [--decay] [--decay-color COLOUR] [--cold-cache]
 
 The recipe: ``batch`` mixtures of a ``seconds`` long target, ``noises`` directional noises of the same length,
 BRIRs of ``brir-seconds``, SNR and RMS jitter set, (mixture, foreground) written. Timed from the first launch
 of a batch to the end of its last kernel, descriptors included; the pools are on the device beforehand, as
 ``PoolMixtureMaker`` keeps them.
+
+``--diffuse-color`` / ``--ltas-eq`` add a diffuse noise over the 8 BRIRs of the room, coloured / matched to the speech
+LTAS; ``--decay`` adds a BRIR decay (the reference's default ranges) to the target's and every noise's BRIR.
+``--cold-cache`` empties the colouring-filter cache before every batch (every filter is then computed on the host
+again); the line then also holds the host time of those misses.
 
 ``--cpu-reference DIR`` instead times ``Mixture`` of a checkout of the reference (philgzl/brever) at DIR on the
 same recipe, one mixture at a time on this host's CPU (``sofa`` and ``soundfile``, which it imports but does
@@ -41,20 +47,34 @@ def gpu(args):
     speech, noises, brirs = recipe(args, rng)
     maker = mixture.PoolMixtureMaker(None, ['mixture', 'foreground'], args.batch, speech=speech, noises=noises,
                                      brirs=[brirs], noise_count=(args.noises, args.noises), rms_jitter=(-3.0, 3.0),
-                                     batch=args.batch, block=args.block)
-    times = []
+                                     batch=args.batch, block=args.block,
+                                     diffuse=args.diffuse_color is not None or args.ltas_eq,
+                                     diffuse_color=args.diffuse_color or 'white', diffuse_ltas_eq=args.ltas_eq,
+                                     decay=args.decay, decay_color=args.decay_color)
+    times, miss_ms = [], []
     for step in range(args.warmup + args.steps):
         meta = maker.draw(step)
+        if args.cold_cache:
+            mixture.color_filters.clear()
+        missed = mixture.color_filters.misses, mixture.color_filters.miss_seconds
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         res = maker.synthesize(meta)
         torch.cuda.synchronize()
         times.append(time.perf_counter() - t0)
+        miss_ms.append((mixture.color_filters.misses - missed[0], 1e3*(mixture.color_filters.miss_seconds - missed[1])))
     res.check()
     t = float(np.median(times[args.warmup:]))
+    extra = dict(diffuse_color=args.diffuse_color, ltas_eq=args.ltas_eq, decay=args.decay,
+                 decay_color=args.decay_color, cold_cache=args.cold_cache, ms_min=1e3*min(times[args.warmup:]),
+                 ms_max=1e3*max(times[args.warmup:]), filter_misses=mixture.color_filters.misses)
+    # what the cache misses of a batch cost on the host (the cache's own clock), median over the timed batches
+    extra.update(filter_misses_per_batch=float(np.median([k for k, _ in miss_ms[args.warmup:]])),
+                 host_ms_filter_misses_per_batch=float(np.median([ms for _, ms in miss_ms[args.warmup:]])),
+                 peak_gib=torch.cuda.max_memory_allocated()/2**30)
     print(json.dumps(dict(metric='mixtures_per_s', value=args.batch/t, ms_per_batch=1e3*t, batch=args.batch,
                           seconds=args.seconds, brir_seconds=args.brir_seconds, noises=args.noises,
-                          block=args.block, steps=args.steps, device=torch.cuda.get_device_name(0))))
+                          block=args.block, steps=args.steps, device=torch.cuda.get_device_name(0), **extra)))
 
 
 def cpu_reference(args):
@@ -90,6 +110,11 @@ if __name__ == '__main__':
     ap.add_argument('--block', type=int, default=256)
     ap.add_argument('--steps', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=2)
+    ap.add_argument('--diffuse-color', default=None, choices=['brown', 'pink', 'white', 'blue', 'violet'])
+    ap.add_argument('--ltas-eq', action='store_true')
+    ap.add_argument('--decay', action='store_true')
+    ap.add_argument('--decay-color', default='white', choices=['brown', 'pink', 'white', 'blue', 'violet'])
+    ap.add_argument('--cold-cache', action='store_true')
     ap.add_argument('--cpu-reference', default=None)
     a = ap.parse_args()
     cpu_reference(a) if a.cpu_reference else gpu(a)
