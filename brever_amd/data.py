@@ -297,8 +297,8 @@ def audio_info(f, name):
     return frames, rate
 
 
-def write_flac(path, x, fs):
-    """Mono 16-bit FLAC file of the float signal ``x`` (what ``torchaudio.save(<name>.flac, x, fs)`` of the
+def flac_bytes(x, fs):
+    """Mono 16-bit FLAC stream of the float signal ``x`` (what ``torchaudio.save(<name>.flac, x, fs)`` of the
     reference's ``scripts/test_model.py:201-209`` produces for a float tensor: samples clipped to [-1, 1),
     scaled by 2^15 and rounded) through the native encoder ``brv_flac_encode16`` (csrc/flac.hip)."""
     import ctypes
@@ -316,8 +316,14 @@ def write_flac(path, x, fs):
     got = lib.brv_flac_encode16(src, pcm.size, int(fs), buf, size)
     if got != size:
         raise RuntimeError(f'brv_flac_encode16 failed ({got})')
+    return bytes(buf)
+
+
+def write_flac(path, x, fs):
+    """``flac_bytes(x, fs)`` written to ``path``."""
+    data = flac_bytes(x, fs)
     with open(path, 'wb') as f:
-        f.write(bytes(buf))
+        f.write(data)
 
 
 def audio_read(f, name):
