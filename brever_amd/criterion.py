@@ -7,6 +7,9 @@ a ``(batch,)`` loss. The masking of ``apply_mask`` (criterion.py:229-234) is
 folded into the reduction kernels: ``lengths`` stays on the device and there
 is no per-item host synchronisation.
 
+``stoi`` / ``estoi`` are not in the reference: minus the STOI / ESTOI metric as a training criterion, forward by the
+metric's own launches and backward in ``libbrever_stoi_loss.so`` (``stoi.py``).
+
 The arithmetic runs in ``libbrever_hip.so`` (``brv_snr_forward`` ...); CPU
 tensors are rejected (no fallback) -- the CPU restatement used for checking
 lives in ``oracle/criterion.py`` and is never imported from here.
@@ -16,6 +19,7 @@ import inspect
 import torch
 
 from . import hip
+from . import stoi as stoi_hip
 from .registry import Registry
 
 eps = torch.finfo(torch.float32).eps
@@ -195,6 +199,55 @@ class _ScaleInvariantFunction(torch.autograd.Function):
         dx = torch.empty_like(x2)
         hip.call('brv_si_scale_backward', g2, x2, y2, lengths, stats, dx, B, S, L, hip.stream())
         return dx.view(ctx.shape), None, None
+
+
+class _StoiFunction(torch.autograd.Function):
+    """Minus STOI / ESTOI per ``(item, middle index)`` row over the item's length, mean over the middle axes.
+    Only ``x`` gets a gradient; it is zero at and beyond the length."""
+
+    @staticmethod
+    def forward(ctx, x, y, lengths, fs, extended):
+        x2, y2, lengths, B, S, L = _rows(x, y, lengths)
+        row_lengths = lengths if S == 1 else lengths.repeat_interleave(S)
+        value, saved = stoi_hip.forward(x2.view(B*S, L), y2.view(B*S, L), fs, extended, row_lengths)
+        ctx.saved = saved
+        ctx.meta = (x.shape, x.dtype, B, S)
+        return -value if S == 1 else -value.view(B, S).mean(1)
+
+    @staticmethod
+    def backward(ctx, grad):
+        shape, in_dtype, B, S = ctx.meta
+        g = grad.float()
+        grow = (g if S == 1 else (g/S).repeat_interleave(S)).contiguous()
+        dx = stoi_hip.backward(ctx.saved, grow)
+        return dx.view(shape).to(in_dtype), None, None, None, None
+
+
+class _StoiLossBase:
+    extended = False
+
+    def __init__(self, fs=16000):
+        if int(fs) != fs or fs < 1:
+            raise ValueError(f'fs must be a positive integer, got {fs}')
+        self.fs = int(fs)
+
+    def __call__(self, x, y, lengths):
+        assert x.shape == y.shape
+        assert x.ndim >= 2
+        return _StoiFunction.apply(x, y, lengths, self.fs, self.extended)
+
+
+@CriterionRegistry.register('stoi')
+class StoiLoss(_StoiLossBase):
+    """Minus the short-time objective intelligibility (Taal et al. 2011) of the estimate ``x`` against the target
+    ``y`` sampled at ``fs``, ``(B, ..., L)`` -> ``(B,)``: minus ``MetricRegistry.get('stoi')``, differentiable in
+    ``x``. A row with fewer than 30 frames left after silent-frame removal has loss -1e-5 and a zero gradient."""
+
+
+@CriterionRegistry.register('estoi')
+class EstoiLoss(_StoiLossBase):
+    """``StoiLoss`` for the extended measure (Jensen & Taal 2016): minus ``MetricRegistry.get('estoi')``."""
+    extended = True
 
 
 @CriterionRegistry.register('multiresyu')

@@ -13,12 +13,11 @@ clean target, batched ``(B, L)`` or single ``(L,)``.
   that reference configs resolve; calling it uses the wheel when it is importable and raises a
   clear ``ImportError`` otherwise (``metric_available('pesq')`` tells which).
 """
-import math
-
 import numpy as np
 import torch
 
 from . import hip
+from . import stoi as stoi_hip
 from .criterion import CriterionRegistry
 from .registry import Registry
 
@@ -36,51 +35,9 @@ def metric_available(name):
 
 
 # ---- STOI / ESTOI ------------------------------------------------------------------------------
-_STOI_FS, _STOI_NFFT, _STOI_FRAME, _STOI_BANDS, _STOI_MINFREQ = 10000, 512, 256, 15, 150
-_stoi_cache = {}
-
-
-def _stoi_constants(device, fs):
-    key = (str(device), fs)
-    if key in _stoi_cache:
-        return _stoi_cache[key]
-    # one-third octave band edges on the 512-point DFT grid (Taal et al. 2011)
-    f = np.linspace(0, _STOI_FS, _STOI_NFFT + 1)[:_STOI_NFFT//2 + 1]
-    k = np.arange(_STOI_BANDS, dtype=float)
-    lo = _STOI_MINFREQ*2.0**((2*k - 1)/6)
-    hi = _STOI_MINFREQ*2.0**((2*k + 1)/6)
-    edges = np.array([[int(np.argmin((f - a)**2)), int(np.argmin((f - b)**2))]
-                      for a, b in zip(lo, hi)], dtype=np.int32)
-    bin0, bin1 = int(edges[:, 0].min()), int(edges[:, 1].max())
-    m = np.arange(_STOI_FRAME)
-    window = np.hanning(_STOI_FRAME + 2)[1:-1]
-    ang = 2*np.pi*np.outer(m, np.arange(bin0, bin1))/_STOI_NFFT
-    basis = np.empty((_STOI_FRAME, 2*(bin1 - bin0)), dtype=np.float64)
-    basis[:, 0::2] = window[:, None]*np.cos(ang)
-    basis[:, 1::2] = -window[:, None]*np.sin(ang)
-    out = {'edges': torch.from_numpy(edges).to(device), 'bin0': bin0,
-           'basis': torch.from_numpy(basis).float().to(device)}
-    if fs != _STOI_FS:
-        # Octave-style Kaiser polyphase filter of pystoi's resample_oct, then padded and scaled
-        # the way scipy.signal.resample_poly applies a given window
-        g = math.gcd(_STOI_FS, fs)
-        up, down = _STOI_FS//g, fs//g
-        cutoff = 1.0/(2*max(up, down))
-        L = int(np.ceil((60.0 - 8)/(28.714*cutoff/10)))
-        t = np.arange(-L, L + 1)
-        h = np.kaiser(2*L + 1, 0.1102*(60.0 - 8.7))*2*up*cutoff*np.sinc(2*cutoff*t)
-        h = h/np.sum(h)*up
-        half = (len(h) - 1)//2
-        n_pre_pad = down - half % down
-        out.update(up=up, down=down, n_pre_remove=(half + n_pre_pad)//down,
-                   hpad=torch.from_numpy(np.concatenate([np.zeros(n_pre_pad), h])).float().to(device))
-    _stoi_cache[key] = out
-    return out
-
-
 def _stoi_hip(x, y, fs, extended, lengths):
-    """x: processed, y: clean, (B, L) float tensors on the GPU; lengths: (B,) or None."""
-    lib = hip.lib()
+    """x: processed, y: clean, (B, L) float tensors on the GPU; lengths: (B,) or None. The launches are those of
+    the ``stoi`` / ``estoi`` criteria (``stoi.forward``)."""
     x = x.detach().float().contiguous()
     y = y.detach().float().contiguous()
     hip.require_device(x, y)
@@ -89,36 +46,7 @@ def _stoi_hip(x, y, fs, extended, lengths):
     if lengths is None:
         lengths = torch.full((B,), L, dtype=torch.int64, device=dev)
     lengths = torch.as_tensor(lengths).to(device=dev, dtype=torch.int64).contiguous()
-    c = _stoi_constants(dev, int(fs))
-    st = hip.stream()
-    sig = torch.stack([y, x]).reshape(2*B, L)                  # clean rows first
-    if fs != _STOI_FS:
-        n10 = -(-L*c['up']//c['down'])
-        res = torch.empty(2*B, n10, dtype=torch.float32, device=dev)
-        len2 = torch.cat([lengths, lengths])
-        hip.call('brv_resample_poly', sig, c['hpad'], res, len2, 2*B, L, n10, c['up'], c['down'], c['hpad'].numel(),
-                 c['n_pre_remove'], st)
-        sig, L = res, n10
-        lengths = -(-lengths*c['up']//c['down'])
-    nf_max = max(int(lib.brv_stoi_frames(L)), 1)
-    out_stride = _STOI_FRAME + nf_max*(_STOI_FRAME//2)
-    comp = torch.empty(2*B, out_stride, dtype=torch.float32, device=dev)
-    geom = torch.empty(B, 4, dtype=torch.int32, device=dev)
-    energy = torch.empty(B, nf_max, dtype=torch.float32, device=dev)
-    kept = torch.empty(B, nf_max, dtype=torch.int32, device=dev)
-    hip.call('brv_stoi_compact', sig[:B], sig[B:], lengths, B, L, comp[:B], comp[B:], out_stride, geom, energy, kept,
-             nf_max, 40.0, st)
-    ncols = c['basis'].shape[1]
-    spec = torch.empty(2*B, nf_max, ncols, dtype=torch.float32, device=dev)
-    # frames are rows of the compacted signals 128 samples apart: one product for all items
-    hip.call('brv_gemm_f32', comp, c['basis'], spec, 2*B, nf_max, ncols, _STOI_FRAME, _STOI_FRAME//2, ncols, ncols,
-             out_stride, 0, nf_max*ncols, 0, 0, 1, 0, 0, None, 0, st)
-    tob = torch.empty(2*B, _STOI_BANDS, nf_max, dtype=torch.float32, device=dev)
-    hip.call('brv_stoi_bands', spec, c['edges'], tob, 2*B, nf_max, ncols, c['bin0'], st)
-    partial = torch.empty(B, max(nf_max - 29, 1), dtype=torch.float32, device=dev)
-    out = torch.empty(B, dtype=torch.float32, device=dev)
-    hip.call('brv_stoi_correlate', tob[:B], tob[B:], geom, partial, out, B, nf_max, int(bool(extended)),
-             10.0**(15.0/20.0), st)
+    out, _ = stoi_hip.forward(x, y, fs, extended, lengths)
     return out.double().cpu().numpy()
 
 
