@@ -51,7 +51,12 @@ class BreverDataLoader(torch.utils.data.DataLoader):
         sizes, shape ``(batch,)`` for tensor items and ``(batch, n_inputs)``
         for tuple items, on the device of the first item
         (brever/data.py:407-491).
+
+        A list of ``CompressedItem`` (``enable_gpu_decode``) is passed on as a ``CompressedBatch``:
+        ``DevicePrefetcher`` decodes it on the device and collates the decoded items with this function.
         """
+        if isinstance(unbatched[0], CompressedItem):
+            return CompressedBatch(list(unbatched))
         single = isinstance(unbatched[0], torch.Tensor)
         rows = [(item,) if single else tuple(item) for item in unbatched]
         lengths = torch.tensor(
@@ -67,6 +72,42 @@ class BreverDataLoader(torch.utils.data.DataLoader):
         if single:
             return batched[0], lengths.squeeze(-1)
         return batched, lengths
+
+
+class CompressedItem:
+    """What ``BreverDataset.__getitem__`` returns after ``enable_gpu_decode``: the FLAC members' bytes
+    (one per source), their frame tables (``flac_gpu.index``; ``flac_gpu.HOST_MEMBER`` for a member the GPU
+    decoder does not take) and the ``(start, end)`` that ``load_segment`` would have cut."""
+
+    def __init__(self, members, tables, window, names):
+        self.members, self.tables, self.window, self.names = members, tables, window, names
+
+
+class CompressedBatch:
+    """A list of ``CompressedItem``: what ``_collate_fn`` makes of them."""
+
+    def __init__(self, items):
+        self.items = items
+
+    def __len__(self):
+        return len(self.items)
+
+
+def enable_gpu_decode(dataset):
+    """Opt in to FLAC decoding on the GPU for on-the-fly batches: ``dataset[i]`` then returns a
+    ``CompressedItem`` and ``DevicePrefetcher`` decodes whole batches on its side stream
+    (``brever_amd/flac_gpu.py``), yielding the same ``(batch, lengths)`` as the host path. Workers only
+    read tar members and index them. Unwraps ``Subset``; returns the ``BreverDataset``."""
+    while isinstance(dataset, torch.utils.data.Subset):
+        dataset = dataset.dataset
+    if not isinstance(dataset, BreverDataset):
+        raise ValueError(f'enable_gpu_decode needs a BreverDataset, got {type(dataset).__name__}')
+    if dataset.rmm_dset is not None:
+        raise ValueError("can't decode on the GPU when using dynamic mixing: there are no files")
+    if dataset._ext != 'flac':
+        raise ValueError(f'enable_gpu_decode needs FLAC members, the dataset has .{dataset._ext} files')
+    dataset._gpu_decode = True
+    return dataset
 
 
 class DevicePrefetcher:
@@ -87,9 +128,34 @@ class DevicePrefetcher:
         self.device = torch.device(device)
         self.depth = max(1, int(depth))
         self._pinned = {}
+        self._decoder = None
 
     def __len__(self):
         return len(self.loader)
+
+    def _stage_compressed(self, batch, slot, stream):
+        """Upload and decode a ``CompressedBatch`` on ``stream``, apply the dataset's ``transform`` per
+        item and collate on the device: the ``(batch, lengths)`` of the host path."""
+        from . import flac_gpu
+        if self._decoder is None:
+            self._decoder = flac_gpu.FlacBatchDecoder(self.device)
+        dataset = self.loader.dataset
+        while isinstance(dataset, torch.utils.data.Subset):
+            dataset = dataset.dataset
+        transform = getattr(dataset, 'transform', None)
+        with torch.cuda.stream(stream):
+            decoded = self._decoder.decode([it.members for it in batch.items], [it.window for it in batch.items],
+                                           names=[it.names for it in batch.items],
+                                           tables=[it.tables for it in batch.items], slot=slot)
+            if hasattr(dataset, '_check_fs'):
+                dataset._check_fs(decoded)
+            items = [decoded.data[i, ..., :n] for i, n in enumerate(decoded.lengths)]
+            if transform is not None:
+                items = [transform(x) for x in items]
+            dev_batch, dev_lengths = BreverDataLoader._collate_fn(items)
+            ev = torch.cuda.Event()
+            ev.record(stream)
+        return dev_batch, dev_lengths, ev, decoded
 
     def _pin(self, slot, key, t):
         """Copy ``t`` into this slot's pinned buffer (grown on demand)."""
@@ -105,6 +171,8 @@ class DevicePrefetcher:
     def _stage(self, item, slot, stream, fence):
         if fence is not None:
             fence.synchronize()          # the copy that last used this slot's buffers is done
+        if isinstance(item, CompressedBatch):
+            return self._stage_compressed(item, slot, stream)
         batch, lengths = item
         with torch.cuda.stream(stream):
             def up(key, t):
@@ -118,11 +186,14 @@ class DevicePrefetcher:
             dev_lengths = up('l', lengths)
             ev = torch.cuda.Event()
             ev.record(stream)
-        return dev_batch, dev_lengths, ev
+        return dev_batch, dev_lengths, ev, None
 
     def __iter__(self):
         if self.device.type != 'cuda':
-            yield from self.loader
+            for item in self.loader:
+                if isinstance(item, CompressedBatch):
+                    raise RuntimeError('enable_gpu_decode needs a ROCm device; got ' + str(self.device))
+                yield item
             return
         stream = torch.cuda.Stream(self.device)
         it = iter(self.loader)
@@ -144,9 +215,13 @@ class DevicePrefetcher:
             if not fill():
                 break
         while queue:
-            batch, lengths, ev = queue.pop(0)
+            batch, lengths, ev, decoded = queue.pop(0)
             cur = torch.cuda.current_stream(self.device)
             cur.wait_event(ev)
+            if decoded is not None:
+                if decoded.summary is not None:
+                    decoded.summary.record_stream(cur)
+                decoded.check()          # the per-frame status, read once: ValueError naming the member
             for t in (batch if isinstance(batch, list) else [batch]) + [lengths]:
                 t.record_stream(cur)
             fill()                       # next copy runs while this batch computes
@@ -485,6 +560,7 @@ class BreverDataset(torch.utils.data.Dataset):
         self.transform = transform
         self.preloaded_data = None
         self._ext = None
+        self._gpu_decode = False          # enable_gpu_decode (no constructor argument: the reference's signature)
         self.get_segment_info()
 
     # -- files ---------------------------------------------------------------------------------
@@ -579,16 +655,117 @@ class BreverDataset(torch.utils.data.Dataset):
     def __getitem__(self, index):
         if self.preloaded_data is not None:
             return self.preloaded_data[index]
+        if self._gpu_decode:
+            return self.load_compressed(index)
         sources = self.load_segment(index)
         if self.transform is not None:
             sources = self.transform(sources)
         return sources
+
+    def _read_members(self, file_idx):
+        """(names, bytes, frame tables) of a file's sources; a table is ``flac_gpu.HOST_MEMBER`` where the
+        GPU decoder does not take the member (its sample rate is checked after the host decode, ``_check_fs``)."""
+        from . import flac_gpu
+        names = self.build_paths(file_idx)
+        members, tables = [], []
+        for p in names:
+            with self.get_file(p) as f:
+                blob = f.read()
+            try:
+                table = flac_gpu.index(blob, p)
+            except flac_gpu.FlacIndexError as e:
+                if e.code != flac_gpu.NOT_TAKEN:
+                    raise
+                table = flac_gpu.HOST_MEMBER
+            if not isinstance(table, str) and table[0]['sample_rate'] != self.fs:
+                raise ValueError('file sampling rate does not match dataset fs attribute, got '
+                                 f"{table[0]['sample_rate']} and {self.fs}")
+            members.append(blob)
+            tables.append(table)
+        return names, members, tables
+
+    def _check_fs(self, decoded):
+        """The sample-rate check of ``load_file`` for a decoded batch, host-decoded members included."""
+        for fs in decoded.sample_rates:
+            if fs != self.fs:
+                raise ValueError('file sampling rate does not match dataset fs attribute, got '
+                                 f'{fs} and {self.fs}')
+
+    def load_compressed(self, index):
+        """The ``CompressedItem`` of segment ``index``: what ``load_segment`` reads and cuts, left
+        compressed. The ``random`` strategy's draw stays here, on the host."""
+        file_idx, (start, end) = self._segment_info[index]
+        if self.segment_strategy == 'random' and self.segment_length != 0.0:
+            start = random.randint(start, end - self.segment_length)
+            end = start + self.segment_length
+        names, members, tables = self._read_members(file_idx)
+        for table in tables:
+            if not isinstance(table, str) and end > table[0]['total_samples'] \
+                    and self.segment_strategy not in ('pad', 'random'):
+                raise ValueError("attempting to load a segment outside of file range but segment "
+                                 f"strategy is not in ['pad', 'random'], got "
+                                 f'{self.segment_strategy}')
+        return CompressedItem(members, tables, (start, end), names)
+
+    # compressed bytes decoded per launch by the GPU path of preload: about 4 x as many bytes of float32
+    # samples and as much scratch again
+    PRELOAD_BYTE_BUDGET = 32 << 20
+
+    def _preload_gpu(self, device):
+        """FLAC members on a ROCm device: every file is read, indexed and decoded ONCE, in chunks of
+        ``PRELOAD_BYTE_BUDGET`` compressed bytes; the segments are cut on the device."""
+        from . import flac_gpu
+        decoder = flac_gpu.FlacBatchDecoder(device)
+        by_file = {}
+        for i, (file_idx, _) in enumerate(self._segment_info):
+            by_file.setdefault(file_idx, []).append(i)
+        data = [None]*len(self)
+        chunk, chunk_bytes, chunk_frames = [], 0, 0
+
+        def flush():
+            nonlocal chunk, chunk_bytes, chunk_frames
+            if not chunk:
+                return
+            decoded = decoder.decode([c[2] for c in chunk], names=[c[1] for c in chunk],
+                                     tables=[c[3] for c in chunk]).check()
+            self._check_fs(decoded)
+            for k, (file_idx, _, _, _) in enumerate(chunk):
+                n = decoded.lengths[k]
+                for i in by_file[file_idx]:
+                    _, (start, end) = self._segment_info[i]
+                    if end > n and self.segment_strategy not in ('pad', 'random'):
+                        raise ValueError("attempting to load a segment outside of file range but segment "
+                                         f"strategy is not in ['pad', 'random'], got "
+                                         f'{self.segment_strategy}')
+                    item = decoded.data[k, ..., start:min(end, n)]
+                    item = F.pad(item, (0, end - n)) if end > n else item.clone()
+                    if self.transform is not None:
+                        item = self.transform(item)
+                    data[i] = item.to(device) if isinstance(item, torch.Tensor) \
+                        else [t.to(device) for t in item]
+            chunk, chunk_bytes, chunk_frames = [], 0, 0
+
+        for file_idx in sorted(by_file):
+            names, members, tables = self._read_members(file_idx)
+            size = sum(len(b) for b in members)
+            n_frames = sum(len(t[1]) for t in tables if not isinstance(t, str))
+            # (one launch takes 65535 x 64 frames: include/brever_flac.h)
+            if chunk and (chunk_bytes + size > self.PRELOAD_BYTE_BUDGET or chunk_frames + n_frames > 4_000_000):
+                flush()
+            chunk.append((file_idx, names, members, tables))
+            chunk_bytes += size
+            chunk_frames += n_frames
+        flush()
+        self.preloaded_data = data
 
     def preload(self, device, tqdm_desc=None):
         if self.segment_strategy == 'random':
             raise ValueError("can't preload when segment_strategy is 'random'")
         if self.rmm_dset is not None:
             raise ValueError("can't preload when using dynamic mixing")
+        if self._ext == 'flac' and torch.device(device).type == 'cuda' \
+                and all(start >= 0 for _, (start, _) in self._segment_info):
+            return self._preload_gpu(torch.device(device))
         data = []
         for i in range(len(self)):
             item = self[i]

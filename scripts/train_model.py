@@ -105,6 +105,13 @@ def main(args):
         segment_strategy='pass', max_segment_length=max_segment_length, tar=ds.tar,
         dynamic_mixing=False)
 
+    if args.gpu_decode:
+        # FLAC members travel compressed through the loader; the trainer's DevicePrefetcher decodes them on the
+        # device (brever_amd/flac_gpu.py). preload decodes FLAC on the device with or without this flag.
+        from brever_amd.data import enable_gpu_decode
+        enable_gpu_decode(train_dataset)
+        enable_gpu_decode(val_dataset)
+
     ignore_checkpoint = trainer_kwargs.pop('ignore_checkpoint')
     trainer = BreverTrainer(
         model=model, train_dataset=train_dataset, val_dataset=val_dataset,
@@ -122,6 +129,8 @@ if __name__ == '__main__':
     parser.add_argument('-f', '--force', action='store_true',
                         help='train even if already trained')
     parser.add_argument('--wandb_run_id', help='accepted for compatibility (wandb is absent)')
+    parser.add_argument('--gpu_decode', action='store_true',
+                        help='decode the FLAC members of the datasets on the GPU (on-the-fly batches)')
     group = parser.add_argument_group('the following options supersede the config file')
     ModelArgParser.add_dataset_args(group, new_group=False)
     ModelArgParser.add_trainer_args(group, new_group=False)
