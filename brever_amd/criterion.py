@@ -8,7 +8,8 @@ folded into the reduction kernels: ``lengths`` stays on the device and there
 is no per-item host synchronisation.
 
 ``stoi`` / ``estoi`` are not in the reference: minus the STOI / ESTOI metric as a training criterion, forward by the
-metric's own launches and backward in ``libbrever_stoi_loss.so`` (``stoi.py``).
+metric's own launches and backward in ``libbrever_stoi_loss.so`` (``stoi.py``). ``sdr`` is not in the reference
+either: minus the BSS-eval signal-to-distortion ratio, forward and backward in ``libbrever_sdr.so`` (``sdr.py``).
 
 The arithmetic runs in ``libbrever_hip.so`` (``brv_snr_forward`` ...); CPU
 tensors are rejected (no fallback) -- the CPU restatement used for checking
@@ -19,6 +20,7 @@ import inspect
 import torch
 
 from . import hip
+from . import sdr as sdr_hip
 from . import stoi as stoi_hip
 from .registry import Registry
 
@@ -248,6 +250,47 @@ class StoiLoss(_StoiLossBase):
 class EstoiLoss(_StoiLossBase):
     """``StoiLoss`` for the extended measure (Jensen & Taal 2016): minus ``MetricRegistry.get('estoi')``."""
     extended = True
+
+
+class _SdrFunction(torch.autograd.Function):
+    """Minus the BSS-eval SDR per ``(item, middle index)`` row over the item's length, mean over the middle axes;
+    0 for a degenerate row. Only ``x`` gets a gradient; it is zero at and beyond the length."""
+
+    @staticmethod
+    def forward(ctx, x, y, lengths, filter_length, load_diag):
+        x2, y2, lengths, B, S, L = _rows(x, y, lengths)
+        row_lengths = lengths if S == 1 else lengths.repeat_interleave(S)
+        value, saved = sdr_hip.forward(x2.view(B*S, L), y2.view(B*S, L), row_lengths, filter_length, load_diag)
+        ctx.saved = saved
+        ctx.meta = (x.shape, x.dtype, B, S)
+        loss = torch.where((saved['flags'] & sdr_hip.DEGENERATE) != 0, torch.zeros_like(value), -value)
+        return (loss if S == 1 else loss.view(B, S).mean(1)).float()
+
+    @staticmethod
+    def backward(ctx, grad):
+        shape, in_dtype, B, S = ctx.meta
+        g = grad.double()
+        grow = (g if S == 1 else (g/S).repeat_interleave(S)).contiguous()
+        dx = sdr_hip.backward(ctx.saved, grow)
+        return dx.view(shape).to(in_dtype), None, None, None, None
+
+
+@CriterionRegistry.register('sdr')
+class SdrLoss:
+    """Minus the BSS-eval signal-to-distortion ratio in dB (Vincent et al. 2006) of the estimate ``x`` against the
+    target ``y`` with an allowed distortion filter of ``filter_length`` taps and a diagonal loading of
+    ``load_diag r[0]``, ``(B, ..., L)`` -> ``(B,)``: minus ``MetricRegistry.get('sdr')``, mean over the middle axes,
+    no permutation search, differentiable in ``x``. A degenerate row -- a target or an estimate that is zero
+    inside the length, or a solver pivot that is not positive -- has loss 0 and a zero gradient (the metric gives
+    NaN)."""
+
+    def __init__(self, filter_length=512, load_diag=0.0):
+        self.filter_length, self.load_diag = sdr_hip.check_options(filter_length, load_diag)
+
+    def __call__(self, x, y, lengths):
+        assert x.shape == y.shape
+        assert x.ndim >= 2
+        return _SdrFunction.apply(x, y, lengths, self.filter_length, self.load_diag)
 
 
 @CriterionRegistry.register('multiresyu')

@@ -3,6 +3,9 @@ signatures -- ``metric(x, y, ..., lengths=None)`` with ``x`` the processed signa
 clean target, batched ``(B, L)`` or single ``(L,)``.
 
 * ``snr`` / ``sisnr``: minus the HIP criteria;
+* ``sdr`` (not in the reference): the BSS-eval signal-to-distortion ratio with a 512-tap allowed distortion filter,
+  in fp64 on the HIP path (``sdr.py``, ``csrc/sdr/sdr.hip``); the call shape of ``snr`` plus ``filter_length`` and
+  ``load_diag``;
 * ``stoi`` / ``estoi``: the reference calls the ``pystoi`` / ``batch_pystoi`` wheels (absent from
   this image, not under the reference tree). Here the published algorithm runs as HIP kernels
   (``csrc/stoi.hip``: polyphase resampling to 10 kHz, silent-frame removal, one-third octave band
@@ -17,6 +20,7 @@ import numpy as np
 import torch
 
 from . import hip
+from . import sdr as sdr_hip
 from . import stoi as stoi_hip
 from .criterion import CriterionRegistry
 from .registry import Registry
@@ -154,3 +158,20 @@ def _negated(name):
 
 snr = MetricRegistry.register('snr')(_negated('snr'))
 sisnr = MetricRegistry.register('sisnr')(_negated('sisnr'))
+
+
+@MetricRegistry.register('sdr')
+def sdr(x, y, lengths=None, filter_length=512, load_diag=0.0):
+    """BSS-eval signal-to-distortion ratio in dB with an allowed distortion filter of ``filter_length`` taps
+    (``sdr.forward``): a ``(B,)`` fp64 tensor on the inputs' device, or a float for a single row. NaN for a
+    degenerate row (a target or an estimate that is zero inside the length, a solver pivot that is not
+    positive)."""
+    filter_length, load_diag = sdr_hip.check_options(filter_length, load_diag)
+    x, y = torch.as_tensor(x), torch.as_tensor(y)
+    hip.require_device(x, y)
+    x, y, lengths, unbatched = _check_input(x, y, lengths)
+    B, W = x.shape[0], x.shape[-1]
+    lengths = torch.as_tensor(lengths).to(device=x.device, dtype=torch.int64).contiguous()
+    value, _ = sdr_hip.forward(x.detach().reshape(B, W).float().contiguous(),
+                               y.detach().reshape(B, W).float().contiguous(), lengths, filter_length, load_diag)
+    return value.item() if unbatched else value
