@@ -1,0 +1,198 @@
+"""Batches of signals encoded as FLAC on the GPU (``libbrever_flacenc.so``, include/brever_flacenc.h):
+the counterpart of ``flac_gpu.FlacBatchDecoder``.
+
+``FlacBatchEncoder.encode`` takes a padded device batch ``(B, C, L)`` (or ``(B, L)``) with per-row lengths and
+returns one complete FLAC stream of RFC 9639 per row as ``bytes``: mono or stereo, 16 or 24 bits, CONSTANT / VERBATIM
+/ FIXED / LPC subframes chosen by exact coded size, partitioned Rice residuals, all four stereo decorrelations. The
+samples never travel to the host as float32; what is downloaded is the offset table (a few words per row) and then
+the compressed bytes in one copy. ``submit`` is the same without waiting: it queues the kernels and the table's copy
+on the current stream and returns a ``PendingStreams`` whose ``result()`` waits for that batch only and downloads
+the bytes on a side stream, so that a writer can overlap it with whatever it queued in between.
+
+``brv_flac_encode16`` of the main library (mono, 16 bits, FIXED predictors; ``data.flac_bytes``) is untouched.
+There is no fallback: without the library or a ROCm device the calls raise.
+"""
+import ctypes
+import os
+
+import torch
+
+from . import hip
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.environ.get('BRV_FLACENC_LIB_PATH') or os.path.join(_HERE, 'csrc', 'libbrever_flacenc.so')
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'brever_flacenc.h')
+
+ROW_MESSAGES = {1: 'a non-finite sample', 2: 'a PCM sample outside the range of the bit depth',
+                4: 'a length outside 1 ... the padded length', 8: 'a frame did not fit its image'}
+MAX_ROWS, MAX_LPC_ORDER = 65535, 32
+
+
+def _header_signatures():
+    if not os.path.exists(HEADER_PATH):
+        raise RuntimeError(f'{HEADER_PATH} is missing: the binding is derived from the C header')
+    with open(HEADER_PATH) as f:
+        return hip.parse_header(f.read())
+
+
+# name -> (restype, argtypes) of every brv_flacenc_* entry point, read from include/brever_flacenc.h
+SIGNATURES = _header_signatures()
+_lib = None
+
+
+def lib():
+    """Load ``libbrever_flacenc.so`` once; fail loudly if it is not built."""
+    global _lib
+    if _lib is None:
+        if not os.path.exists(LIB_PATH):
+            raise RuntimeError(f'{LIB_PATH} is missing: build it with `python -c "import __graft_entry__ as g; '
+                               'g.build()"` or `make -C brever_amd/csrc` (needs hipcc, targets gfx950). '
+                               'The GPU FLAC encoder has no fallback.')
+        handle = ctypes.CDLL(LIB_PATH)
+        for name, (restype, argtypes) in SIGNATURES.items():
+            fn = getattr(handle, name)
+            fn.restype, fn.argtypes = restype, argtypes
+        _lib = handle
+    return _lib
+
+
+def last_error():
+    msg = lib().brv_flacenc_last_error()
+    return msg.decode() if msg else ''
+
+
+def call(name, *args):
+    """Call the ``brv_flacenc_*`` entry point ``name``; a non-zero status raises with the library's message."""
+    status = getattr(lib(), name)(*args)
+    if status:
+        raise RuntimeError(f'{name} failed with status {status}: {last_error()}')
+
+
+def query(name, *args):
+    """A size query of the library; a negative answer raises with the library's message."""
+    n = int(getattr(lib(), name)(*args))
+    if n < 0:
+        raise ValueError(f'{name}{args}: {last_error()}')
+    return n
+
+
+def status_message(status):
+    return ', '.join(text for bit, text in ROW_MESSAGES.items() if status & bit) or f'status {status}'
+
+
+class PendingStreams:
+    """A batch that ``FlacBatchEncoder.submit`` queued. ``result()`` gives the ``list[bytes]``."""
+
+    def __init__(self, encoder, out, table_dev, table_host, event, rows, keep):
+        self._encoder, self._out, self._table_dev, self._table = encoder, out, table_dev, table_host
+        self._event, self._rows, self._keep = event, rows, keep
+        self._streams = None
+        self.seconds = {}                                      # wait / copy, filled by result()
+
+    def result(self, check=True):
+        """Wait for this batch, download its bytes in one copy on the encoder's side stream and cut them into
+        rows. A row with a non-zero status raises ``ValueError`` naming the row (``check=False``: gives ``None``
+        in its place)."""
+        import time
+        if self._streams is None:
+            t0 = time.perf_counter()
+            self._event.synchronize()
+            t1 = time.perf_counter()
+            rows = self._rows
+            table = self._table.tolist()
+            offsets, sizes, status = table[:rows + 1], table[rows + 1:2*rows + 1], table[2*rows + 1:]
+            total = offsets[rows]
+            data = b''
+            if total:
+                enc = self._encoder
+                host = enc._pin('bytes', total)
+                with torch.cuda.stream(enc._side):
+                    host[:total].copy_(self._out[:total], non_blocking=True)
+                enc._side.synchronize()
+                data = host[:total].numpy().tobytes()
+            self._streams = [None if status[r] else data[offsets[r]:offsets[r] + sizes[r]] for r in range(rows)]
+            self._status = status
+            self._out = self._table_dev = self._keep = None    # the device buffers are free again
+            self.seconds = dict(wait=t1 - t0, copy=time.perf_counter() - t1)
+        if check:
+            for r, st in enumerate(self._status):
+                if st:
+                    raise ValueError(f'row {r} was not encoded: {status_message(st)} (status {st})')
+        return self._streams
+
+    @property
+    def status(self):
+        self.result(check=False)
+        return list(self._status)
+
+
+class FlacBatchEncoder:
+    """Encodes batches on ``device``. It owns the pinned staging of the downloads; the scratch and the output buffer
+    of a batch belong to that batch until its ``result()`` was taken, so several batches may be in flight."""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+        if self.device.type != 'cuda':
+            raise RuntimeError(f'the GPU FLAC encoder runs on a ROCm device only; got {self.device} '
+                               '(brv_flac_encode16 is the host encoder)')
+        lib()
+        self._pinned = {}
+        self._side = torch.cuda.Stream(device=self.device)
+
+    def _pin(self, key, nbytes):
+        buf = self._pinned.get(key)
+        if buf is None or buf.numel() < nbytes:
+            buf = torch.empty(max(nbytes, 1), dtype=torch.uint8).pin_memory()
+            self._pinned[key] = buf
+        return buf
+
+    def submit(self, x, lengths=None, fs=16000, bits_per_sample=16, block_size=4096, lpc_order=8, pcm=False,
+               events=None):
+        """Queue the encode of ``x`` on the current stream; nothing here waits for the device. ``x``: ``(B, C, L)``
+        or ``(B, L)`` on the device, float32 (quantised as ``clip(rint(x 2^(bits-1)), -2^(bits-1), 2^(bits-1) - 1)``)
+        or, with ``pcm=True``, int32 already in that range. ``lengths``: per row, a sequence or a tensor; ``None``
+        for ``L`` everywhere. ``events``: a list that gets a pair of ``torch.cuda.Event`` around the kernels
+        (tools/flac_enc_bench.py)."""
+        if x.device != self.device and not (x.is_cuda and self.device.index is None):
+            raise ValueError(f'x is on {x.device}, the encoder on {self.device}')
+        if x.dim() == 2:
+            x = x.unsqueeze(1)
+        if x.dim() != 3:
+            raise ValueError(f'x is (B, C, L) or (B, L), got {tuple(x.shape)}')
+        want = torch.int32 if pcm else torch.float32
+        if x.dtype != want:
+            raise ValueError(f'x must be {want} with pcm={pcm}, got {x.dtype}')
+        x = x.contiguous()
+        rows, channels, max_len = x.shape
+        if lengths is None:
+            lengths = torch.full((rows,), max_len, dtype=torch.int64, device=x.device)
+        elif isinstance(lengths, torch.Tensor):
+            lengths = lengths.to(device=x.device, dtype=torch.int64).contiguous()
+        else:
+            lengths = torch.tensor([int(n) for n in lengths], dtype=torch.int64).to(x.device, non_blocking=True)
+        if lengths.shape != (rows,):
+            raise ValueError(f'lengths has shape {tuple(lengths.shape)}, the batch {rows} rows')
+        extents = (rows, channels, max_len, int(bits_per_sample), int(block_size))
+        scratch_elems = query('brv_flacenc_scratch_elems', *extents)
+        capacity = query('brv_flacenc_out_capacity', *extents)
+        scratch = torch.empty(scratch_elems, dtype=torch.int32, device=x.device)
+        out = torch.empty(capacity, dtype=torch.uint8, device=x.device)
+        table = torch.empty(3*rows + 1, dtype=torch.int64, device=x.device)
+        if events is not None:
+            events.append(torch.cuda.Event(enable_timing=True))
+            events[-1].record()
+        call('brv_flacenc_encode', x, 1 if pcm else 0, lengths, rows, channels, max_len, int(fs), int(bits_per_sample),
+             int(block_size), int(lpc_order), scratch, scratch_elems, out, capacity, table, hip.stream())
+        if events is not None:
+            events.append(torch.cuda.Event(enable_timing=True))
+            events[-1].record()
+        host = torch.empty(3*rows + 1, dtype=torch.int64).pin_memory()
+        host.copy_(table, non_blocking=True)
+        event = torch.cuda.Event()
+        event.record()
+        return PendingStreams(self, out, table, host, event, rows, (x, lengths, scratch))
+
+    def encode(self, x, lengths=None, fs=16000, bits_per_sample=16, block_size=4096, lpc_order=8, pcm=False):
+        """``submit(...).result()``: the streams of the batch as ``list[bytes]``; a row with a non-zero status raises
+        ``ValueError`` naming the row."""
+        return self.submit(x, lengths, fs, bits_per_sample, block_size, lpc_order, pcm).result()

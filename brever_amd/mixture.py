@@ -935,3 +935,88 @@ class PoolMixtureMaker:
         if self._items is None:
             self.set_epoch(self._epoch)
         return self._items[i]
+
+    # -- a fixed dataset on disk ------------------------------------------------------------------------------
+    def write_dataset(self, path, epoch=0, bits_per_sample=16, tar=True, block_size=4096, lpc_order=8):
+        """Freeze ``epoch`` as a dataset ``BreverDataset(path)`` reads: ``path/audio.tar`` with members
+        ``audio/NNNNN_<source>.flac`` (``tar=False``: the directory ``path/audio/``) and ``path/mixture_info.json``,
+        the list ``draw(epoch)`` returns. The epoch is synthesised batch by batch and every source is encoded on
+        the device (``flac_enc.FlacBatchEncoder``): the float32 components never go to the host. Two batches
+        stay queued behind the one whose bytes are being downloaded and written, as in ``set_epoch``. Member names,
+        order, mode, owner and mtime (0) are fixed, so ``(seed, epoch)`` gives byte-identical archives. The maker's
+        own epoch is left as it is. Returns the seconds spent per stage (``synthesis`` and ``encode`` are the
+        host's time to queue them; the device's time shows up in ``wait``)."""
+        import io
+        import json
+        import tarfile
+        from .flac_enc import FlacBatchEncoder, status_message
+        meta = self.draw(epoch)
+        encoder = FlacBatchEncoder(self.device)
+        os.makedirs(path, exist_ok=True)
+        seconds = dict(synthesis=0.0, encode=0.0, wait=0.0, copy=0.0, write=0.0)
+        if tar:
+            archive = tarfile.open(os.path.join(path, 'audio.tar'), 'w', format=tarfile.GNU_FORMAT)
+        else:
+            archive = None
+            os.makedirs(os.path.join(path, 'audio'), exist_ok=True)
+
+        def finish(res, pending, start):
+            t0 = time.perf_counter()
+            res.check()                            # waits for the batch's synthesis
+            seconds['wait'] += time.perf_counter() - t0
+            for name, p in zip(self.sources, pending):
+                streams = p.result(check=False)
+                seconds['wait'] += p.seconds['wait']
+                seconds['copy'] += p.seconds['copy']
+                for j, st in enumerate(p.status):
+                    if st:
+                        raise ValueError(f'mixture {start + j}, source {name}: {status_message(st)}')
+                t0 = time.perf_counter()
+                for j, blob in enumerate(streams):
+                    member = f'audio/{start + j:05d}_{name}.flac'
+                    if archive is None:
+                        with open(os.path.join(path, member), 'wb') as f:
+                            f.write(blob)
+                    else:
+                        info = tarfile.TarInfo(member)
+                        info.size, info.mtime, info.mode = len(blob), 0, 0o644
+                        info.uid = info.gid = 0
+                        info.uname = info.gname = ''
+                        archive.addfile(info, io.BytesIO(blob))
+                seconds['write'] += time.perf_counter() - t0
+
+        try:
+            queue = []
+            for start in range(0, self.size, self.batch):
+                t0 = time.perf_counter()
+                res = self.synthesize(meta[start:start + self.batch])
+                t1 = time.perf_counter()
+                # components are (mixtures, frames, 2): the encoder takes (rows, channels, frames)
+                pending = [encoder.submit(res.components[name].transpose(1, 2), res.lengths, fs=self.fs,
+                                          bits_per_sample=bits_per_sample, block_size=block_size,
+                                          lpc_order=lpc_order) for name in self.sources]
+                seconds['synthesis'] += t1 - t0
+                seconds['encode'] += time.perf_counter() - t1
+                queue.append((res, pending, start))
+                if len(queue) > 2:
+                    finish(*queue.pop(0))
+            while queue:
+                finish(*queue.pop(0))
+        finally:
+            if archive is not None:
+                archive.close()
+
+        def clean(v):                              # numpy scalars and tuples out, NaN never occurs in a draw
+            if isinstance(v, dict):
+                return {str(k): clean(x) for k, x in v.items()}
+            if isinstance(v, (list, tuple)):
+                return [clean(x) for x in v]
+            if isinstance(v, (np.integer, np.bool_)):
+                return int(v)
+            if isinstance(v, np.floating):
+                return float(v)
+            return v
+        with open(os.path.join(path, 'mixture_info.json'), 'w') as f:
+            json.dump(clean(meta), f, indent=1, sort_keys=True)
+            f.write('\n')
+        return seconds

@@ -1,0 +1,96 @@
+"""Freeze mixtures synthesised on the GPU as a dataset on disk: ``DIR/audio.tar`` (members
+``audio/NNNNN_<source>.flac``) and ``DIR/mixture_info.json``, the layout ``BreverDataset`` and the entry points
+(``init_model.py --train_path DIR --val_path DIR``) read.
+
+A thin command line over ``brever_amd.mixture.PoolMixtureMaker.write_dataset``: the mixtures of ``--epoch`` are
+drawn from ``--seed``, synthesised batch by batch from the in-memory pools of ``--pool`` (a ``.npz`` with
+``speech_<i>``, ``noise_<i>``, ``brir_<room>_<angle>`` arrays) and encoded as stereo FLAC on the device; the same
+``(seed, epoch)`` gives byte-identical archives. Like the reference's ``scripts/create_dataset.py`` it refuses a
+directory that already holds a ``mixture_info.json`` unless ``-f`` is given, and ``--no_tar`` writes the directory
+``DIR/audio/`` instead of the archive.
+
+Differences, on purpose: the reference's script takes a dataset directory whose ``config.yaml`` holds an ``rmm``
+section (corpora, rooms, angle ranges, file limits) for ``RandomMixtureMaker``. This script does not read that
+configuration: there is no corpus scanning in this build. The pools are given as arrays and
+the maker's options by their own names, below."""
+import argparse
+import os
+import time
+
+# read when the HIP runtime loads (torch import): see brever_amd/__init__.py
+os.environ.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')
+
+from _common import ROOT  # noqa: E402,F401
+
+COMPONENTS = ('mixture', 'foreground', 'background', 'speech', 'noise', 'early_speech', 'late_speech', 'dir_noise',
+              'diffuse')
+
+
+def parse(argv=None):
+    p = argparse.ArgumentParser(description='write a fixed dataset of GPU-synthesised mixtures')
+    p.add_argument('--pool', required=True, help='.npz with speech_<i>, noise_<i>, brir_<room>_<angle> arrays')
+    p.add_argument('--output', required=True, help='dataset directory to write')
+    p.add_argument('--size', type=int, required=True, help='number of mixtures')
+    p.add_argument('--sources', nargs='+', default=['mixture', 'foreground'], choices=COMPONENTS)
+    p.add_argument('--seed', type=int, default=0)
+    p.add_argument('--epoch', type=int, default=0, help='which epoch of the seed to freeze')
+    p.add_argument('--bits', type=int, default=16, choices=(16, 24), help='bits per sample of the FLAC members')
+    p.add_argument('--no_tar', action='store_true', help='write the directory audio/ instead of audio.tar')
+    p.add_argument('-f', '--force', action='store_true', help='overwrite if already exists')
+    p.add_argument('--block_size', type=int, default=4096, help='FLAC block size')
+    p.add_argument('--lpc_order', type=int, default=8, help='0 switches the LPC candidates off')
+    # the maker's options, by its own names
+    p.add_argument('--fs', type=int, default=16000)
+    p.add_argument('--padding', type=float, default=0.0)
+    p.add_argument('--noise_count', type=int, nargs=2, default=[0, 3])
+    p.add_argument('--snr', type=float, nargs=2, default=[-5.0, 10.0])
+    p.add_argument('--ndr', type=float, nargs=2, default=[0.0, 30.0])
+    p.add_argument('--diffuse', action='store_true')
+    p.add_argument('--rms_jitter', type=float, nargs=2, default=[0.0, 0.0])
+    p.add_argument('--batch', type=int, default=64, help='mixtures per synthesis batch')
+    p.add_argument('--block', type=int, default=256, help='partition size of the convolution')
+    p.add_argument('--device', default='cuda')
+    p.add_argument('--diffuse_color', default='white')
+    p.add_argument('--diffuse_ltas_eq', action='store_true')
+    p.add_argument('--decay', action='store_true')
+    p.add_argument('--decay_color', default='white')
+    p.add_argument('--decay_rt60', type=float, nargs=2, default=[0.1, 5.0])
+    p.add_argument('--decay_drr', type=float, nargs=2, default=[5.0, 35.0])
+    p.add_argument('--decay_delay', type=float, nargs=2, default=[0.075, 0.100])
+    p.add_argument('--synthetic_noises', nargs='*', default=[])
+    return p.parse_args(argv)
+
+
+def main(argv=None):
+    args = parse(argv)
+    info = os.path.join(args.output, 'mixture_info.json')
+    if os.path.exists(info) and not args.force:
+        raise SystemExit(f'{info} already exists: a dataset was written here; pass -f to overwrite it')
+    if args.size < 1:
+        raise SystemExit('--size must be at least 1')
+    from brever_amd.mixture import PoolMixtureMaker
+    maker = PoolMixtureMaker(
+        args.pool, args.sources, args.size, seed=args.seed, fs=args.fs, padding=args.padding,
+        noise_count=args.noise_count, snr=args.snr, ndr=args.ndr, diffuse=args.diffuse, rms_jitter=args.rms_jitter,
+        batch=args.batch, block=args.block, device=args.device, diffuse_color=args.diffuse_color,
+        diffuse_ltas_eq=args.diffuse_ltas_eq, decay=args.decay, decay_color=args.decay_color,
+        decay_rt60=args.decay_rt60, decay_drr=args.decay_drr, decay_delay=args.decay_delay,
+        synthetic_noises=args.synthetic_noises)
+    if args.force:                                 # what the other form of an earlier run left
+        import shutil
+        stale = os.path.join(args.output, 'audio' if not args.no_tar else 'audio.tar')
+        if os.path.isdir(stale):
+            shutil.rmtree(stale)
+        elif os.path.exists(stale):
+            os.remove(stale)
+    t0 = time.perf_counter()
+    seconds = maker.write_dataset(args.output, epoch=args.epoch, bits_per_sample=args.bits, tar=not args.no_tar,
+                                  block_size=args.block_size, lpc_order=args.lpc_order)
+    total = time.perf_counter() - t0
+    audio = sum(maker.draw(args.epoch)[i]['frames'] for i in range(args.size))/args.fs
+    print(f'{args.size} mixtures, {audio:.1f} s of audio per source, written in {total:.2f} s: ' +
+          ', '.join(f'{k} {v:.2f} s' for k, v in seconds.items()))
+
+
+if __name__ == '__main__':
+    main()
