@@ -582,3 +582,6 @@ int brv_ffs_step_emit(const brv_ffs_config* cfg, const float* window, void* stat
 }
 
 }  // extern "C"
+
+// the library's last-error message and its two status exports (../status.h)
+BRV_DEFINE_STATUS(brv_ffs_version, brv_ffs_last_error)

@@ -421,3 +421,6 @@ int brv_flacdec_decode(const uint8_t* bytes, int64_t bytes_size, const int64_t* 
 }
 
 }  // extern "C"
+
+// the library's last-error message and its two status exports (../status.h)
+BRV_DEFINE_STATUS(brv_flacdec_version, brv_flacdec_last_error)

@@ -297,3 +297,6 @@ int brv_flacenc_encode(const void* x, int64_t pcm, const int64_t* lengths, int64
 }
 
 }  // extern "C"
+
+// the library's last-error message and its two status exports (../status.h)
+BRV_DEFINE_STATUS(brv_flacenc_version, brv_flacenc_last_error)

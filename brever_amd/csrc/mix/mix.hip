@@ -454,3 +454,6 @@ int brv_mix_compose(const float* y, const double* gains, const int32_t* mix, con
 }
 
 }
+
+// the library's last-error message and its two status exports (../status.h)
+BRV_DEFINE_STATUS(brv_mix_version, brv_mix_last_error)

@@ -252,3 +252,6 @@ int brv_mixfx_decay_brirs(const float* brir_pool, const float* noise_pool, const
 }
 
 }
+
+// the library's last-error message and its two status exports (../status.h)
+BRV_DEFINE_STATUS(brv_mixfx_version, brv_mixfx_last_error)

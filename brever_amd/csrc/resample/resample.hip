@@ -330,3 +330,6 @@ int brv_rs_synthesis(double* work, const int64_t* desc, const double* slab, cons
 }
 
 }
+
+// the library's last-error message and its two status exports (../status.h)
+BRV_DEFINE_STATUS(brv_rs_version, brv_rs_last_error)

@@ -334,3 +334,6 @@ int brv_sdr_backward(const float* x, const float* y, const int64_t* lengths, con
 }
 
 }
+
+// the library's last-error message and its two status exports (../status.h)
+BRV_DEFINE_STATUS(brv_sdr_version, brv_sdr_last_error)

@@ -7,9 +7,26 @@
 
 namespace brv {
 
-// Stores msg in the library's thread-local message (status.hip) and returns code.
+// Stores msg in the library's thread-local message (BRV_DEFINE_STATUS) and returns code.
 __attribute__((visibility("hidden"))) int fail(int code, const char* msg);
-inline int fail(int code, const std::string& msg) { return fail(code, msg.c_str()); }
+// (hidden as well: next to the definition the compiler may emit this overload out of line, and as a weak default
+// symbol one library's copy could be bound to another's, whose message it would then set)
+__attribute__((visibility("hidden"))) inline int fail(int code, const std::string& msg) {
+  return fail(code, msg.c_str());
+}
+
+// The library's last-error message and its two status exports: one thread-local string, written through brv::fail
+// only (hidden: every library has its own, non-interposable copy) and read through last_error_fn. Goes into exactly
+// ONE translation unit per shared library, at file scope, after the library's header has declared the two names.
+#define BRV_DEFINE_STATUS(version_fn, last_error_fn)                                                    \
+  namespace {                                                                                           \
+  thread_local std::string g_err;                                                                       \
+  }                                                                                                     \
+  int brv::fail(int code, const char* msg) { g_err = msg ? msg : ""; return code; }                     \
+  extern "C" {                                                                                          \
+  int version_fn(void) { return 100; }                                                                  \
+  const char* last_error_fn(void) { return g_err.c_str(); }                                             \
+  }
 
 // a failing HIP call ends the entry point with its hipError_t
 #define BRV_HIP_OK(expr)                                                                  \

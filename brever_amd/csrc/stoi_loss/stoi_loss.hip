@@ -353,3 +353,6 @@ int brv_sl_resample_backward(const float* dy, const float* hpad, const int64_t* 
 }
 
 }  // extern "C"
+
+// the library's last-error message and its two status exports (../status.h)
+BRV_DEFINE_STATUS(brv_sl_version, brv_sl_last_error)

@@ -12,64 +12,25 @@ the bytes on a side stream, so that a writer can overlap it with whatever it que
 ``brv_flac_encode16`` of the main library (mono, 16 bits, FIXED predictors; ``data.flac_bytes``) is untouched.
 There is no fallback: without the library or a ROCm device the calls raise.
 """
-import ctypes
-import os
-
 import torch
 
 from . import hip
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get('BRV_FLACENC_LIB_PATH') or os.path.join(_HERE, 'csrc', 'libbrever_flacenc.so')
-HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'brever_flacenc.h')
 
 ROW_MESSAGES = {1: 'a non-finite sample', 2: 'a PCM sample outside the range of the bit depth',
                 4: 'a length outside 1 ... the padded length', 8: 'a frame did not fit its image'}
 MAX_ROWS, MAX_LPC_ORDER = 65535, 32
 
 
-def _header_signatures():
-    if not os.path.exists(HEADER_PATH):
-        raise RuntimeError(f'{HEADER_PATH} is missing: the binding is derived from the C header')
-    with open(HEADER_PATH) as f:
-        return hip.parse_header(f.read())
-
-
-# name -> (restype, argtypes) of every brv_flacenc_* entry point, read from include/brever_flacenc.h
-SIGNATURES = _header_signatures()
-_lib = None
-
-
-def lib():
-    """Load ``libbrever_flacenc.so`` once; fail loudly if it is not built."""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError(f'{LIB_PATH} is missing: build it with `python -c "import __graft_entry__ as g; '
-                               'g.build()"` or `make -C brever_amd/csrc` (needs hipcc, targets gfx950). '
-                               'The GPU FLAC encoder has no fallback.')
-        handle = ctypes.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in SIGNATURES.items():
-            fn = getattr(handle, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        _lib = handle
-    return _lib
-
-
-def last_error():
-    msg = lib().brv_flacenc_last_error()
-    return msg.decode() if msg else ''
-
-
-def call(name, *args):
-    """Call the ``brv_flacenc_*`` entry point ``name``; a non-zero status raises with the library's message."""
-    status = getattr(lib(), name)(*args)
-    if status:
-        raise RuntimeError(f'{name} failed with status {status}: {last_error()}')
+# the brv_flacenc_* entry points of include/brever_flacenc.h
+_LIB = hip.Library('brever_flacenc.h', 'libbrever_flacenc.so', 'BRV_FLACENC_LIB_PATH',
+                   'The GPU FLAC encoder has no fallback.')
+LIB_PATH, HEADER_PATH, SIGNATURES = _LIB.path, _LIB.header_path, _LIB.signatures
+lib, call, last_error = _LIB.lib, _LIB.call, _LIB.last_error
 
 
 def query(name, *args):
-    """A size query of the library; a negative answer raises with the library's message."""
+    """A size query of the library; a negative answer is the caller's ``ValueError`` with the library's message, its
+    arguments named (``Library.query`` raises ``RuntimeError``)."""
     n = int(getattr(lib(), name)(*args))
     if n < 0:
         raise ValueError(f'{name}{args}: {last_error()}')

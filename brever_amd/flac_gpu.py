@@ -13,16 +13,11 @@ There is no other fallback: without the library or a ROCm device the calls raise
 """
 import ctypes
 import logging
-import os
 
 import numpy as np
 import torch
 
 from . import hip
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get('BRV_FLAC_LIB_PATH') or os.path.join(_HERE, 'csrc', 'libbrever_flac.so')
-HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'brever_flac.h')
 
 INFO_WORDS, FRAME_WORDS, JOB_WORDS = 8, 8, 12
 NOT_TAKEN, NOT_FLAC, BAD_HEADER, BAD_CRC16, BAD_NUMBER, TRUNCATED = -2, -10, -60, -61, -62, -63
@@ -34,44 +29,10 @@ INFO_FIELDS = ('sample_rate', 'channels', 'bits_per_sample', 'total_samples', 'm
                'first_frame', 'variable')
 
 
-def _header_signatures():
-    if not os.path.exists(HEADER_PATH):
-        raise RuntimeError(f'{HEADER_PATH} is missing: the binding is derived from the C header')
-    with open(HEADER_PATH) as f:
-        return hip.parse_header(f.read())
-
-
-# name -> (restype, argtypes) of every brv_flacdec_* entry point, read from include/brever_flac.h
-SIGNATURES = _header_signatures()
-_lib = None
-
-
-def lib():
-    """Load ``libbrever_flac.so`` once; fail loudly if it is not built."""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError(f'{LIB_PATH} is missing: build it with `python -c "import __graft_entry__ as g; '
-                               'g.build()"` or `make -C brever_amd/csrc` (needs hipcc, targets gfx950). '
-                               'The GPU FLAC decoder has no fallback.')
-        handle = ctypes.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in SIGNATURES.items():
-            fn = getattr(handle, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        _lib = handle
-    return _lib
-
-
-def last_error():
-    msg = lib().brv_flacdec_last_error()
-    return msg.decode() if msg else ''
-
-
-def call(name, *args):
-    """Call the ``brv_flacdec_*`` entry point ``name``; a non-zero status raises with the library's message."""
-    status = getattr(lib(), name)(*args)
-    if status:
-        raise RuntimeError(f'{name} failed with status {status}: {last_error()}')
+# the brv_flacdec_* entry points of include/brever_flac.h
+_LIB = hip.Library('brever_flac.h', 'libbrever_flac.so', 'BRV_FLAC_LIB_PATH', 'The GPU FLAC decoder has no fallback.')
+LIB_PATH, HEADER_PATH, SIGNATURES = _LIB.path, _LIB.header_path, _LIB.signatures
+lib, call, last_error = _LIB.lib, _LIB.call, _LIB.last_error
 
 
 class FlacIndexError(ValueError):

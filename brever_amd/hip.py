@@ -2,7 +2,8 @@
 
 ``include/brever_hip.h`` is the single declaration of the C ABI: ``SIGNATURES`` is parsed from it at import
 (``parse_header``), so an entry point is added or changed there and nowhere else. ``call`` / ``query`` invoke an
-entry point by name and raise with the library's own message; pointer arguments take tensors directly.
+entry point by name and raise with the library's own message; pointer arguments take tensors directly. ``Library``
+is that binding for any library of ``csrc/``: this module and every module with a library of its own use it once.
 
 The HIP library is the product; there is no CPU or PyTorch fallback. Every
 helper here raises ``RuntimeError`` when the shared library is missing or when
@@ -15,10 +16,6 @@ import re
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# BRV_LIB_PATH: load another build of the same library (tools/: diagnostic builds)
-LIB_PATH = os.environ.get('BRV_LIB_PATH') or os.path.join(_HERE, 'csrc', 'libbrever_hip.so')
-# the header sits next to the package (there is no install layout); diagnostic builds share it
-HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'brever_hip.h')
 
 _c_i64 = ctypes.c_int64
 
@@ -140,59 +137,77 @@ def parse_header(text):
     return table
 
 
-def _header_signatures():
-    if not os.path.exists(HEADER_PATH):
-        raise RuntimeError(f'{HEADER_PATH} is missing: the binding is derived from the C header')
-    with open(HEADER_PATH) as f:
+def _header_signatures(path=None):
+    path = path or HEADER_PATH
+    if not os.path.exists(path):
+        raise RuntimeError(f'{path} is missing: the binding is derived from the C header')
+    with open(path) as f:
         return parse_header(f.read())
 
 
-# name -> (restype, argtypes), read from the header; the export test checks every name resolves.
-SIGNATURES = _header_signatures()
+class Library:
+    """The binding of one shared library of ``csrc/``: ``include/<header>`` is the single declaration of its C ABI and
+    ``csrc/<soname>`` (or the build that the environment variable ``env`` names, read here) is loaded at the first
+    use. ``what`` ends the message of a library that is not built: there is no fallback. A module binds its library
+    once and takes ``lib``, ``call``, ``query`` and ``last_error`` from it as plain functions."""
 
-_lib = None
+    def __init__(self, header, soname, env, what, last_error=None):
+        self.header_path = os.path.join(os.path.dirname(_HERE), 'include', header)
+        self.path = os.environ.get(env) or os.path.join(_HERE, 'csrc', soname)
+        # name -> (restype, argtypes), read from the header; the export tests check every name resolves
+        self.signatures = _header_signatures(self.header_path)
+        if last_error is None:
+            last_error, = (name for name in self.signatures if name.endswith('_last_error'))
+        handle = None         # (a cell of the closures below: a call on the loaded library looks nothing else up)
+
+        def lib():
+            """Load the shared library once; fail loudly if it is not built."""
+            nonlocal handle
+            if handle is None:
+                if not os.path.exists(self.path):
+                    raise RuntimeError(
+                        f'{self.path} is missing: build it with '
+                        '`python -c "import __graft_entry__ as g; g.build()"` or '
+                        f'`make -C brever_amd/csrc` (needs hipcc, targets gfx950). {what}')
+                loaded = ctypes.CDLL(self.path)
+                for name, (restype, argtypes) in self.signatures.items():
+                    fn = getattr(loaded, name)
+                    fn.restype, fn.argtypes = restype, argtypes
+                handle = loaded
+            return handle
+
+        def message():
+            """The library's message of this thread's last failing call."""
+            msg = getattr(lib(), last_error)()
+            return msg.decode() if msg else ''
+
+        def check(status, what):
+            if status != 0:
+                raise RuntimeError(f'{what} failed with status {status}: {message()}')
+
+        def call(name, *args):
+            """Call the entry point ``name``, which returns an int status; anything but 0 raises with the library's
+            message."""
+            status = getattr(handle or lib(), name)(*args)
+            if status:
+                check(status, name)
+
+        def query(name, *args):
+            """Value of the int64_t size / count query ``name``; a negative one raises like ``call``."""
+            n = getattr(handle or lib(), name)(*args)
+            if n < 0:
+                check(int(n), name)
+            return n
+
+        self.lib, self.last_error, self.check, self.call, self.query = lib, message, check, call, query
 
 
-def lib():
-    """Load the shared library once; fail loudly if it is not built."""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError(
-                f'{LIB_PATH} is missing: build it with '
-                '`python -c "import __graft_entry__ as g; g.build()"` or '
-                '`make -C brever_amd/csrc` (needs hipcc, targets gfx950). '
-                'brever_amd has no CPU/PyTorch fallback for its kernels.'
-            )
-        handle = ctypes.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in SIGNATURES.items():
-            fn = getattr(handle, name)
-            fn.restype = restype
-            fn.argtypes = argtypes
-        _lib = handle
-    return _lib
-
-
-def check(status, what):
-    if status != 0:
-        msg = lib().brv_last_error()
-        raise RuntimeError(f'{what} failed with status {status}: '
-                           f'{msg.decode() if msg else ""}')
-
-
-def call(name, *args):
-    """Call the entry point ``name``, which returns an int status; anything but 0 raises with the library's message."""
-    status = getattr(_lib or lib(), name)(*args)
-    if status:
-        check(status, name)
-
-
-def query(name, *args):
-    """Value of the int64_t size / count query ``name``; a negative one raises like ``call``."""
-    n = getattr(_lib or lib(), name)(*args)
-    if n < 0:
-        check(int(n), name)
-    return n
+# BRV_LIB_PATH: load another build of the same library (tools/: diagnostic builds). The header sits next to the
+# package (there is no install layout); diagnostic builds share it.
+_LIB = Library('brever_hip.h', 'libbrever_hip.so', 'BRV_LIB_PATH',
+               'brever_amd has no CPU/PyTorch fallback for its kernels.')
+LIB_PATH, HEADER_PATH, SIGNATURES = _LIB.path, _LIB.header_path, _LIB.signatures
+lib, last_error, check, call, query = _LIB.lib, _LIB.last_error, _LIB.check, _LIB.call, _LIB.query
 
 
 def require_device(*tensors):

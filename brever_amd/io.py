@@ -15,59 +15,20 @@ fallback: without the library or a ROCm device the calls raise. A signal longer 
 or out) is refused, never truncated.
 """
 import collections
-import ctypes
-import os
 
 import numpy as np
 import torch
 
 from . import hip
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get('BRV_RESAMPLE_LIB_PATH') or os.path.join(_HERE, 'csrc', 'libbrever_resample.so')
-HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'brever_resample.h')
 MAX_COLUMNS = 32768                    # columns per launch (the library's bound)
 WORK_BYTES = 2 << 30                   # scratch per launch group: columns of one L are chunked to fit
 
-
-def _header_signatures():
-    if not os.path.exists(HEADER_PATH):
-        raise RuntimeError(f'{HEADER_PATH} is missing: the binding is derived from the C header')
-    with open(HEADER_PATH) as f:
-        return hip.parse_header(f.read())
-
-
-# name -> (restype, argtypes) of every brv_rs_* entry point, read from include/brever_resample.h
-SIGNATURES = _header_signatures()
-_lib = None
-
-
-def lib():
-    """Load ``libbrever_resample.so`` once; fail loudly if it is not built."""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError(f'{LIB_PATH} is missing: build it with `python -c "import __graft_entry__ as g; '
-                               'g.build()"` or `make -C brever_amd/csrc` (needs hipcc, targets gfx950). '
-                               'The resampler has no CPU fallback.')
-        handle = ctypes.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in SIGNATURES.items():
-            fn = getattr(handle, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        _lib = handle
-    return _lib
-
-
-def _message():
-    msg = lib().brv_rs_last_error()
-    return msg.decode() if msg else ''
-
-
-def call(name, *args):
-    """Call the ``brv_rs_*`` entry point ``name``; a non-zero status raises with the library's message."""
-    status = getattr(lib(), name)(*args)
-    if status:
-        raise RuntimeError(f'{name} failed with status {status}: {_message()}')
+# the brv_rs_* entry points of include/brever_resample.h
+_LIB = hip.Library('brever_resample.h', 'libbrever_resample.so', 'BRV_RESAMPLE_LIB_PATH',
+                   'The resampler has no CPU fallback.')
+LIB_PATH, HEADER_PATH, SIGNATURES = _LIB.path, _LIB.header_path, _LIB.signatures
+lib, call, last_error = _LIB.lib, _LIB.call, _LIB.last_error
 
 
 def max_length():
@@ -87,7 +48,7 @@ def fft_length(n, m):
     name when the library does not take the signal."""
     L = int(lib().brv_rs_fft_length(int(n), int(m)))
     if L < 0:
-        raise ValueError(f'cannot resample: {_message()} (brv_rs_max_length() = {max_length()})')
+        raise ValueError(f'cannot resample: {last_error()} (brv_rs_max_length() = {max_length()})')
     return L
 
 

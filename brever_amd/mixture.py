@@ -25,7 +25,6 @@ speech is padded before AND after spatialisation, so a target of L samples gives
 There is no CPU fallback: without ``libbrever_mix.so`` or a ROCm device the calls raise.
 """
 import collections
-import ctypes
 import os
 import time
 
@@ -39,85 +38,14 @@ COMPONENTS = ('mixture', 'foreground', 'background', 'speech', 'noise', 'early_s
 EN_CHUNK = 2048          # samples per partial energy sum (csrc/mix/mix.hip)
 MAX_PARTS = 512          # partitions per impulse response the LDS tile of the product holds
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get('BRV_MIX_LIB_PATH') or os.path.join(_HERE, 'csrc', 'libbrever_mix.so')
-HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'brever_mix.h')
-
-
-def _header_signatures():
-    if not os.path.exists(HEADER_PATH):
-        raise RuntimeError(f'{HEADER_PATH} is missing: the binding is derived from the C header')
-    with open(HEADER_PATH) as f:
-        return hip.parse_header(f.read())
-
-
-# name -> (restype, argtypes) of every brv_mix_* entry point, read from include/brever_mix.h
-SIGNATURES = _header_signatures()
-_lib = None
-
-
-def lib():
-    """Load ``libbrever_mix.so`` once; fail loudly if it is not built."""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError(f'{LIB_PATH} is missing: build it with `python -c "import __graft_entry__ as g; '
-                               'g.build()"` or `make -C brever_amd/csrc` (needs hipcc, targets gfx950). '
-                               'The mixture engine has no CPU fallback.')
-        handle = ctypes.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in SIGNATURES.items():
-            fn = getattr(handle, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        _lib = handle
-    return _lib
-
-
-def call(name, *args):
-    """Call the ``brv_mix_*`` entry point ``name``; a non-zero status raises with the library's message."""
-    status = getattr(lib(), name)(*args)
-    if status:
-        msg = lib().brv_mix_last_error()
-        raise RuntimeError(f'{name} failed with status {status}: {msg.decode() if msg else ""}')
-
-
-FX_LIB_PATH = os.environ.get('BRV_MIXFX_LIB_PATH') or os.path.join(_HERE, 'csrc', 'libbrever_mixfx.so')
-FX_HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'brever_mixfx.h')
-
-
-def _fx_header_signatures():
-    if not os.path.exists(FX_HEADER_PATH):
-        raise RuntimeError(f'{FX_HEADER_PATH} is missing: the binding is derived from the C header')
-    with open(FX_HEADER_PATH) as f:
-        return hip.parse_header(f.read())
-
-
-# name -> (restype, argtypes) of every brv_mixfx_* entry point, read from include/brever_mixfx.h
-FX_SIGNATURES = _fx_header_signatures()
-_fx_lib = None
-
-
-def fx_lib():
-    """Load ``libbrever_mixfx.so`` (colouring, LTAS matching, BRIR decay) once; fail loudly if it is not built."""
-    global _fx_lib
-    if _fx_lib is None:
-        if not os.path.exists(FX_LIB_PATH):
-            raise RuntimeError(f'{FX_LIB_PATH} is missing: build it with `python -c "import __graft_entry__ as g; '
-                               'g.build()"` or `make -C brever_amd/csrc` (needs hipcc, targets gfx950). '
-                               'The mixture engine has no CPU fallback.')
-        handle = ctypes.CDLL(FX_LIB_PATH)
-        for name, (restype, argtypes) in FX_SIGNATURES.items():
-            fn = getattr(handle, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        _fx_lib = handle
-    return _fx_lib
-
-
-def fx_call(name, *args):
-    """Call the ``brv_mixfx_*`` entry point ``name``; a non-zero status raises with the library's message."""
-    status = getattr(fx_lib(), name)(*args)
-    if status:
-        msg = fx_lib().brv_mixfx_last_error()
-        raise RuntimeError(f'{name} failed with status {status}: {msg.decode() if msg else ""}')
+# the brv_mix_* entry points of include/brever_mix.h
+_LIB = hip.Library('brever_mix.h', 'libbrever_mix.so', 'BRV_MIX_LIB_PATH', 'The mixture engine has no CPU fallback.')
+LIB_PATH, HEADER_PATH, SIGNATURES, lib, call = _LIB.path, _LIB.header_path, _LIB.signatures, _LIB.lib, _LIB.call
+# the brv_mixfx_* entry points of include/brever_mixfx.h: colouring, LTAS matching, BRIR decay
+_FX = hip.Library('brever_mixfx.h', 'libbrever_mixfx.so', 'BRV_MIXFX_LIB_PATH',
+                  'The mixture engine has no CPU fallback.')
+FX_LIB_PATH, FX_HEADER_PATH, FX_SIGNATURES = _FX.path, _FX.header_path, _FX.signatures
+fx_lib, fx_call = _FX.lib, _FX.call
 
 
 _tables = {}

@@ -11,16 +11,9 @@ Only the estimate gets a gradient. Every reduction has a fixed order, so values 
 and a row gives the same bits alone as in a batch. ``lengths`` stays on the device; nothing here synchronises. There
 is no CPU fallback: without the library or a ROCm device the calls raise.
 """
-import ctypes
-import os
-
 import torch
 
 from . import hip
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get('BRV_SDR_LIB_PATH') or os.path.join(_HERE, 'csrc', 'libbrever_sdr.so')
-HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'brever_sdr.h')
 
 MAX_FILTER_LENGTH = 512
 # bits of the per-row flags word (include/brever_sdr.h)
@@ -28,40 +21,11 @@ NO_REFERENCE, NO_ESTIMATE, BAD_PIVOT, NUMERATOR_FLOOR, DENOMINATOR_FLOOR = 1, 2,
 DEGENERATE = NO_REFERENCE | NO_ESTIMATE | BAD_PIVOT
 
 
-def _header_signatures():
-    if not os.path.exists(HEADER_PATH):
-        raise RuntimeError(f'{HEADER_PATH} is missing: the binding is derived from the C header')
-    with open(HEADER_PATH) as f:
-        return hip.parse_header(f.read())
-
-
-# name -> (restype, argtypes) of every brv_sdr_* entry point, read from include/brever_sdr.h
-SIGNATURES = _header_signatures()
-_lib = None
-
-
-def lib():
-    """Load ``libbrever_sdr.so`` once; fail loudly if it is not built."""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError(f'{LIB_PATH} is missing: build it with `python -c "import __graft_entry__ as g; '
-                               'g.build()"` or `make -C brever_amd/csrc` (needs hipcc, targets gfx950). '
-                               'The sdr metric and criterion have no CPU fallback.')
-        handle = ctypes.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in SIGNATURES.items():
-            fn = getattr(handle, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        _lib = handle
-    return _lib
-
-
-def call(name, *args):
-    """Call the ``brv_sdr_*`` entry point ``name``; a non-zero status raises with the library's message."""
-    status = getattr(lib(), name)(*args)
-    if status:
-        msg = lib().brv_sdr_last_error()
-        raise RuntimeError(f'{name} failed with status {status}: {msg.decode() if msg else ""}')
+# the brv_sdr_* entry points of include/brever_sdr.h
+_LIB = hip.Library('brever_sdr.h', 'libbrever_sdr.so', 'BRV_SDR_LIB_PATH',
+                   'The sdr metric and criterion have no CPU fallback.')
+LIB_PATH, HEADER_PATH, SIGNATURES = _LIB.path, _LIB.header_path, _LIB.signatures
+lib, call, last_error = _LIB.lib, _LIB.call, _LIB.last_error
 
 
 def check_options(filter_length, load_diag):
@@ -85,7 +49,7 @@ def forward(x, y, lengths, filter_length=512, load_diag=0.0):
     dev = x.device
     nbytes = lib().brv_sdr_workspace_bytes(R, W, filter_length)
     if nbytes < 0:
-        raise RuntimeError(f'brv_sdr_workspace_bytes: {lib().brv_sdr_last_error().decode()}')
+        raise RuntimeError(f'brv_sdr_workspace_bytes: {last_error()}')
     f64 = dict(dtype=torch.float64, device=dev)
     ws = torch.empty(nbytes//8, **f64)
     value, q, e = torch.empty(R, **f64), torch.empty(R, **f64), torch.empty(R, **f64)

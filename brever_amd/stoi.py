@@ -17,18 +17,12 @@ Only the estimate gets a gradient; frame selection and everything computed from 
 stage is a gather in a fixed order, so a gradient is bitwise repeatable. ``lengths`` stays on the device; nothing
 here synchronises. There is no CPU fallback: without the libraries or a ROCm device the calls raise.
 """
-import ctypes
 import math
-import os
 
 import numpy as np
 import torch
 
 from . import hip
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get('BRV_STOI_LOSS_LIB_PATH') or os.path.join(_HERE, 'csrc', 'libbrever_stoi_loss.so')
-HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'brever_stoi_loss.h')
 
 FS, NFFT, FRAME, BANDS, MINFREQ, SEGMENT = 10000, 512, 256, 15, 150, 30
 HOP = FRAME//2
@@ -39,40 +33,10 @@ CLIP = 10.0**(15.0/20.0)
 _GEMM_SPLIT_FROM = 16*32
 
 
-def _header_signatures():
-    if not os.path.exists(HEADER_PATH):
-        raise RuntimeError(f'{HEADER_PATH} is missing: the binding is derived from the C header')
-    with open(HEADER_PATH) as f:
-        return hip.parse_header(f.read())
-
-
-# name -> (restype, argtypes) of every brv_sl_* entry point, read from include/brever_stoi_loss.h
-SIGNATURES = _header_signatures()
-_lib = None
-
-
-def lib():
-    """Load ``libbrever_stoi_loss.so`` once; fail loudly if it is not built."""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError(f'{LIB_PATH} is missing: build it with `python -c "import __graft_entry__ as g; '
-                               'g.build()"` or `make -C brever_amd/csrc` (needs hipcc, targets gfx950). '
-                               'The STOI / ESTOI criteria have no CPU fallback.')
-        handle = ctypes.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in SIGNATURES.items():
-            fn = getattr(handle, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        _lib = handle
-    return _lib
-
-
-def call(name, *args):
-    """Call the ``brv_sl_*`` entry point ``name``; a non-zero status raises with the library's message."""
-    status = getattr(lib(), name)(*args)
-    if status:
-        msg = lib().brv_sl_last_error()
-        raise RuntimeError(f'{name} failed with status {status}: {msg.decode() if msg else ""}')
+# the brv_sl_* entry points of include/brever_stoi_loss.h
+_LIB = hip.Library('brever_stoi_loss.h', 'libbrever_stoi_loss.so', 'BRV_STOI_LOSS_LIB_PATH',
+                   'The STOI / ESTOI criteria have no CPU fallback.')
+LIB_PATH, HEADER_PATH, SIGNATURES, lib, call = _LIB.path, _LIB.header_path, _LIB.signatures, _LIB.lib, _LIB.call
 
 
 _cache = {}

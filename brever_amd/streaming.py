@@ -189,7 +189,7 @@ class DCCRNStreamer(_StreamSlots):
         try:
             nbytes = hip.query('brv_dccrn_stream_state_bytes', ctypes.byref(self._geometry(model)))
         except RuntimeError:
-            raise ValueError(f'this DCCRN cannot stream: {hip.lib().brv_last_error().decode()}') from None
+            raise ValueError(f'this DCCRN cannot stream: {hip.last_error()}') from None
         hip.require_device(model.flat_params())
         self.model = model
         self.use_amp = bool(use_amp)

@@ -32,8 +32,8 @@ import os, sys
 sys.path.insert(0, {ROOT!r})
 os.environ['BRV_CTN_STREAMS'] = '1'
 os.environ['BRV_BWD_FUSE'] = {fuse!r}
+os.environ['BRV_LIB_PATH'] = {lib!r}
 import brever_amd.hip as hip
-hip.LIB_PATH = {lib!r}
 import torch
 from brever_amd.models import ConvTasNet
 torch.manual_seed(0)
