@@ -106,7 +106,7 @@ __global__ __launch_bounds__(256) void pack_brirs_kernel(const float* __restrict
 // of it depends on the batch (the LDS strides do, the arithmetic does not).
 constexpr int MAC_BINS = 4;
 constexpr int MAC_CHUNK = 256;
-constexpr int MAC_MAX_PARTS = 512;
+constexpr int MAC_MAX_PARTS = BRV_MIX_MAX_PARTS;
 
 struct MacParams {
   const float2* x; const float2* h; float2* y; const int* slots; const int* jobs;
@@ -205,7 +205,8 @@ __global__ __launch_bounds__(256) void partition_mac_kernel(const MacParams p) {
 }
 
 // ---- energies ---------------------------------------------------------------------------------------------------
-constexpr int EN_CHUNK = 2048;       // samples per workgroup: the chunking depends on a mixture's own length only
+// samples per workgroup: the chunking depends on a mixture's own length only
+constexpr int EN_CHUNK = BRV_MIX_ENERGY_CHUNK;
 constexpr int EN_SUMS = 40;
 
 __global__ __launch_bounds__(256) void energies_kernel(const float* __restrict__ y, const int* __restrict__ mix,

@@ -277,7 +277,7 @@ int64_t brv_rs_fft_length(int64_t n, int64_t m) {
 int brv_rs_chirp_spectra(double* slab, const int64_t* desc, const double* tw, int64_t nslots, int64_t fft_len,
                          int64_t count, brv_stream_t stream) {
   BRV_REFUSE(!slab || !desc || !tw, "null slab, desc or tw");
-  BRV_REFUSE(nslots < 1 || count < 1 || count > 32768, "requires nslots >= 1 and 1 <= count <= 32768");
+  BRV_REFUSE(nslots < 1 || count < 1 || count > BRV_RS_MAX_COLUMNS, "requires nslots >= 1 and 1 <= count <= 32768");
   if (int e = check_fft_len(fft_len)) return e;
   hipStream_t st = (hipStream_t)stream;
   const long long* d = (const long long*)desc;
@@ -291,7 +291,7 @@ int brv_rs_analysis(const void* x, const int64_t* desc, const double* slab, cons
                     int64_t x_len, int64_t x_float32, int64_t nslots, int64_t fft_len, int64_t ncols,
                     brv_stream_t stream) {
   BRV_REFUSE(!x || !desc || !slab || !tw || !work, "null x, desc, slab, tw or work");
-  BRV_REFUSE(x_len < 1 || x_float32 < 0 || nslots < 1 || ncols < 1 || ncols > 32768,
+  BRV_REFUSE(x_len < 1 || x_float32 < 0 || nslots < 1 || ncols < 1 || ncols > BRV_RS_MAX_COLUMNS,
              "requires x_len >= 1, x_float32 >= 0, nslots >= 1 and 1 <= ncols <= 32768");
   if (int e = check_fft_len(fft_len)) return e;
   hipStream_t st = (hipStream_t)stream;
@@ -313,7 +313,7 @@ int brv_rs_synthesis(double* work, const int64_t* desc, const double* slab, cons
                      int64_t out_len, int64_t out_float32, int64_t nslots, int64_t fft_len, int64_t ncols,
                      brv_stream_t stream) {
   BRV_REFUSE(!work || !desc || !slab || !tw || !out, "null work, desc, slab, tw or out");
-  BRV_REFUSE(out_len < 1 || out_float32 < 0 || nslots < 1 || ncols < 1 || ncols > 32768,
+  BRV_REFUSE(out_len < 1 || out_float32 < 0 || nslots < 1 || ncols < 1 || ncols > BRV_RS_MAX_COLUMNS,
              "requires out_len >= 1, out_float32 >= 0, nslots >= 1 and 1 <= ncols <= 32768");
   if (int e = check_fft_len(fft_len)) return e;
   hipStream_t st = (hipStream_t)stream;

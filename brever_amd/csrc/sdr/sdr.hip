@@ -27,8 +27,8 @@
 
 namespace {
 
-constexpr int kMaxL = 512;                     // filter taps; 64 lanes x 8 lags
-constexpr int kChunk = 2048;                   // samples per correlation workgroup
+constexpr int kMaxL = BRV_SDR_MAX_FILTER_LENGTH;   // filter taps; 64 lanes x 8 lags
+constexpr int kChunk = BRV_SDR_CHUNK;          // samples per correlation workgroup
 constexpr int kParts = 4;                      // waves of a correlation workgroup: quarters of the chunk
 constexpr int kPartLen = kChunk/kParts;
 constexpr int kStage = kChunk + kMaxL;         // the chunk and its halo
@@ -37,7 +37,8 @@ constexpr int kBwdHalo = kMaxL + 8;            // samples staged in front of the
 constexpr double kEps = 2.220446049250313e-16; // 2^-52
 constexpr double kTenOverLn10 = 4.342944819032518;
 constexpr long long kMaxRows = 65535;          // rows ride on gridDim.y
-constexpr int kNoRef = 1, kNoEst = 2, kPivot = 4, kNumFloor = 8, kDenFloor = 16;
+constexpr int kNoRef = BRV_SDR_FLAG_NO_REFERENCE, kNoEst = BRV_SDR_FLAG_NO_ESTIMATE, kPivot = BRV_SDR_FLAG_BAD_PIVOT,
+              kNumFloor = BRV_SDR_FLAG_NUMERATOR_FLOOR, kDenFloor = BRV_SDR_FLAG_DENOMINATOR_FLOOR;
 
 __device__ __forceinline__ long long row_length(const long long* lengths, int row, long long stride) {
   const long long n = lengths[row];

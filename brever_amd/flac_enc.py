@@ -16,16 +16,16 @@ import torch
 
 from . import hip
 
-ROW_MESSAGES = {1: 'a non-finite sample', 2: 'a PCM sample outside the range of the bit depth',
-                4: 'a length outside 1 ... the padded length', 8: 'a frame did not fit its image'}
-MAX_ROWS, MAX_LPC_ORDER = 65535, 32
-
-
 # the brv_flacenc_* entry points of include/brever_flacenc.h
 _LIB = hip.Library('brever_flacenc.h', 'libbrever_flacenc.so', 'BRV_FLACENC_LIB_PATH',
                    'The GPU FLAC encoder has no fallback.')
 LIB_PATH, HEADER_PATH, SIGNATURES = _LIB.path, _LIB.header_path, _LIB.signatures
 lib, call, last_error = _LIB.lib, _LIB.call, _LIB.last_error
+# the header's BRV_FLACENC_* constants: the bits of a row's status, the limits of a call
+ROW_MESSAGES = {_LIB.constants['BRV_FLACENC_ROW_' + name]: text for name, text in (
+    ('NONFINITE', 'a non-finite sample'), ('RANGE', 'a PCM sample outside the range of the bit depth'),
+    ('LENGTH', 'a length outside 1 ... the padded length'), ('INTERNAL', 'a frame did not fit its image'))}
+MAX_ROWS, MAX_LPC_ORDER = _LIB.constants['BRV_FLACENC_MAX_ROWS'], _LIB.constants['BRV_FLACENC_MAX_LPC_ORDER']
 
 
 def query(name, *args):

@@ -19,10 +19,6 @@ import torch
 
 from . import hip
 
-INFO_WORDS, FRAME_WORDS, JOB_WORDS = 8, 8, 12
-NOT_TAKEN, NOT_FLAC, BAD_HEADER, BAD_CRC16, BAD_NUMBER, TRUNCATED = -2, -10, -60, -61, -62, -63
-JOB_MESSAGES = {1: 'job fields outside the extents of the call', 2: 'reserved or invalid field in a subframe',
-                3: "the frame's bits ran out", 4: 'the frame does not end where the index says'}
 # in place of an ``index`` result: the index declined the member (``NOT_TAKEN``), the host decoder reads it
 HOST_MEMBER = 'host'
 INFO_FIELDS = ('sample_rate', 'channels', 'bits_per_sample', 'total_samples', 'min_block', 'max_block',
@@ -33,6 +29,15 @@ INFO_FIELDS = ('sample_rate', 'channels', 'bits_per_sample', 'total_samples', 'm
 _LIB = hip.Library('brever_flac.h', 'libbrever_flac.so', 'BRV_FLAC_LIB_PATH', 'The GPU FLAC decoder has no fallback.')
 LIB_PATH, HEADER_PATH, SIGNATURES = _LIB.path, _LIB.header_path, _LIB.signatures
 lib, call, last_error = _LIB.lib, _LIB.call, _LIB.last_error
+# the header's BRV_FLACDEC_* constants: table widths in words, index statuses, job statuses
+INFO_WORDS, FRAME_WORDS, JOB_WORDS, NOT_TAKEN, NOT_FLAC, BAD_HEADER, BAD_CRC16, BAD_NUMBER, TRUNCATED = (
+    _LIB.constants['BRV_FLACDEC_' + name] for name in (
+        'INFO_WORDS', 'FRAME_WORDS', 'JOB_WORDS', 'NOT_TAKEN', 'NOT_FLAC', 'BAD_HEADER', 'BAD_CRC16', 'BAD_NUMBER',
+        'TRUNCATED'))
+JOB_MESSAGES = {_LIB.constants['BRV_FLACDEC_JOB_' + name]: text for name, text in (
+    ('BAD_FIELDS', 'job fields outside the extents of the call'),
+    ('RESERVED', 'reserved or invalid field in a subframe'), ('OVERRUN', "the frame's bits ran out"),
+    ('LENGTH', 'the frame does not end where the index says'))}
 
 
 class FlacIndexError(ValueError):

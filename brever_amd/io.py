@@ -21,7 +21,6 @@ import torch
 
 from . import hip
 
-MAX_COLUMNS = 32768                    # columns per launch (the library's bound)
 WORK_BYTES = 2 << 30                   # scratch per launch group: columns of one L are chunked to fit
 
 # the brv_rs_* entry points of include/brever_resample.h
@@ -29,6 +28,7 @@ _LIB = hip.Library('brever_resample.h', 'libbrever_resample.so', 'BRV_RESAMPLE_L
                    'The resampler has no CPU fallback.')
 LIB_PATH, HEADER_PATH, SIGNATURES = _LIB.path, _LIB.header_path, _LIB.signatures
 lib, call, last_error = _LIB.lib, _LIB.call, _LIB.last_error
+MAX_COLUMNS = _LIB.constants['BRV_RS_MAX_COLUMNS']      # columns per launch
 
 
 def max_length():

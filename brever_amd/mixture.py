@@ -35,12 +35,12 @@ from . import hip
 
 COMPONENTS = ('mixture', 'foreground', 'background', 'speech', 'noise', 'early_speech', 'late_speech',
               'dir_noise', 'diffuse')
-EN_CHUNK = 2048          # samples per partial energy sum (csrc/mix/mix.hip)
-MAX_PARTS = 512          # partitions per impulse response the LDS tile of the product holds
 
 # the brv_mix_* entry points of include/brever_mix.h
 _LIB = hip.Library('brever_mix.h', 'libbrever_mix.so', 'BRV_MIX_LIB_PATH', 'The mixture engine has no CPU fallback.')
 LIB_PATH, HEADER_PATH, SIGNATURES, lib, call = _LIB.path, _LIB.header_path, _LIB.signatures, _LIB.lib, _LIB.call
+EN_CHUNK = _LIB.constants['BRV_MIX_ENERGY_CHUNK']       # samples per partial energy sum
+MAX_PARTS = _LIB.constants['BRV_MIX_MAX_PARTS']         # partitions per impulse response the product's LDS tile holds
 # the brv_mixfx_* entry points of include/brever_mixfx.h: colouring, LTAS matching, BRIR decay
 _FX = hip.Library('brever_mixfx.h', 'libbrever_mixfx.so', 'BRV_MIXFX_LIB_PATH',
                   'The mixture engine has no CPU fallback.')

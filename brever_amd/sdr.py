@@ -15,17 +15,17 @@ import torch
 
 from . import hip
 
-MAX_FILTER_LENGTH = 512
-# bits of the per-row flags word (include/brever_sdr.h)
-NO_REFERENCE, NO_ESTIMATE, BAD_PIVOT, NUMERATOR_FLOOR, DENOMINATOR_FLOOR = 1, 2, 4, 8, 16
-DEGENERATE = NO_REFERENCE | NO_ESTIMATE | BAD_PIVOT
-
-
 # the brv_sdr_* entry points of include/brever_sdr.h
 _LIB = hip.Library('brever_sdr.h', 'libbrever_sdr.so', 'BRV_SDR_LIB_PATH',
                    'The sdr metric and criterion have no CPU fallback.')
 LIB_PATH, HEADER_PATH, SIGNATURES = _LIB.path, _LIB.header_path, _LIB.signatures
 lib, call, last_error = _LIB.lib, _LIB.call, _LIB.last_error
+MAX_FILTER_LENGTH = _LIB.constants['BRV_SDR_MAX_FILTER_LENGTH']
+# bits of the per-row flags word
+NO_REFERENCE, NO_ESTIMATE, BAD_PIVOT, NUMERATOR_FLOOR, DENOMINATOR_FLOOR = (
+    _LIB.constants['BRV_SDR_FLAG_' + name] for name in (
+        'NO_REFERENCE', 'NO_ESTIMATE', 'BAD_PIVOT', 'NUMERATOR_FLOOR', 'DENOMINATOR_FLOOR'))
+DEGENERATE = NO_REFERENCE | NO_ESTIMATE | BAD_PIVOT
 
 
 def check_options(filter_length, load_diag):

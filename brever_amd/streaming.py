@@ -25,11 +25,64 @@ from . import hip
 
 
 class _StreamSlots:
-    """Slot bookkeeping shared by the streamers: ``max_streams`` slots of ``state_bytes`` in one HBM buffer."""
+    """What the streamers share: ``max_streams`` slots of ``state_bytes`` in one HBM buffer, the grow-only workspace,
+    the checks of a chunk, a rest and the model's device and, for a streamer that asks for it, how many hops each
+    slot received and whether it was flushed. A streamer gives ``_launch_reset(t, n)``."""
+
+    def __init__(self, max_streams):
+        if int(max_streams) < 1:
+            raise ValueError(f'max_streams must be >= 1, got {max_streams}')
+        self.max_streams = int(max_streams)
+
+    def _allocate(self, state_bytes, device, track_end=False):
+        self.state_bytes = int(state_bytes)
+        self._state = torch.zeros(self.max_streams*self.state_bytes, dtype=torch.uint8, device=device)
+        self._open = [False]*self.max_streams
+        self._hops = [0]*self.max_streams if track_end else None        # hops received per slot
+        self._ended = [False]*self.max_streams if track_end else None   # flushed: reset or close it next
+        self._ws = self._ids_cache = None
 
     @property
     def device(self):
         return self._state.device
+
+    def _reset(self, ids):
+        self._launch_reset(self._ids_tensor(ids), len(ids))
+        if self._ended is not None:
+            for i in ids:
+                self._hops[i] = 0
+                self._ended[i] = False
+
+    def _workspace(self, nbytes):
+        if self._ws is None or self._ws.numel() < nbytes:
+            self._ws = None
+            self._ws = torch.empty(int(nbytes), dtype=torch.uint8, device=self.device)
+        return self._ws
+
+    def _whole_hops(self, L):
+        if L == 0 or L % self.hop:
+            raise ValueError(f'a chunk must be a positive multiple of hop = {self.hop} samples, got {L}')
+        return L//self.hop
+
+    def _rest(self, rest, n):
+        """``(rest, r)`` of a flush: the last ``r < hop`` samples as ``_input`` shapes them, or ``(None, 0)``."""
+        if rest is None:
+            return None, 0
+        rest = self._input(rest, n, 'rest')
+        if rest.shape[-1] >= self.hop:
+            raise ValueError(f'rest must be shorter than hop = {self.hop} samples, got {rest.shape[-1]}; '
+                             'process the whole hops first')
+        return rest, rest.shape[-1]
+
+    def _check_device(self, t):
+        hip.require_device(t)
+        if t.device != self.device:
+            raise RuntimeError(f'the model moved to {t.device}; the streams live on {self.device}')
+
+    def _check_live(self, ids, already=''):
+        for i in ids:
+            if self._ended[i]:
+                raise ValueError(f'stream {i} was flushed{already}; reset or close it first')
 
     # ---- slots ----------------------------------------------------------------------------------
     def open(self, n=1):
@@ -74,7 +127,8 @@ class _StreamSlots:
             self._ids_cache = (key, torch.tensor(ids, dtype=torch.int32).to(self.device))
         return self._ids_cache[1]
 
-    def _mono(self, x, n):
+    def _input(self, x, n, what='input'):
+        """The mono (n, samples) fp32 input of a call (the FFNN streamer keeps the channels instead)."""
         hip.require_device(x)
         if x.dim() == 3:
             x = x.mean(axis=-2)          # channels averaged, as enhance does
@@ -99,25 +153,17 @@ class ConvTasNetStreamer(_StreamSlots):
                              'non-causal model needs the whole signal')
         if model.cfg.filter_length % 2:
             raise ValueError('streaming needs an even filter_length (hop = filter_length // 2)')
-        if int(max_streams) < 1:
-            raise ValueError(f'max_streams must be >= 1, got {max_streams}')
+        super().__init__(max_streams)
         hip.require_device(model.flat_params())
         self.model = model
         self.use_amp = bool(use_amp)
-        self.max_streams = int(max_streams)
         self.hop = model.cfg.filter_length//2
         self.lag = self.hop               # the output lags the input by one hop
         self.sources = model.output_sources
-        self.state_bytes = int(hip.query('brv_ctn_stream_state_bytes', model._cfg_ptr()))
-        self._state = torch.zeros(self.max_streams*self.state_bytes, dtype=torch.uint8,
-                                  device=model.flat_params().device)
-        self._open = [False]*self.max_streams
-        self._ws = None
-        self._ids_cache = None
+        self._allocate(hip.query('brv_ctn_stream_state_bytes', model._cfg_ptr()), model.flat_params().device)
 
-    def _reset(self, ids):
-        t = self._ids_tensor(ids)
-        hip.call('brv_ctn_stream_reset', self.model._cfg_ptr(), self._state, t, len(ids), hip.stream())
+    def _launch_reset(self, t, n):
+        hip.call('brv_ctn_stream_reset', self.model._cfg_ptr(), self._state, t, n, hip.stream())
 
     # ---- compute --------------------------------------------------------------------------------
     def process(self, x, ids):
@@ -125,26 +171,19 @@ class ConvTasNetStreamer(_StreamSlots):
         returns ``(n, sources, k hop)``, one hop behind the input."""
         ids = self._check_ids(ids)
         n = len(ids)
-        x = self._mono(x, n)
+        x = self._input(x, n)
         L = x.shape[1]
-        if L == 0 or L % self.hop:
-            raise ValueError(f'a chunk must be a positive multiple of hop = {self.hop} samples, got {L}')
-        hops = L//self.hop
+        hops = self._whole_hops(L)
         model = self.model
         model._check_layout()
         flat = model.flat_params()
-        hip.require_device(flat)
-        if flat.device != self.device:
-            raise RuntimeError(f'the model moved to {flat.device}; the streams live on {self.device}')
+        self._check_device(flat)
         cfg = model._cfg_ptr()
-        nbytes = hip.query('brv_ctn_stream_workspace_bytes', cfg, n, hops, int(self.use_amp))
-        if self._ws is None or self._ws.numel() < nbytes:
-            self._ws = None
-            self._ws = torch.empty(int(nbytes), dtype=torch.uint8, device=self.device)
+        ws = self._workspace(hip.query('brv_ctn_stream_workspace_bytes', cfg, n, hops, int(self.use_amp)))
         y = torch.empty(n, self.sources, L, dtype=torch.float32, device=self.device)
         t = self._ids_tensor(ids)
-        hip.call('brv_ctn_stream_step', cfg, flat, self._state, t, n, x, hops, y, int(self.use_amp), self._ws,
-                 self._ws.numel(), None, hip.stream())
+        hip.call('brv_ctn_stream_step', cfg, flat, self._state, t, n, x, hops, y, int(self.use_amp), ws, ws.numel(),
+                 None, hip.stream())
         return y
 
     def flush(self, ids, rest=None):
@@ -154,13 +193,7 @@ class ConvTasNetStreamer(_StreamSlots):
         ids = self._check_ids(ids)
         n = len(ids)
         out = []
-        r = 0
-        if rest is not None:
-            rest = self._mono(rest, n)
-            r = rest.shape[1]
-            if r >= self.hop:
-                raise ValueError(f'rest must be shorter than hop = {self.hop} samples, got {r}; '
-                                 'process the whole hops first')
+        rest, r = self._rest(rest, n)
         if r:
             x = torch.zeros(n, self.hop, dtype=torch.float32, device=self.device)
             x[:, :r] = rest
@@ -170,6 +203,16 @@ class ConvTasNetStreamer(_StreamSlots):
         hip.call('brv_ctn_stream_tail', self.model._cfg_ptr(), self._state, t, n, tail, hip.stream())
         out.append(tail[..., :r] if r else tail)
         return torch.cat(out, dim=-1)
+
+
+def _check_stft(stft, name):
+    """The STFT settings the DCCRN and FFNN streaming kernels take; ``ValueError`` in the streamer's own words."""
+    if stft.frame_length % (2*stft.hop_length):
+        raise ValueError(f'{name} streaming needs frame_length to be a multiple of 2 hop (the centre padding '
+                         f'in whole hops), got {stft.frame_length} and hop {stft.hop_length}')
+    if not (stft.n_fft == stft.frame_length and stft.center and stft.pad_mode == 'constant' and stft.normalized
+            and stft.onesided and stft.compression_factor == 1 and stft.scale_factor == 1):
+        raise ValueError(f'{name} streaming needs the STFT settings {name} builds')
 
 
 class DCCRNStreamer(_StreamSlots):
@@ -184,8 +227,7 @@ class DCCRNStreamer(_StreamSlots):
 
     def __init__(self, model, max_streams=64, use_amp=False):
         self.lag = self.lag_for(model)           # (validates the model)
-        if int(max_streams) < 1:
-            raise ValueError(f'max_streams must be >= 1, got {max_streams}')
+        super().__init__(max_streams)
         try:
             nbytes = hip.query('brv_dccrn_stream_state_bytes', ctypes.byref(self._geometry(model)))
         except RuntimeError:
@@ -193,16 +235,8 @@ class DCCRNStreamer(_StreamSlots):
         hip.require_device(model.flat_params())
         self.model = model
         self.use_amp = bool(use_amp)
-        self.max_streams = int(max_streams)
         self.hop = model.stft.hop_length
-        self.state_bytes = int(nbytes)
-        self._state = torch.zeros(self.max_streams*self.state_bytes, dtype=torch.uint8,
-                                  device=model.flat_params().device)
-        self._open = [False]*self.max_streams
-        self._hops = [0]*self.max_streams          # hops received per slot
-        self._ended = [False]*self.max_streams     # flushed: reset or close before the next process
-        self._ws = None
-        self._ids_cache = None
+        self._allocate(nbytes, model.flat_params().device, track_end=True)
         self._offsets = None
 
     # ---- configuration --------------------------------------------------------------------------
@@ -220,12 +254,7 @@ class DCCRNStreamer(_StreamSlots):
         stft = model.stft
         if stft.n_fft != stft.frame_length:
             raise ValueError(f'DCCRN streaming needs n_fft == frame_length, got {stft.n_fft} and {stft.frame_length}')
-        if stft.frame_length % (2*stft.hop_length):
-            raise ValueError('DCCRN streaming needs frame_length to be a multiple of 2 hop (the centre padding '
-                             f'in whole hops), got {stft.frame_length} and hop {stft.hop_length}')
-        if not (stft.center and stft.pad_mode == 'constant' and stft.normalized and stft.onesided
-                and stft.compression_factor == 1 and stft.scale_factor == 1):
-            raise ValueError('DCCRN streaming needs the STFT settings DCCRN builds')
+        _check_stft(stft, 'DCCRN')
         net = model.mask_net
         for blk in list(net.encoder) + list(net.decoder):
             if blk.norm is not None and (not getattr(blk.norm, 'track_running_stats', True)
@@ -293,28 +322,19 @@ class DCCRNStreamer(_StreamSlots):
                 raise RuntimeError('the running buffers must be contiguous fp32 tensors')
         return cfg
 
-    def _reset(self, ids):
-        t = self._ids_tensor(ids)
+    def _launch_reset(self, t, n):
         cfg = self._geometry(self.model)
-        hip.call('brv_dccrn_stream_reset', ctypes.byref(cfg), self._state, t, len(ids), hip.stream())
-        for i in ids:
-            self._hops[i] = 0
-            self._ended[i] = False
+        hip.call('brv_dccrn_stream_reset', ctypes.byref(cfg), self._state, t, n, hip.stream())
 
     def _call(self, ids, n, hops):
-        """What every launch of a call needs: params, tables, config, workspace."""
+        """What every launch of a call needs: config, params, tables, the ids on the device (and the workspace)."""
         model = self.model
         flat = model.flat_params()
-        hip.require_device(flat)
-        if flat.device != self.device:
-            raise RuntimeError(f'the model moved to {flat.device}; the streams live on {self.device}')
+        self._check_device(flat)
         cfg = self._config()
-        nbytes = hip.query('brv_dccrn_stream_workspace_bytes', ctypes.byref(cfg), n, hops, int(self.use_amp))
-        if self._ws is None or self._ws.numel() < nbytes:
-            self._ws = None
-            self._ws = torch.empty(int(nbytes), dtype=torch.uint8, device=self.device)
+        self._workspace(hip.query('brv_dccrn_stream_workspace_bytes', ctypes.byref(cfg), n, hops, int(self.use_amp)))
         tb = model.stft._tables(self.device)
-        return cfg, flat, tb
+        return cfg, flat, tb, self._ids_tensor(ids)
 
     # ---- compute --------------------------------------------------------------------------------
     def process(self, x, ids):
@@ -322,17 +342,12 @@ class DCCRNStreamer(_StreamSlots):
         returns ``(n, k hop)``, ``lag`` samples behind the input."""
         ids = self._check_ids(ids)
         n = len(ids)
-        x = self._mono(x, n)
+        x = self._input(x, n)
         L = x.shape[1]
-        if L == 0 or L % self.hop:
-            raise ValueError(f'a chunk must be a positive multiple of hop = {self.hop} samples, got {L}')
-        for i in ids:
-            if self._ended[i]:
-                raise ValueError(f'stream {i} was flushed; reset or close it first')
-        hops = L//self.hop
-        cfg, flat, tb = self._call(ids, n, hops)
+        hops = self._whole_hops(L)
+        self._check_live(ids)
+        cfg, flat, tb, t = self._call(ids, n, hops)
         y = torch.empty(n, L, dtype=torch.float32, device=self.device)
-        t = self._ids_tensor(ids)
         hip.call('brv_dccrn_stream_step', ctypes.byref(cfg), flat, tb['window'], tb['basis'], tb['synthesis'],
                  self._state, t, n, x, hops, y, int(self.use_amp), self._ws, self._ws.numel(), None, hip.stream())
         for i in ids:
@@ -345,28 +360,20 @@ class DCCRNStreamer(_StreamSlots):
         output samples still owed. Reset or close the streams afterwards."""
         ids = self._check_ids(ids)
         n = len(ids)
-        r = 0
-        if rest is not None:
-            rest = self._mono(rest, n)
-            r = rest.shape[1]
-            if r >= self.hop:
-                raise ValueError(f'rest must be shorter than hop = {self.hop} samples, got {r}; '
-                                 'process the whole hops first')
+        rest, r = self._rest(rest, n)
         stft = self.model.stft
         (_, kt), _, _, _ = self.model.mask_net.geom
         need = 1 + len(self.model.mask_net.encoder)*(kt - 1)     # STFT frames the offline model needs
         for i in ids:
-            if self._ended[i]:
-                raise ValueError(f'stream {i} was flushed already; reset or close it first')
+            self._check_live([i], ' already')
             length = self._hops[i]*self.hop + r
             frames = stft.frame_count(length) + stft.n_fft//self.hop
             if frames < need:
                 raise ValueError(f'stream {i} has {length} samples: DCCRN needs at least {need} STFT frames '
                                  f'({frames} here)')
         hops = self.lag//self.hop + (1 if r else 0)
-        cfg, flat, tb = self._call(ids, n, hops)
+        cfg, flat, tb, t = self._call(ids, n, hops)
         y = torch.empty(n, self.lag + r, dtype=torch.float32, device=self.device)
-        t = self._ids_tensor(ids)
         hip.call('brv_dccrn_stream_tail', ctypes.byref(cfg), flat, tb['window'], tb['basis'], tb['synthesis'],
                  self._state, t, n, rest if r else None, r, y, int(self.use_amp), self._ws, self._ws.numel(), None,
                  hip.stream())
@@ -386,8 +393,7 @@ class FFNNStreamer(_StreamSlots):
     def __init__(self, model, max_streams=64, channels=2):
         from . import ffnn_stream as ffs
         self.lag = self.lag_for(model)           # (validates the model)
-        if int(max_streams) < 1:
-            raise ValueError(f'max_streams must be >= 1, got {max_streams}')
+        super().__init__(max_streams)
         if int(channels) < 1:
             raise ValueError(f'channels must be >= 1, got {channels}')
         self._ffs = ffs
@@ -397,17 +403,9 @@ class FFNNStreamer(_StreamSlots):
             nbytes = ffs.query('brv_ffs_state_bytes', ctypes.byref(self._geometry(model, self.channels)))
         except RuntimeError:
             raise ValueError(f'this FFNN cannot stream: {ffs.last_error()}') from None
-        device = next(model.parameters()).device
         hip.require_device(next(model.parameters()))
-        self.max_streams = int(max_streams)
         self.hop = model.stft.hop_length
-        self.state_bytes = int(nbytes)
-        self._state = torch.zeros(self.max_streams*self.state_bytes, dtype=torch.uint8, device=device)
-        self._open = [False]*self.max_streams
-        self._hops = [0]*self.max_streams          # hops received per slot
-        self._ended = [False]*self.max_streams     # flushed: reset or close before the next process
-        self._ws = None
-        self._ids_cache = None
+        self._allocate(nbytes, next(model.parameters()).device, track_end=True)
         self._mel = None
         self._bufs = {}
 
@@ -428,12 +426,7 @@ class FFNNStreamer(_StreamSlots):
                 raise ValueError(f"FFNN streaming does not take the DCT feature '{f}': its delta rows are "
                                  'differences along the frames')
         stft = model.stft
-        if stft.frame_length % (2*stft.hop_length):
-            raise ValueError('FFNN streaming needs frame_length to be a multiple of 2 hop (the centre padding '
-                             f'in whole hops), got {stft.frame_length} and hop {stft.hop_length}')
-        if not (stft.n_fft == stft.frame_length and stft.center and stft.pad_mode == 'constant' and stft.normalized
-                and stft.onesided and stft.compression_factor == 1 and stft.scale_factor == 1):
-            raise ValueError('FFNN streaming needs the STFT settings FFNN builds')
+        _check_stft(stft, 'FFNN')
         hidden = sum(isinstance(m, torch.nn.Linear) for m in model.ffnn.module_list) - 1
         from .ffnn_stream import MAX_HIDDEN
         if hidden > MAX_HIDDEN:
@@ -482,9 +475,7 @@ class FFNNStreamer(_StreamSlots):
             cfg.mean, cfg.std = norm.mean.data_ptr(), norm.std.data_ptr()
             tensors += [norm.mean, norm.std]
         for t in tensors:
-            hip.require_device(t)
-            if t.device != self.device:
-                raise RuntimeError(f'the model moved to {t.device}; the streams live on {self.device}')
+            self._check_device(t)
             if t.dtype != torch.float32 or not t.is_contiguous():
                 raise RuntimeError('the weights, biases and statistics must be contiguous fp32 tensors')
         if self._mel is None:
@@ -494,13 +485,9 @@ class FFNNStreamer(_StreamSlots):
         cfg.mel_fwd, cfg.mel_inv = self._mel[0].data_ptr(), self._mel[1].data_ptr()
         return cfg
 
-    def _reset(self, ids):
-        t = self._ids_tensor(ids)
+    def _launch_reset(self, t, n):
         cfg = self._geometry(self.model, self.channels)
-        self._ffs.call('brv_ffs_reset', ctypes.byref(cfg), self._state, self.max_streams, t, len(ids), hip.stream())
-        for i in ids:
-            self._hops[i] = 0
-            self._ended[i] = False
+        self._ffs.call('brv_ffs_reset', ctypes.byref(cfg), self._state, self.max_streams, t, n, hip.stream())
 
     def _input(self, x, n, what='input'):
         hip.require_device(x)
@@ -518,10 +505,7 @@ class FFNNStreamer(_StreamSlots):
         ffs, stft = self._ffs, self.model.stft
         cfg = self._config()
         c = ctypes.byref(cfg)
-        nbytes = ffs.query('brv_ffs_workspace_bytes', c, n, hops)
-        if self._ws is None or self._ws.numel() < nbytes:
-            self._ws = None
-            self._ws = torch.empty(int(nbytes), dtype=torch.uint8, device=self.device)
+        ws = self._workspace(ffs.query('brv_ffs_workspace_bytes', c, n, hops))
         C, N, hop, bins = self.channels, stft.n_fft, self.hop, stft.bins
         if (n, hops) not in self._bufs:
             if len(self._bufs) >= 16:
@@ -532,7 +516,7 @@ class FFNNStreamer(_StreamSlots):
                                      torch.empty(n, hops, N, **f32))
         xin, spec, mspec, frames = self._bufs[(n, hops)]
         tb = stft._tables(self.device)
-        t, st, ws = self._ids_tensor(ids), hip.stream(), self._ws
+        t, st = self._ids_tensor(ids), hip.stream()
         ffs.call('brv_ffs_step_frames', c, self._state, self.max_streams, t, n, x, hops, rest, xin, st)
         hip.call('brv_dft64_forward', xin, tb['basis'], spec, n*C, self.lag + hops*hop, N, hop, 0, hops, bins, 1.0,
                  1.0, st)
@@ -550,12 +534,8 @@ class FFNNStreamer(_StreamSlots):
         n = len(ids)
         x = self._input(x, n)
         L = x.shape[-1]
-        if L == 0 or L % self.hop:
-            raise ValueError(f'a chunk must be a positive multiple of hop = {self.hop} samples, got {L}')
-        for i in ids:
-            if self._ended[i]:
-                raise ValueError(f'stream {i} was flushed; reset or close it first')
-        hops = L//self.hop
+        hops = self._whole_hops(L)
+        self._check_live(ids)
         y = torch.empty(n, L, dtype=torch.float32, device=self.device)
         self._run(ids, n, x, hops, -1, y)
         for i in ids:
@@ -568,16 +548,8 @@ class FFNNStreamer(_StreamSlots):
         owed. Reset or close the streams afterwards."""
         ids = self._check_ids(ids)
         n = len(ids)
-        r = 0
-        if rest is not None:
-            rest = self._input(rest, n, 'rest')
-            r = rest.shape[-1]
-            if r >= self.hop:
-                raise ValueError(f'rest must be shorter than hop = {self.hop} samples, got {r}; '
-                                 'process the whole hops first')
-        for i in ids:
-            if self._ended[i]:
-                raise ValueError(f'stream {i} was flushed already; reset or close it first')
+        rest, r = self._rest(rest, n)
+        self._check_live(ids, ' already')
         y = torch.empty(n, self.lag + r, dtype=torch.float32, device=self.device)
         self._run(ids, n, rest if r else None, self.model.stft.n_fft//self.hop, r, y)
         for i in ids:

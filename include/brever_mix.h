@@ -29,6 +29,9 @@ typedef void* brv_stream_t;          /* hipStream_t */
 int brv_mix_version(void);
 const char* brv_mix_last_error(void);
 
+#define BRV_MIX_ENERGY_CHUNK 2048    /* samples per partial sum of brv_mix_energies */
+#define BRV_MIX_MAX_PARTS 512        /* partitions per impulse response the LDS tile of brv_mix_partition_mac holds */
+
 /* rows (nrows, row_len): row r = zeros, with pool[src, src + n) at [dst, dst + n).
  * desc (nrows, 3) int64 = (src, n, dst); pool_len bounds src + n. */
 int brv_mix_pack_signals(const float* pool, const int64_t* desc, float* rows, int64_t pool_len,

@@ -39,6 +39,8 @@ typedef void* brv_stream_t;          /* hipStream_t */
 int brv_rs_version(void);
 const char* brv_rs_last_error(void);
 
+#define BRV_RS_MAX_COLUMNS 32768     /* the most columns (count, ncols) one call takes */
+
 /* The longest input (and output) in samples: 2^22. */
 int64_t brv_rs_max_length(void);
 

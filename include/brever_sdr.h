@@ -45,6 +45,15 @@ typedef void* brv_stream_t;          /* hipStream_t */
 int brv_sdr_version(void);
 const char* brv_sdr_last_error(void);
 
+#define BRV_SDR_MAX_FILTER_LENGTH 512
+#define BRV_SDR_CHUNK 2048
+/* the bits of a row's flags word (the table above) */
+#define BRV_SDR_FLAG_NO_REFERENCE 1
+#define BRV_SDR_FLAG_NO_ESTIMATE 2
+#define BRV_SDR_FLAG_BAD_PIVOT 4
+#define BRV_SDR_FLAG_NUMERATOR_FLOOR 8
+#define BRV_SDR_FLAG_DENOMINATOR_FLOOR 16
+
 /* the largest filter_length the kernels take (512) and the chunk length of the correlation kernel (2048) */
 int64_t brv_sdr_max_filter_length(void);
 int64_t brv_sdr_chunk(void);

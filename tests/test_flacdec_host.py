@@ -195,11 +195,16 @@ def test_header_parses_and_every_export_resolves():
     assert restype is ctypes.c_int and argtypes[-1] is hip._c_ptr          # the stream, explicit
     assert (flac_gpu.INFO_WORDS, flac_gpu.FRAME_WORDS, flac_gpu.JOB_WORDS) == (8, 8, 12)
     with open(flac_gpu.HEADER_PATH) as f:
-        text = f.read()
-    for name, value in (('INFO_WORDS', 8), ('FRAME_WORDS', 8), ('JOB_WORDS', 12), ('NOT_TAKEN', '(-2)'),
-                        ('NOT_FLAC', '(-10)'), ('BAD_HEADER', '(-60)'), ('BAD_CRC16', '(-61)'),
-                        ('BAD_NUMBER', '(-62)'), ('TRUNCATED', '(-63)')):
-        assert f'#define BRV_FLACDEC_{name} {value}' in text
+        constants = hip.parse_constants(f.read())
+    assert constants == flac_gpu._LIB.constants and len(constants) == 13
+    for name, value in (('INFO_WORDS', 8), ('FRAME_WORDS', 8), ('JOB_WORDS', 12), ('NOT_TAKEN', -2),
+                        ('NOT_FLAC', -10), ('BAD_HEADER', -60), ('BAD_CRC16', -61),
+                        ('BAD_NUMBER', -62), ('TRUNCATED', -63)):
+        assert constants['BRV_FLACDEC_' + name] == getattr(flac_gpu, name) == value, name
+    assert {name[len('BRV_FLACDEC_JOB_'):]: value for name, value in constants.items()
+            if name.startswith('BRV_FLACDEC_JOB_') and name != 'BRV_FLACDEC_JOB_WORDS'} == \
+        dict(BAD_FIELDS=1, RESERVED=2, OVERRUN=3, LENGTH=4)
+    assert list(flac_gpu.JOB_MESSAGES) == [1, 2, 3, 4]
 
 
 def test_every_entry_point_sets_its_message():

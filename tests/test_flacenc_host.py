@@ -33,9 +33,12 @@ def test_header_parses_and_every_export_resolves():
     assert lib.brv_flacenc_version() >= 100
     restype, argtypes = table['brv_flacenc_encode']
     assert restype is ctypes.c_int and argtypes[-1] is hip._c_ptr          # the stream, explicit
-    for name, value in (('ROW_NONFINITE', 1), ('ROW_RANGE', 2), ('ROW_LENGTH', 4), ('ROW_INTERNAL', 8),
-                        ('MAX_LPC_ORDER', 32), ('MAX_ROWS', 65535)):
-        assert f'#define BRV_FLACENC_{name} {value}' in text
+    constants = hip.parse_constants(text)
+    assert constants == flac_enc._LIB.constants == {'BRV_FLACENC_' + name: value for name, value in (
+        ('ROW_NONFINITE', 1), ('ROW_RANGE', 2), ('ROW_LENGTH', 4), ('ROW_INTERNAL', 8), ('MAX_LPC_ORDER', 32),
+        ('MAX_ROWS', 65535))}
+    assert (flac_enc.MAX_ROWS, flac_enc.MAX_LPC_ORDER) == \
+        (constants['BRV_FLACENC_MAX_ROWS'], constants['BRV_FLACENC_MAX_LPC_ORDER'])
     assert set(flac_enc.ROW_MESSAGES) == {1, 2, 4, 8}
     assert (flac_enc.MAX_ROWS, flac_enc.MAX_LPC_ORDER) == (65535, 32)
 

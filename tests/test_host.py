@@ -187,6 +187,110 @@ def test_header_parser_is_strict():
             hip.parse_header(bad)
 
 
+SYNTHETIC_HEADER = """
+    #ifndef BRV_SYNTHETIC_H
+    #define BRV_SYNTHETIC_H
+    #define BRV_MACRO(x) ((x) + 1)          /* function-like: no constant */
+    #define BRV_N 3
+    #define BRV_MASK 0x1fu                  /* hex with a suffix */
+    #define BRV_BIG 65536L
+    #define BRV_REFUSED (-2)
+    #define BRV_PLAIN_NEGATIVE -7
+    #define BRV_SPACED ( 12 )
+    #define BRV_ZERO 0
+    // #define BRV_IN_A_COMMENT 9
+    #define OTHER_PREFIX (1 << 4)           /* not a BRV_ macro: not read */
+    typedef struct brv_small { uint32_t size; float gain; void* handle; } brv_small;
+    typedef struct brv_all {
+      int32_t a, b,        /* declarators spread over lines */
+              c;
+      uint32_t flags;      // a line comment between fields
+      /* a block comment
+         between fields */
+      int64_t count;
+      float eps[BRV_N];
+      int32_t twice[2*BRV_N], more[BRV_N + 1], fixed[5];
+      int64_t cube[4][2][4];
+      int64_t table[2*BRV_N][7];
+      const float* p[BRV_N];
+      void* handle;
+      const int32_t *ids, *more_ids;
+      float last;
+    } brv_all;
+    int brv_use(const brv_all* cfg, const brv_small* opts);
+    #endif
+"""
+
+
+def test_constant_and_struct_parsers_read_every_accepted_form():
+    """`hip.parse_constants` / `hip.parse_structs` on a synthetic header with every accepted form: the values, the
+    field list, and the offsets the C rules give (worked out by hand for the LP64 ABI)."""
+    c_i32, c_i64, c_f32, c_ptr = ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p
+    constants = hip.parse_constants(SYNTHETIC_HEADER)
+    assert constants == {'BRV_N': 3, 'BRV_MASK': 0x1f, 'BRV_BIG': 65536, 'BRV_REFUSED': -2,
+                         'BRV_PLAIN_NEGATIVE': -7, 'BRV_SPACED': 12, 'BRV_ZERO': 0}
+    structs = hip.parse_structs(SYNTHETIC_HEADER, constants)
+    assert list(structs) == ['brv_small', 'brv_all']
+    small, everything = structs['brv_small'], structs['brv_all']
+    assert issubclass(small, ctypes.Structure) and small.__name__ == 'brv_small'
+    assert small._fields_ == [('size', ctypes.c_uint32), ('gain', c_f32), ('handle', c_ptr)]
+    assert ctypes.sizeof(small) == 16
+    s = small(16, 0.5, None)                               # positional construction, in the header's order
+    assert (s.size, s.gain, s.handle) == (16, 0.5, None)
+    expected = [('a', c_i32, 0), ('b', c_i32, 4), ('c', c_i32, 8), ('flags', ctypes.c_uint32, 12),
+                ('count', c_i64, 16), ('eps', c_f32*3, 24), ('twice', c_i32*6, 36), ('more', c_i32*4, 60),
+                ('fixed', c_i32*5, 76), ('cube', ((c_i64*4)*2)*4, 96), ('table', (c_i64*7)*6, 352),
+                ('p', c_ptr*3, 688), ('handle', c_ptr, 712), ('ids', c_ptr, 720), ('more_ids', c_ptr, 728),
+                ('last', c_f32, 736)]
+    assert [name for name, _ in everything._fields_] == [name for name, _, _ in expected]
+    for name, ctype, offset in expected:
+        field = getattr(everything, name)
+        assert (dict(everything._fields_)[name], field.offset) == (ctype, offset), name
+    assert ctypes.sizeof(everything) == 744                # 740 rounded up to the 8-byte alignment
+    v = everything()
+    v.cube[3][1][2], v.table[5][6] = 7, 9                  # [4][2][4]: the first extent is the outermost
+    assert ctypes.sizeof(v.cube[0]) == 64 and len(v.cube) == 4 and len(v.cube[0]) == 2 and len(v.cube[0][0]) == 4
+    assert hip.parse_header(SYNTHETIC_HEADER)['brv_use'] == (ctypes.c_int, [hip._c_ptr, hip._c_ptr])
+
+
+@pytest.mark.parametrize('bad, named', [
+    ('#define BRV_SHIFT (1 << 4)', 'BRV_SHIFT'), ('#define BRV_SUM BRV_N + 1', 'BRV_SUM'),
+    ('#define BRV_FLOAT 1.5', 'BRV_FLOAT'), ('#define BRV_OCTAL 017', 'BRV_OCTAL'),
+    ('#define BRV_TEXT "text"', 'BRV_TEXT'), ('#define BRV_OPEN (3', 'BRV_OPEN'),
+    ('#define BRV_UNSIGNED_LONG_LONG 3ull + 1', 'BRV_UNSIGNED_LONG_LONG')])
+def test_constant_parser_refuses(bad, named):
+    with pytest.raises(RuntimeError, match='^' + named + ':'):
+        hip.parse_constants('#define BRV_N 3\n' + bad + '\n')
+
+
+@pytest.mark.parametrize('bad, named', [
+    ('typedef struct brv_x { int32_t a; struct { int32_t b; } in; } brv_x;', 'brv_x'),           # nested struct
+    ('typedef struct brv_x { int32_t a; brv_y inner; } brv_x;', r'brv_x\.inner'),                 # ... by name
+    ('typedef struct brv_x { int32_t a; struct brv_y y; } brv_x;', 'brv_y'),
+    ('typedef struct brv_x { int32_t a : 3; } brv_x;', r'brv_x\.a : 3'),                          # bit-field
+    ('typedef struct brv_x { int32_t a; double d; } brv_x;', r'brv_x\.d'),
+    ('typedef struct brv_x { int32_t a; int b; } brv_x;', r'brv_x\.b'),
+    ('typedef struct brv_x { unsigned int a; } brv_x;', r'brv_x\.int a'),
+    ('typedef struct brv_x { void v; } brv_x;', r'brv_x\.v'),
+    ('typedef struct brv_x { void (*done)(int); } brv_x;', r'brv_x\..*done'),                     # function pointer
+    ('typedef struct brv_x { float** rows; } brv_x;', r'brv_x\..*rows'),
+    ('typedef struct brv_x { int32_t a[BRV_UNKNOWN]; } brv_x;', r'brv_x\.a: .*BRV_UNKNOWN'),      # unknown extents
+    ('typedef struct brv_x { int32_t a[BRV_N*2]; } brv_x;', r'brv_x\.a: .*BRV_N\*2'),
+    ('typedef struct brv_x { int32_t a[2*BRV_N + 1]; } brv_x;', r'brv_x\.a'),
+    ('typedef struct brv_x { int32_t a[sizeof(int)]; } brv_x;', r'brv_x\.a'),
+    ('typedef struct brv_x { int32_t a[]; } brv_x;', r'brv_x\.a'),
+    ('typedef struct brv_x { int32_t a[2][2][2][2]; } brv_x;', r'brv_x\.a'),                      # four extents
+    ('typedef struct brv_x { int32_t a; int32_t b } brv_x;', 'brv_x'),                            # no semicolon
+    ('typedef struct brv_x { } brv_x;', 'brv_x'),
+    ('typedef struct brv_x { int32_t a; } brv_other;', 'brv_x'),
+    ('typedef struct other_x { int32_t a; } other_x;', 'other_x'),
+    ('struct brv_x { int32_t a; };', 'brv_x'),                                                    # no typedef
+    ('typedef struct { int32_t a; } brv_x;', 'struct')])
+def test_struct_parser_refuses(bad, named):
+    with pytest.raises(RuntimeError, match=named):
+        hip.parse_structs(bad, {'BRV_N': 3})
+
+
 def test_signatures_come_from_the_header():
     import re
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -209,10 +313,9 @@ def test_signatures_come_from_the_header():
     assert hip.SIGNATURES['brv_prof_destroy'][0] is None
 
 
-def test_a_missing_header_is_named(monkeypatch, tmp_path):
-    monkeypatch.setattr(hip, 'HEADER_PATH', str(tmp_path/'include'/'brever_hip.h'))
+def test_a_missing_header_is_named(tmp_path):
     with pytest.raises(RuntimeError, match=str(tmp_path/'include'/'brever_hip.h')):
-        hip._header_signatures()
+        hip._header_text(str(tmp_path/'include'/'brever_hip.h'))
 
 
 def test_pointer_argtype_takes_tensors():

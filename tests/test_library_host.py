@@ -35,6 +35,76 @@ def test_paths_and_signatures_come_from_the_arguments(bound):
     assert hip.SIGNATURES is not sdr.SIGNATURES and 'brv_last_error' in hip.SIGNATURES
 
 
+def test_structs_and_constants_come_from_the_header(bound):
+    from brever_amd import ffnn_stream
+    with open(bound.header_path) as f:
+        text = f.read()
+    assert bound.constants == hip.parse_constants(text) == sdr._LIB.constants and bound.structs == {}
+    with open(hip.HEADER_PATH) as f:
+        text = f.read()
+    constants = hip.parse_constants(text)
+    assert hip._LIB.constants == constants and len(constants) == 14
+    assert {name: getattr(hip, name[4:]) for name in constants if name.startswith('BRV_OPT_')} == \
+        {name: value for name, value in constants.items() if name.startswith('BRV_OPT_')}
+    assert hip.OPT_KNOWN == 0x17ff and hip.DCCRN_STREAM_MAX_LEVELS == constants['BRV_DCCRN_STREAM_MAX_LEVELS'] == 8
+    assert sorted(flag for _, flag, _ in hip._ENV_FLAGS) == sorted(
+        value for name, value in constants.items() if name.startswith('BRV_OPT_') and name != 'BRV_OPT_KNOWN')
+    assert hip._LIB.structs == {'brv_launch_opts': hip.LaunchOpts, 'brv_ctn_config': hip.CtnConfig,
+                                'brv_dccrn_stream_config': hip.DccrnStreamConfig}
+    assert ffnn_stream._LIB.structs == {'brv_ffs_config': ffnn_stream.FfsConfig}
+    assert [name for name, _ in hip.CtnConfig._fields_] == [
+        'filters', 'filter_length', 'bottleneck_channels', 'hidden_channels', 'skip_channels', 'kernel_size',
+        'layers', 'repeats', 'output_sources', 'causal']
+    cfg = hip.CtnConfig(512, 32, 128, 512, 128, 3, 8, 3, 2, 1)       # positional, as models/convtasnet.py builds it
+    assert (cfg.filters, cfg.skip_channels, cfg.causal) == (512, 128, 1)
+    assert hip.LaunchOpts._fields_ == [('size', ctypes.c_uint32), ('flags', ctypes.c_uint32),
+                                       ('cu_eighths', ctypes.c_int32), ('wg_target', ctypes.c_int32),
+                                       ('prof', ctypes.c_void_p)]
+
+
+def test_struct_layouts_equal_the_compilers(tmp_path):
+    """Every struct of every header: `sizeof`, and `offsetof` and size of each field, as a C++ compiler sees the
+    header, against the classes derived from its text."""
+    import glob
+    import shutil
+    clang = '/opt/rocm/lib/llvm/bin/clang++'
+    compilers = [c for c in (clang if os.path.exists(clang) else None, shutil.which('clang++'), shutil.which('g++'))
+                 if c]
+    assert compilers, 'no C++ compiler'
+    headers = sorted(glob.glob(os.path.join(ROOT, 'include', '*.h')))
+    assert len(headers) == 9
+    sizes = {}
+    for header in headers:
+        with open(header) as f:
+            text = f.read()
+        structs = hip.parse_structs(text, hip.parse_constants(text))
+        if not structs:
+            continue
+        lines = ['#include <cstddef>', '#include <cstdio>', f'#include "{header}"', 'int main() {']
+        expected = []
+        for name, cls in structs.items():
+            sizes[name] = ctypes.sizeof(cls)
+            lines.append(f'  std::printf("{name} %zu\\n", sizeof({name}));')
+            expected.append(f'{name} {ctypes.sizeof(cls)}')
+            for field, _ in cls._fields_:
+                lines.append(f'  std::printf("{name}.{field} %zu %zu\\n", offsetof({name}, {field}), '
+                             f'sizeof((({name}*)0)->{field}));')
+                expected.append(f'{name}.{field} {getattr(cls, field).offset} {getattr(cls, field).size}')
+        src, exe = str(tmp_path/'layout.cpp'), str(tmp_path/'layout')
+        with open(src, 'w') as f:
+            f.write('\n'.join(lines + ['  return 0;', '}', '']))
+        for cxx in compilers:
+            r = subprocess.run([cxx, '-std=c++17', src, '-o', exe], capture_output=True, text=True)
+            if r.returncode == 0:
+                break
+        else:
+            pytest.fail(f'the layout program of {header} does not compile:\n' + r.stderr)
+        out = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+        assert out.returncode == 0 and out.stdout.splitlines() == expected, header
+    assert sizes == {'brv_launch_opts': 24, 'brv_ctn_config': 40, 'brv_dccrn_stream_config': 1592,
+                     'brv_ffs_config': 336}
+
+
 def test_a_missing_library_names_the_path_the_build_and_the_consequence():
     missing = hip.Library('brever_sdr.h', 'libbrever_no_such.so', 'BRV_NO_SUCH_SWITCH', WHAT)
     path = os.path.join(ROOT, 'brever_amd', 'csrc', 'libbrever_no_such.so')

@@ -76,6 +76,9 @@ def test_header_parses_and_every_export_resolves():
     assert lib.brv_mix_version() >= 100
     # a library of its own: nothing of it is declared in, or exported by, the main one
     assert not any(n.startswith('brv_mix_') for n in hip.SIGNATURES)
+    # the limits are the header's macros
+    assert mixture._LIB.constants == {'BRV_MIX_ENERGY_CHUNK': 2048, 'BRV_MIX_MAX_PARTS': 512}
+    assert (mixture.EN_CHUNK, mixture.MAX_PARTS) == (2048, 512)
 
 
 # Number arguments that a call would ACCEPT (by position), where all ones would not be: with them as the baseline

@@ -117,6 +117,8 @@ def test_header_parses_and_every_export_resolves():
     from brever_amd import mixture
     assert not any(n.startswith('brv_rs_') for n in list(hip.SIGNATURES) + list(mixture.SIGNATURES))
     assert not hasattr(hip.lib(), 'brv_rs_version')
+    # the limit is the header's macro
+    assert io._LIB.constants == {'BRV_RS_MAX_COLUMNS': 32768} and io.MAX_COLUMNS == 32768
 
 
 def _args(name, fill, fft_len=4096):

@@ -91,6 +91,17 @@ def test_header_parses_and_every_export_resolves():
     assert lib.brv_sdr_version() >= 100
     assert lib.brv_sdr_max_filter_length() == sdr.MAX_FILTER_LENGTH == 512
     assert lib.brv_sdr_chunk() == R.CHUNK
+    # the limits and the flag bits are the header's macros, and the library was compiled from the same ones
+    constants = sdr._LIB.constants
+    assert constants == {'BRV_SDR_MAX_FILTER_LENGTH': 512, 'BRV_SDR_CHUNK': 2048, 'BRV_SDR_FLAG_NO_REFERENCE': 1,
+                         'BRV_SDR_FLAG_NO_ESTIMATE': 2, 'BRV_SDR_FLAG_BAD_PIVOT': 4,
+                         'BRV_SDR_FLAG_NUMERATOR_FLOOR': 8, 'BRV_SDR_FLAG_DENOMINATOR_FLOOR': 16}
+    assert constants['BRV_SDR_MAX_FILTER_LENGTH'] == sdr.MAX_FILTER_LENGTH == lib.brv_sdr_max_filter_length()
+    assert constants['BRV_SDR_CHUNK'] == lib.brv_sdr_chunk()
+    assert (sdr.NO_REFERENCE, sdr.NO_ESTIMATE, sdr.BAD_PIVOT, sdr.NUMERATOR_FLOOR, sdr.DENOMINATOR_FLOOR) == \
+        tuple(constants['BRV_SDR_FLAG_' + name] for name in (
+            'NO_REFERENCE', 'NO_ESTIMATE', 'BAD_PIVOT', 'NUMERATOR_FLOOR', 'DENOMINATOR_FLOOR')) == (1, 2, 4, 8, 16)
+    assert sdr.DEGENERATE == 7
     assert not any(n.startswith('brv_sdr_') for n in hip.SIGNATURES)
     assert not hasattr(hip.lib(), 'brv_sdr_version')
 
