@@ -5,7 +5,8 @@
 A thin command line over ``brever_amd.mixture.PoolMixtureMaker.write_dataset``: the mixtures of ``--epoch`` are
 drawn from ``--seed``, synthesised batch by batch from the in-memory pools of ``--pool`` (a ``.npz`` with
 ``speech_<i>``, ``noise_<i>``, ``brir_<room>_<angle>`` arrays) and encoded as stereo FLAC on the device; the same
-``(seed, epoch)`` gives byte-identical archives. Like the reference's ``scripts/create_dataset.py`` it refuses a
+``(seed, epoch)`` gives byte-identical archives. With ``--simulate_rooms N`` the BRIRs are not read from the pool
+but simulated on the device for ``N`` random shoebox rooms (``brever_amd.rir``; ``--room_*``). Like the reference's ``scripts/create_dataset.py`` it refuses a
 directory that already holds a ``mixture_info.json`` unless ``-f`` is given, and ``--no_tar`` writes the directory
 ``DIR/audio/`` instead of the archive.
 
@@ -58,7 +59,27 @@ def parse(argv=None):
     p.add_argument('--decay_drr', type=float, nargs=2, default=[5.0, 35.0])
     p.add_argument('--decay_delay', type=float, nargs=2, default=[0.075, 0.100])
     p.add_argument('--synthetic_noises', nargs='*', default=[])
+    # BRIRs simulated on the device instead of read from the pool (brever_amd.rir: random_rooms, simulate_brirs)
+    p.add_argument('--simulate_rooms', type=int, default=0, metavar='N',
+                   help='simulate N shoebox rooms for the BRIRs; --pool then needs speech_<i> / noise_<i> only')
+    p.add_argument('--room_seed', type=int, default=0)
+    p.add_argument('--room_rt60', type=float, nargs=2, default=[0.2, 0.8], metavar=('LO', 'HI'))
+    p.add_argument('--room_distance', type=float, nargs=2, default=[0.5, 3.0], metavar=('LO', 'HI'))
+    p.add_argument('--room_angles', type=float, nargs='+', default=list(range(-90, 91, 10)), metavar='A')
+    p.add_argument('--room_taps', type=int, default=None, help='taps of every BRIR; default ceil(rt60 fs) per room')
     return p.parse_args(argv)
+
+
+def simulated_pools(args):
+    """``speech``, ``noises`` of ``--pool`` and the BRIRs of ``--simulate_rooms`` rooms, as the maker's keywords."""
+    from brever_amd import rir
+    from brever_amd.mixture import PoolMixtureMaker
+    if args.simulate_rooms < 1:
+        raise SystemExit('--simulate_rooms must be at least 1')
+    speech, noises, _ = PoolMixtureMaker._load(args.pool)
+    rooms = rir.random_rooms(args.simulate_rooms, args.room_seed, rt60=args.room_rt60, distance=args.room_distance,
+                             angles=args.room_angles, taps=args.room_taps, fs=args.fs)
+    return dict(speech=speech, noises=noises, brirs=rir.simulate_brirs(rooms, fs=args.fs, device=args.device))
 
 
 def main(argv=None):
@@ -69,13 +90,14 @@ def main(argv=None):
     if args.size < 1:
         raise SystemExit('--size must be at least 1')
     from brever_amd.mixture import PoolMixtureMaker
+    pools = simulated_pools(args) if args.simulate_rooms else {}
     maker = PoolMixtureMaker(
         args.pool, args.sources, args.size, seed=args.seed, fs=args.fs, padding=args.padding,
         noise_count=args.noise_count, snr=args.snr, ndr=args.ndr, diffuse=args.diffuse, rms_jitter=args.rms_jitter,
         batch=args.batch, block=args.block, device=args.device, diffuse_color=args.diffuse_color,
         diffuse_ltas_eq=args.diffuse_ltas_eq, decay=args.decay, decay_color=args.decay_color,
         decay_rt60=args.decay_rt60, decay_drr=args.decay_drr, decay_delay=args.decay_delay,
-        synthetic_noises=args.synthetic_noises)
+        synthetic_noises=args.synthetic_noises, **pools)
     if args.force:                                 # what the other form of an earlier run left
         import shutil
         stale = os.path.join(args.output, 'audio' if not args.no_tar else 'audio.tar')

@@ -1,0 +1,121 @@
+"""Time of the shoebox image-source simulator (brever_amd/rir.py).
+
+    python tools/rir_bench.py [--shapes 100x19x8000 2x3x800] [--fs 16000] [--seed 0] [--repeats 3]
+
+One JSON line per shape ROOMSxANGLESxTAPS: `random_rooms(ROOMS, seed, angles=ANGLES equally spaced, taps=TAPS)`,
+two ears per angle. `value` is the median over `--repeats` launches of brv_rir_simulate alone (a host clock around a
+launch that ends in a device synchronise, after one warm-up launch); `tables_ms` is the host's table building,
+`end_to_end_ms` one whole `simulate_brirs` call (tables, upload, launch, download).
+
+What the model asks for is counted from the tables, not timed: `images` are the images that touch at least one tap,
+`window_evaluations` the (image, tap) pairs with |t - tau| < W/2. Both are exact for the first job of every room and
+multiplied by the room's jobs (the ears of a room differ by centimetres). A window evaluation needs 7 fp64 vector
+operations (a subtraction, two FMAs, two products, a reciprocal, an addition); `share_of_fp64_issue_peak` sets
+that against 39.3 T fp64 vector instructions per second (the 78.6 TFLOP/s of the datasheet), and is therefore a
+floor's share, not a utilisation: the kernel's reciprocal alone is five instructions, and selects, compares and LDS
+reads come on top. `tile_images` gives the median and the largest number of images per tile of the first job,
+which is what makes the last tiles of a long response the expensive ones."""
+import argparse
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from brever_amd import rir  # noqa: E402
+
+FP64_INSTRUCTIONS_PER_SECOND = 39.3e12
+INSTRUCTIONS_PER_EVALUATION = 7
+
+
+def job_inputs(rooms):
+    """``geom``, ``shape`` as ``simulate_brirs`` lays them out, and the first job of every room with its job count."""
+    geom, shape, first, at = [], [], [], 0
+    for room in rooms:
+        first.append((len(geom), 2*len(room.angles)))
+        ears, side = room.ears(), room.side()
+        for angle in room.angles:
+            for e in range(2):
+                geom.append(rir._geom_row(room.dims, room.beta, room.source(angle), ears[e],
+                                          side if e == 0 else -side, room.ear_pattern))
+                shape.append((room.taps, at + e, 2))
+            at += 2*room.taps
+    return np.array(geom), np.array(shape), first
+
+
+def count_job(rows, ix, opts, tiles=False):
+    """``(images, window evaluations, images per tile or None)`` of one job from its tables."""
+    fs, c, W = opts
+    hdr, nx, ny, nz, taps = (int(v) for v in ix[:5])
+    x2, y2, z2 = (rows[a:b, 3] for a, b in ((hdr + 1, hdr + 1 + nx), (hdr + 1 + nx, hdr + 1 + nx + ny),
+                                            (hdr + 1 + nx + ny, hdr + 1 + nx + ny + nz)))
+    tau = np.sqrt((x2[:, None, None] + y2[None, :, None]) + z2[None, None, :]).ravel()*fs/c
+    first = np.maximum(np.floor(tau - W/2) + 1, 0)
+    last = np.minimum(np.ceil(tau + W/2) - 1, taps - 1)
+    n = np.maximum(last - first + 1, 0)
+    hit = n > 0
+    per_tile = None
+    if tiles:                                           # an image counts in every tile it touches
+        first, last = first[hit], last[hit]
+        per_tile = np.array([np.count_nonzero((first <= t + rir.TILE - 1) & (last >= t))
+                             for t in range(0, taps, rir.TILE)])
+    return int(hit.sum()), int(n.sum()), per_tile
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--shapes', nargs='+', default=['100x19x8000', '2x3x800'])
+    ap.add_argument('--fs', type=int, default=16000)
+    ap.add_argument('--seed', type=int, default=0)
+    ap.add_argument('--repeats', type=int, default=3)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit('rir_bench needs a ROCm device: a time from anywhere else says nothing')
+    dev = torch.device('cuda:0')
+    for spec in args.shapes:
+        n_rooms, n_angles, taps = (int(v) for v in spec.split('x'))
+        angles = np.linspace(-90.0, 90.0, n_angles).tolist() if n_angles > 1 else [0.0]
+        rooms = rir.random_rooms(n_rooms, args.seed, angles=angles, taps=taps, fs=args.fs)
+        geom, shape, first = job_inputs(rooms)
+        t0 = time.perf_counter()
+        rows, index, opts = rir.build_tables(geom, shape, args.fs)
+        tables_ms = 1e3*(time.perf_counter() - t0)
+        images = evaluations = 0
+        for j, jobs in first:
+            i, e, per_tile = count_job(rows, index[j], opts, tiles=j == 0)
+            images, evaluations = images + i*jobs, evaluations + e*jobs
+            if j == 0:
+                tile_images = dict(median=float(np.median(per_tile)), largest=float(per_tile.max()),
+                                   tiles=len(per_tile))
+        tables, index_d = torch.from_numpy(rows).to(dev), torch.from_numpy(index).to(dev)
+        out = torch.zeros(2*taps*n_rooms*n_angles, dtype=torch.float32, device=dev)
+        times = []
+        for k in range(args.repeats + 1):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            rir.launch(tables, index_d, opts, -1, taps, out)
+            torch.cuda.synchronize()
+            times.append(time.perf_counter() - t0)
+        seconds = float(np.median(times[1:]))
+        t0 = time.perf_counter()
+        brirs = rir.simulate_brirs(rooms, fs=args.fs, device=dev)
+        end_to_end_ms = 1e3*(time.perf_counter() - t0)
+        assert np.array_equal(brirs[0][0].reshape(-1), out[:2*taps].cpu().numpy())
+        line = dict(metric='rir_simulate_ms', value=1e3*seconds, min_ms=1e3*float(min(times[1:])),
+                    first_launch_ms=1e3*times[0], repeats=args.repeats, rooms=n_rooms, angles=n_angles, taps=taps,
+                    jobs=len(geom), fs=args.fs, window=float(opts[2]), table_rows=len(rows), tables_ms=tables_ms,
+                    end_to_end_ms=end_to_end_ms, images=images, window_evaluations=evaluations,
+                    images_per_s=images/seconds, window_evaluations_per_s=evaluations/seconds,
+                    share_of_fp64_issue_peak=evaluations*INSTRUCTIONS_PER_EVALUATION/seconds /
+                    FP64_INSTRUCTIONS_PER_SECOND, tile_images=tile_images,
+                    timing='host clock around one launch ending in a device synchronise, median',
+                    counts='exact for the first job of every room, times the jobs of the room')
+        print(json.dumps(line), flush=True)
+
+
+if __name__ == '__main__':
+    main()
