@@ -19,6 +19,8 @@
 //
 // Entry positions, the flush points and the slices of the waves are functions of the job's own tables and of the
 // tile, nothing else: no atomics, bitwise repeatable, a job alone equals the job in a batch.
+//
+// rir_bands.cuh, included at the end, adds the band entry points (octave-band walls, a spherical-head ear).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -366,6 +368,9 @@ int brv_rir_simulate(const double* tables, const int64_t* index, int64_t n_jobs,
 }
 
 }
+
+// the band entry points (include/rir/brever_rir_bands.h)
+#include "rir_bands.cuh"
 
 // the library's last-error message and its two status exports (../status.h)
 BRV_DEFINE_STATUS(brv_rir_version, brv_rir_last_error)

@@ -8,6 +8,13 @@ scaled by the walls it crossed, by ``1/(4 pi d)`` and by a first-order receiver 
 accumulation are fp64, the output is fp32; results are bitwise repeatable and a response is the same alone as in a
 batch.
 
+With ``beta`` of shape ``(K, 6)`` the walls have one coefficient per octave band (centres ``125 * 2^k`` Hz), and with
+``ear_model='sphere'`` an ear is a point on a rigid sphere (Brown & Duda 1998): a delay that follows the path round
+the head and a head shadow that grows with frequency (include/rir/brever_rir_bands.h; csrc/rir/rir_bands.cuh;
+DESIGN.md 5n). Every image then has one amplitude per channel, the tile kernel accumulates the channels together and
+a second kernel passes each through its fixed filter (``band_filters``). Air absorption, measured HRTFs and pinna
+cues, source directivity, torso effects and other room shapes stay out of scope.
+
 ``simulate_brirs(random_rooms(n, seed))`` is the ``brirs=`` argument of ``PoolMixtureMaker``; ``save_pool`` writes the
 ``.npz`` its ``path`` argument reads. There is no CPU fallback: without the library or a ROCm device the calls raise.
 """
@@ -27,24 +34,49 @@ GEOM_DOUBLES, SHAPE_WORDS, OPT_DOUBLES, ROW_DOUBLES, INDEX_WORDS, TILE, MAX_AXIS
     _LIB.constants['BRV_RIR_' + name] for name in (
         'GEOM_DOUBLES', 'SHAPE_WORDS', 'OPT_DOUBLES', 'ROW_DOUBLES', 'INDEX_WORDS', 'TILE', 'MAX_AXIS_ROWS',
         'MAX_TAPS', 'MAX_JOBS'))
+# the brv_rir_bands_* entry points of the same library (include/rir/brever_rir_bands.h)
+_BANDS = hip.Library('rir/brever_rir_bands.h', 'libbrever_rir.so', 'BRV_RIR_LIB_PATH',
+                     'The room simulator has no CPU fallback.')
+bands_call, bands_query = _BANDS.call, _BANDS.query
+MAX_BANDS, BANDS_GEOM_DOUBLES, BANDS_OPT_DOUBLES, PATTERN, SPHERE, MAX_FILTER, COMBINE_TILE = (
+    _BANDS.constants['BRV_RIR_BANDS_' + name] for name in (
+        'MAX_BANDS', 'GEOM_DOUBLES', 'OPT_DOUBLES', 'PATTERN', 'SPHERE', 'MAX_FILTER', 'COMBINE_TILE'))
+EAR_MODELS = {'pattern': PATTERN, 'sphere': SPHERE}
+FILTER_MULTIPLE = 16                             # brv_rir_bands_combine takes the filter 16 taps at a time
 SABINE = 0.161                                   # s/m
 
 
 class ShoeboxRoom:
     """A room with a head in it: ``dims`` (3,) metres, ``beta`` (6,) wall reflection coefficients
-    ``(x0, x1, y0, y1, z0, z1)``, ``head`` (3,) the head's centre, ``yaw`` radians (the head looks along
-    ``(cos yaw, sin yaw, 0)``), a source at ``distance`` metres at the ears' height for every azimuth of ``angles``
-    (degrees, counter-clockwise seen from above: positive is left), responses of ``taps`` samples."""
+    ``(x0, x1, y0, y1, z0, z1)`` or ``(K, 6)``, one row per octave band from 125 Hz upwards, ``head`` (3,) the head's
+    centre, ``yaw`` radians (the head looks along ``(cos yaw, sin yaw, 0)``), a source at ``distance`` metres at the
+    ears' height for every azimuth of ``angles`` (degrees, counter-clockwise seen from above: positive is left),
+    responses of ``taps`` samples. ``ear_model``: ``'pattern'``, an ear is a first-order receiver ``ear_pattern`` at
+    ``head_radius`` from the centre, or ``'sphere'``, an ear is a point on a rigid sphere of that radius."""
 
-    def __init__(self, dims, beta, head, yaw, distance, angles, taps, ear_pattern=0.75, head_radius=0.0875):
+    def __init__(self, dims, beta, head, yaw, distance, angles, taps, ear_pattern=0.75, head_radius=0.0875,
+                 ear_model='pattern'):
         self.dims = tuple(float(v) for v in dims)
-        self.beta = tuple(float(v) for v in beta)
+        banded = np.ndim(beta) == 2
+        if banded:
+            self.beta = tuple(tuple(float(v) for v in row) for row in beta)
+            if not 1 <= len(self.beta) <= MAX_BANDS or any(len(row) != 6 for row in self.beta):
+                raise ValueError(f'beta by band is (K, 6) with 1 <= K <= {MAX_BANDS}')
+        else:
+            self.beta = tuple(float(v) for v in beta)
+        if ear_model not in EAR_MODELS:
+            raise ValueError(f'ear_model is one of {sorted(EAR_MODELS)}, not {ear_model!r}')
+        self.ear_model = ear_model
         self.head = tuple(float(v) for v in head)
         self.yaw, self.distance, self.angles, self.taps = float(yaw), float(distance), \
             tuple(float(v) for v in angles), int(taps)
         self.ear_pattern, self.head_radius = float(ear_pattern), float(head_radius)
-        if len(self.dims) != 3 or len(self.beta) != 6 or len(self.head) != 3 or not self.angles:
+        if len(self.dims) != 3 or (not banded and len(self.beta) != 6) or len(self.head) != 3 or not self.angles:
             raise ValueError('dims and head have 3 values, beta has 6, angles at least one')
+
+    def bands(self):
+        """Octave bands of ``beta``; 0 for one coefficient per wall."""
+        return len(self.beta) if np.ndim(self.beta) == 2 else 0
 
     def side(self):
         """Unit vector from the head's centre to the left ear."""
@@ -62,13 +94,16 @@ class ShoeboxRoom:
     def __repr__(self):
         return (f'ShoeboxRoom(dims={self.dims}, beta={self.beta}, head={self.head}, yaw={self.yaw}, '
                 f'distance={self.distance}, angles={self.angles}, taps={self.taps}, '
-                f'ear_pattern={self.ear_pattern}, head_radius={self.head_radius})')
+                f'ear_pattern={self.ear_pattern}, head_radius={self.head_radius}' +
+                ('' if self.ear_model == 'pattern' else f', ear_model={self.ear_model!r}') + ')')
 
 
 def beta_from_rt60(dims, rt60):
     """The one reflection coefficient of all six walls that gives ``rt60`` seconds by Sabine's formula: uniform
     absorption ``alpha = 0.161 V / (S rt60)``, ``beta = sqrt(1 - alpha)``. ``ValueError`` for an ``rt60`` the room
-    cannot reach (``alpha >= 1``)."""
+    cannot reach (``alpha >= 1``). A sequence of ``rt60`` (one per band) gives a tuple, one value per band."""
+    if np.ndim(rt60) > 0:
+        return tuple(beta_from_rt60(dims, float(v)) for v in rt60)
     alpha = min_rt60(dims)/rt60 if rt60 > 0 else math.inf
     if not alpha < 1.0:
         raise ValueError(f'rt60 {rt60} s is out of reach of a {tuple(dims)} m room: Sabine absorption {alpha:.3f} >= 1')
@@ -133,17 +168,202 @@ def _geom_row(dims, beta, source, receiver, orientation, pattern):
     return row
 
 
+# -- octave bands and the spherical head (include/rir/brever_rir_bands.h) -----------------------------
+def default_band_taps(fs):
+    """``N = 2^ceil(log2(fs / 62.5))``: 256 at 16 kHz, 1 024 at 48 kHz -- a bin spacing of at most 62.5 Hz, half the
+    centre of the lowest band."""
+    return 1 << max(math.ceil(math.log2(fs/62.5)), 1)
+
+
+def band_centres(bands):
+    return 125.0*2.0**np.arange(int(bands))
+
+
+def band_filter_bank(fs, bands, taps=None):
+    """``(K, N)`` float64: the linear-phase band filters ``g_k``. On the ``N/2 + 1`` real-DFT bins the gains are
+    raised cosines on a log-frequency axis (``G_k = cos^2(pi y / 2)``, ``G_{k+1} = sin^2(pi y / 2)`` with
+    ``y = log2(f / fc_k)`` between two centres; the first band is 1 below its centre, the last 1 above its own), so
+    they sum to one in every bin; ``g_k = fftshift(irfft(G_k)) * hann`` with the Hann window's peak at ``N/2``, so the
+    ``g_k`` sum to the unit impulse at ``N/2``."""
+    K, N = int(bands), default_band_taps(fs) if taps is None else int(taps)
+    fc = band_centres(K)
+    if not 1 <= K <= MAX_BANDS:
+        raise ValueError(f'requires 1 <= bands <= {MAX_BANDS}')
+    if not fc[-1] < 0.5*fs:
+        raise ValueError(f'the centre of band {K - 1}, {fc[-1]:g} Hz, is not below fs/2 = {0.5*fs:g} Hz')
+    if N < 2 or N % 2 or N > MAX_FILTER:
+        raise ValueError(f'requires an even number of filter taps in [2, {MAX_FILTER}]')
+    f = np.arange(N//2 + 1)*(fs/N)
+    G = np.zeros((K, len(f)))
+    G[0, f <= fc[0]] = 1.0
+    G[K - 1, f >= fc[K - 1]] = 1.0
+    for k in range(K - 1):
+        m = (f >= fc[k]) & (f < fc[k + 1])
+        y = np.log2(f[m]/fc[k])
+        G[k, m], G[k + 1, m] = np.cos(0.5*np.pi*y)**2, np.sin(0.5*np.pi*y)**2
+    hann = 0.5*(1.0 + np.cos(2.0*np.pi*(np.arange(N) - N//2)/N))
+    return np.fft.fftshift(np.fft.irfft(G, N, axis=1), axes=1)*hann
+
+
+def head_lowpass(fs, head_radius, c=343.0):
+    """The head-shadow low-pass ``1 / (1 + s / (2 w0))``, ``w0 = c / rad``, by the bilinear transform
+    (``y[n] = (x[n] + x[n-1]) / (1 + kk) - (1 - kk) / (1 + kk) y[n-1]``, ``kk = fs / w0``) as a FIR of
+    ``ceil(40 ln 2 / -ln |pole|)`` taps: what is cut off is below ``2^-40``."""
+    kk = fs*head_radius/c
+    pole = -(1.0 - kk)/(1.0 + kk)
+    if not 0.0 < abs(pole) < 1.0:
+        raise ValueError(f'no low-pass for fs {fs}, head radius {head_radius}, c {c}')
+    M = math.ceil(40.0*math.log(2.0)/-math.log(abs(pole)))
+    lp = np.empty(M)
+    lp[0] = 1.0/(1.0 + kk)
+    if M > 1:
+        lp[1:] = lp[0]*(1.0 + pole)*pole**np.arange(M - 1)
+    return lp
+
+
+_FILTERS = {}
+
+
+def band_filters(fs, bands, ear_model='pattern', head_radius=0.0875, c=343.0, taps=None):
+    """``(filters, pad)``: the ``(C, M_f)`` float64 channel filters of ``brv_rir_bands_combine`` and ``pad = N/2``.
+    Pattern mode: channel ``k`` is ``g_k``. Sphere mode: channel ``k`` is ``g_k`` and channel ``K + k`` is ``g_k``
+    convolved with the head's low-pass. ``M_f`` is padded with zeros to a multiple of 16. Cached per argument set;
+    the array is read-only."""
+    N = default_band_taps(fs) if taps is None else int(taps)
+    sphere = EAR_MODELS[ear_model] == SPHERE
+    key = (float(fs), int(bands), N, float(head_radius) if sphere else None, float(c) if sphere else None)
+    if key not in _FILTERS:
+        g = band_filter_bank(fs, bands, N)
+        rows = list(g)
+        if sphere:
+            lp = head_lowpass(fs, head_radius, c)
+            rows += [np.convolve(row, lp) for row in g]
+        longest = max(len(row) for row in rows)
+        m_f = -(-longest//FILTER_MULTIPLE)*FILTER_MULTIPLE
+        if m_f > MAX_FILTER:
+            raise ValueError(f'the channel filters have {longest} taps, more than {MAX_FILTER}')
+        filters = np.zeros((len(rows), m_f))
+        for i, row in enumerate(rows):
+            filters[i, :len(row)] = row
+        filters.setflags(write=False)
+        _FILTERS[key] = (filters, N//2)
+    return _FILTERS[key]
+
+
+def _band_geom_row(dims, beta, source, receiver, orientation, pattern):
+    row = np.zeros(BANDS_GEOM_DOUBLES)
+    row[0:3], row[3:6], row[6:9], row[9:12], row[12] = dims, source, receiver, orientation, pattern
+    beta = np.asarray(beta, dtype=np.float64).reshape(-1, 6)
+    row[13:13 + beta.size] = beta.ravel()
+    return row
+
+
+def band_opts(fs, bands, ear_model='pattern', head_radius=0.0875, window=None, c=343.0, pad=None):
+    """The seven options of the band entry points as the library takes them."""
+    if ear_model not in EAR_MODELS:
+        raise ValueError(f'ear_model is one of {sorted(EAR_MODELS)}, not {ear_model!r}')
+    opts = np.array([fs, c, default_window(fs) if window is None else window, bands, EAR_MODELS[ear_model],
+                     head_radius, default_band_taps(fs)//2 if pad is None else pad], dtype=np.float64)
+    assert len(opts) == BANDS_OPT_DOUBLES
+    return opts
+
+
+def build_band_tables(geom, shape, opts, max_order=-1):
+    """The two host steps of the band entry points for ``geom`` (J, 61) float64, ``shape`` (J, 3) int64 and ``opts``
+    of ``band_opts``: ``(rows, index)`` with rows of ``3 + K`` doubles; ``index[:, 7]`` is where a job's channel rows
+    begin in the scratch. Refused values raise with the library's message."""
+    geom = np.ascontiguousarray(geom, dtype=np.float64).reshape(-1, BANDS_GEOM_DOUBLES)
+    shape = np.ascontiguousarray(shape, dtype=np.int64).reshape(-1, SHAPE_WORDS)
+    jobs = len(geom)
+    if len(shape) != jobs:
+        raise ValueError('one shape row per job')
+    n_rows = bands_query('brv_rir_bands_table_rows', geom.ctypes.data, shape.ctypes.data, jobs, opts.ctypes.data,
+                         max_order)
+    rows = np.empty((n_rows, 3 + int(opts[3])), dtype=np.float64)
+    index = np.empty((jobs, INDEX_WORDS), dtype=np.int64)
+    bands_call('brv_rir_bands_build_tables', geom.ctypes.data, shape.ctypes.data, jobs, opts.ctypes.data, max_order,
+               rows.ctypes.data, index.ctypes.data, n_rows)
+    return rows, index
+
+
+def channels_of(opts):
+    return int(opts[3])*(2 if int(opts[4]) == SPHERE else 1)
+
+
+def launch_bands(tables, index, opts, max_order, max_taps, scratch, filters, out):
+    """``brv_rir_bands_channels`` and ``brv_rir_bands_combine`` on the current stream; everything but ``opts`` on the
+    device of ``out``."""
+    hip.require_device(tables, index, scratch, filters, out)
+    bands_call('brv_rir_bands_channels', tables, index, len(index), len(tables), int(max_taps), opts.ctypes.data,
+               int(max_order), scratch, scratch.numel(), hip.stream())
+    bands_call('brv_rir_bands_combine', scratch, scratch.numel(), index, len(index), int(max_taps),
+               opts.ctypes.data, filters, filters.shape[1], out, out.numel(), hip.stream())
+
+
+def chunk_jobs(taps, channels, pad, scratch_bytes):
+    """``[(first, end), ...]``: consecutive jobs whose channel rows (``channels * (taps + pad)`` doubles each) stay
+    within ``scratch_bytes`` together; a job that alone is larger has a chunk of its own."""
+    chunks, first, used = [], 0, 0
+    for j, t in enumerate(taps):
+        need = 8*channels*(int(t) + pad)
+        if j > first and used + need > scratch_bytes:
+            chunks.append((first, j))
+            first, used = j, 0
+        used += need
+    chunks.append((first, len(taps)))
+    return chunks
+
+
+def _run_bands(geom, shape, out, fs, bands, ear_model, head_radius, window, max_order, c, scratch_bytes,
+               band_taps=None):
+    """Tables, upload and the launch pair, chunk by chunk, into the flat fp32 ``out`` on the device."""
+    max_order, scratch_bytes = int(max_order), int(scratch_bytes)
+    if scratch_bytes < 1:
+        raise ValueError('scratch_bytes must be positive')
+    filters, pad = band_filters(fs, bands, ear_model, head_radius, c, band_taps)
+    opts = band_opts(fs, bands, ear_model, head_radius, window, c, pad)
+    geom, shape = np.asarray(geom, dtype=np.float64), np.asarray(shape, dtype=np.int64)
+    channels = channels_of(opts)
+    with torch.cuda.device(out.device):
+        filters_d = torch.tensor(filters, device=out.device)         # (a copy: the cached array is read-only)
+        for first, end in chunk_jobs(shape[:, 0], channels, pad, scratch_bytes):
+            rows, index = build_band_tables(geom[first:end], shape[first:end], opts, max_order)
+            scratch = torch.empty(int(index[-1, 7]) + channels*(int(index[-1, 4]) + pad), dtype=torch.float64,
+                                  device=out.device)
+            launch_bands(torch.from_numpy(rows).to(out.device), torch.from_numpy(index).to(out.device), opts,
+                         max_order, index[:, 4].max(), scratch, filters_d, out)
+
+
+def _device(device):
+    device = torch.device(device)
+    if device.type != 'cuda':
+        raise RuntimeError(f'brever_amd kernels run on a ROCm device only; got {device} (there is no CPU fallback)')
+    return device
+
+
 def simulate_rirs(dims, beta, sources, receivers, orientations, patterns, taps, fs, window=None, max_order=-1,
-                  c=343.0, device='cuda'):
+                  c=343.0, device='cuda', scratch_bytes=1 << 30, band_taps=None, ear_model='pattern',
+                  head_radius=0.0875):
     """Responses of one room from every source to every receiver: ``sources`` (S, 3), ``receivers`` (R, 3),
     ``orientations`` (R, 3) unit vectors, ``patterns`` (R,) in [0, 1] (1 omni, 0.5 cardioid). Returns a
-    ``(S, R, taps)`` float32 tensor on ``device``."""
+    ``(S, R, taps)`` float32 tensor on ``device``. ``beta`` is (6,) or, by octave band, ``(K, 6)``: the responses of
+    the bands are then accumulated together and filtered (``band_filters``), with at most ``scratch_bytes`` of
+    channel rows on the device at a time. With ``ear_model='sphere'`` a receiver is the centre of a head of
+    ``head_radius``, its orientation the outward axis of the ear, and ``patterns`` is not used."""
     sources, receivers, orientations = (np.asarray(v, dtype=np.float64).reshape(-1, 3)
                                         for v in (sources, receivers, orientations))
     patterns = np.asarray(patterns, dtype=np.float64).reshape(-1)
     if not len(receivers) == len(orientations) == len(patterns):
         raise ValueError('one orientation and one pattern per receiver')
     taps = int(taps)
+    if np.ndim(beta) == 2 or ear_model != 'pattern':
+        geom = [_band_geom_row(dims, beta, s, receivers[i], orientations[i], patterns[i])
+                for s in sources for i in range(len(receivers))]
+        shape = [(taps, j*taps, 1) for j in range(len(geom))]
+        out = torch.zeros(len(geom)*taps, dtype=torch.float32, device=_device(device))
+        _run_bands(geom, shape, out, fs, len(np.reshape(beta, (-1, 6))), ear_model, head_radius, window, max_order, c,
+                   scratch_bytes, band_taps)
+        return out.view(len(sources), len(receivers), taps)
     geom = [_geom_row(dims, beta, s, receivers[i], orientations[i], patterns[i])
             for s in sources for i in range(len(receivers))]
     shape = [(taps, j*taps, 1) for j in range(len(geom))]
@@ -151,39 +371,75 @@ def simulate_rirs(dims, beta, sources, receivers, orientations, patterns, taps, 
     return out.view(len(sources), len(receivers), taps)
 
 
-def simulate_brirs(rooms, fs=16000, window=None, max_order=-1, c=343.0, device='cuda'):
-    """The BRIRs of every ``ShoeboxRoom`` of ``rooms`` in one launch: a list of rooms, each a list with one
-    ``(taps, 2)`` float32 array (left, right) per angle -- the ``brirs=`` argument of ``PoolMixtureMaker``."""
-    geom, shape, at = [], [], 0
-    for room in rooms:
-        ears, side = room.ears(), room.side()
-        for angle in room.angles:
-            source = room.source(angle)
-            for e in range(2):
-                geom.append(_geom_row(room.dims, room.beta, source, ears[e], side if e == 0 else -side,
-                                      room.ear_pattern))
-                shape.append((room.taps, at + e, 2))
-            at += 2*room.taps
-    if not geom:
-        return []
-    flat = _run(np.array(geom), np.array(shape), fs, window, max_order, c, device).cpu().numpy()
-    out, at = [], 0
-    for room in rooms:
-        out.append([flat[at + 2*room.taps*i:at + 2*room.taps*(i + 1)].reshape(room.taps, 2)
-                    for i in range(len(room.angles))])
-        at += 2*room.taps*len(room.angles)
+def simulate_brirs(rooms, fs=16000, window=None, max_order=-1, c=343.0, device='cuda', scratch_bytes=1 << 30):
+    """The BRIRs of every ``ShoeboxRoom`` of ``rooms``: a list of rooms, each a list with one ``(taps, 2)`` float32
+    array (left, right) per angle -- the ``brirs=`` argument of ``PoolMixtureMaker``. The rooms with one coefficient
+    per wall and ``ear_model='pattern'`` take one launch of ``brv_rir_simulate``; the others are grouped by
+    ``(bands, ear_model, head_radius)`` and take one launch pair of the band entry points per group and per chunk of
+    jobs whose channel rows fit ``scratch_bytes``."""
+    rooms = list(rooms)
+    plain, groups = [], {}
+    for i, room in enumerate(rooms):
+        if room.bands() == 0 and room.ear_model == 'pattern':
+            plain.append(i)
+        else:
+            groups.setdefault((max(room.bands(), 1), room.ear_model, room.head_radius), []).append(i)
+    out = [None]*len(rooms)
+
+    def jobs(members, row):
+        """``geom``, ``shape`` and the output length of the rooms ``members``: per angle two jobs, interleaved."""
+        geom, shape, at = [], [], 0
+        for i in members:
+            room = rooms[i]
+            ears, side = room.ears(), room.side()
+            for angle in room.angles:
+                source = room.source(angle)
+                for e in range(2):
+                    # the sphere's receiver is the head's centre, and the ear is where its axis leaves the sphere
+                    geom.append(row(room.dims, room.beta, source, room.head if room.ear_model == 'sphere' else ears[e],
+                                    side if e == 0 else -side, room.ear_pattern))
+                    shape.append((room.taps, at + e, 2))
+                at += 2*room.taps
+        return np.array(geom), np.array(shape), at
+
+    def split(members, flat):
+        at = 0
+        for i in members:
+            room = rooms[i]
+            out[i] = [flat[at + 2*room.taps*k:at + 2*room.taps*(k + 1)].reshape(room.taps, 2)
+                      for k in range(len(room.angles))]
+            at += 2*room.taps*len(room.angles)
+
+    if plain:
+        geom, shape, _ = jobs(plain, _geom_row)
+        split(plain, _run(geom, shape, fs, window, max_order, c, device).cpu().numpy())
+    for (bands, ear_model, head_radius), members in groups.items():
+        geom, shape, length = jobs(members, _band_geom_row)
+        flat = torch.zeros(length, dtype=torch.float32, device=_device(device))
+        _run_bands(geom, shape, flat, fs, bands, ear_model, head_radius, window, max_order, c, scratch_bytes)
+        split(members, flat.cpu().numpy())
     return out
 
 
 def random_rooms(n, seed, dims=((3, 3, 2.4), (10, 8, 4)), rt60=(0.2, 0.8), distance=(0.5, 3.0),
-                 angles=range(-90, 91, 10), margin=0.3, taps=None, fs=16000, ear_pattern=0.75, head_radius=0.0875):
+                 angles=range(-90, 91, 10), margin=0.3, taps=None, fs=16000, ear_pattern=0.75, head_radius=0.0875,
+                 bands=0, band_tilt=(0.0, 0.25), ear_model='pattern'):
     """``n`` rooms drawn from ``np.random.default_rng([seed])``, a function of the arguments only. Per room, in this
     order: the three dimensions uniformly between ``dims[0]`` and ``dims[1]``; the source distance uniformly in
     ``distance``, capped so that a circle of that radius plus ``head_radius + margin`` fits the floor plan; the
     head's centre uniformly where that circle stays inside (no rejection); the ears' height uniformly in
     ``[1.0, min(1.8, Lz - margin)]``; the yaw uniformly in [0, 2 pi); ``rt60`` uniformly in its range, raised to 1.01
-    times the least that Sabine's formula allows the room. ``taps`` defaults to ``ceil(rt60 fs)``."""
+    times the least that Sabine's formula allows the room. ``taps`` defaults to ``ceil(rt60 fs)``.
+
+    With ``bands = K > 0`` the walls get one coefficient per octave band: a tilt ``u`` per room, uniform in
+    ``band_tilt`` from a generator of its own (``np.random.default_rng([seed, 1])``, so that nothing above changes),
+    ``rt60_k = max(rt60 2^(-u (k - 2)), 1.01 min_rt60)`` (the drawn ``rt60`` holds at 500 Hz and falls by ``u``
+    octaves per octave) and all six walls of a band from Sabine's formula. ``ear_model`` goes to every room."""
     rng = np.random.default_rng([int(seed)])
+    tilt_rng = np.random.default_rng([int(seed), 1])
+    bands = int(bands)
+    if not 0 <= bands <= MAX_BANDS:
+        raise ValueError(f'requires 0 <= bands <= {MAX_BANDS}')
     lo, hi = np.asarray(dims[0], dtype=np.float64), np.asarray(dims[1], dtype=np.float64)
     rooms = []
     for _ in range(int(n)):
@@ -199,9 +455,16 @@ def random_rooms(n, seed, dims=((3, 3, 2.4), (10, 8, 4)), rt60=(0.2, 0.8), dista
         hz = rng.uniform(1.0, min(1.8, L[2] - margin))
         yaw = rng.uniform(0.0, 2.0*math.pi)
         t60 = max(float(rng.uniform(rt60[0], rt60[1])), 1.01*min_rt60(L))
-        rooms.append(ShoeboxRoom(L, (beta_from_rt60(L, t60),)*6, (hx, hy, hz), yaw, rho, angles,
-                                 math.ceil(t60*fs) if taps is None else taps, ear_pattern, head_radius))
+        beta = (beta_from_rt60(L, t60),)*6
+        if bands:
+            u = float(tilt_rng.uniform(band_tilt[0], band_tilt[1]))
+            t60_bands = tuple(max(t60*2.0**(-u*(k - 2)), 1.01*min_rt60(L)) for k in range(bands))
+            beta = tuple((b,)*6 for b in beta_from_rt60(L, t60_bands))
+        rooms.append(ShoeboxRoom(L, beta, (hx, hy, hz), yaw, rho, angles,
+                                 math.ceil(t60*fs) if taps is None else taps, ear_pattern, head_radius, ear_model))
         rooms[-1].rt60 = t60
+        if bands:
+            rooms[-1].rt60_bands = t60_bands
     return rooms
 
 

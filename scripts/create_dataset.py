@@ -67,6 +67,12 @@ def parse(argv=None):
     p.add_argument('--room_distance', type=float, nargs=2, default=[0.5, 3.0], metavar=('LO', 'HI'))
     p.add_argument('--room_angles', type=float, nargs='+', default=list(range(-90, 91, 10)), metavar='A')
     p.add_argument('--room_taps', type=int, default=None, help='taps of every BRIR; default ceil(rt60 fs) per room')
+    p.add_argument('--room_bands', type=int, default=0, metavar='K',
+                   help='octave bands of the wall coefficients from 125 Hz upwards; 0: one coefficient per wall')
+    p.add_argument('--room_band_tilt', type=float, nargs=2, default=[0.0, 0.25], metavar=('LO', 'HI'),
+                   help='with --room_bands: rt60 falls by 2^-u per octave, u uniform in this range per room')
+    p.add_argument('--room_ear_model', choices=['pattern', 'sphere'], default='pattern',
+                   help='an ear is a first-order receiver, or a point on a rigid sphere (head shadow, Woodworth delay)')
     return p.parse_args(argv)
 
 
@@ -78,7 +84,8 @@ def simulated_pools(args):
         raise SystemExit('--simulate_rooms must be at least 1')
     speech, noises, _ = PoolMixtureMaker._load(args.pool)
     rooms = rir.random_rooms(args.simulate_rooms, args.room_seed, rt60=args.room_rt60, distance=args.room_distance,
-                             angles=args.room_angles, taps=args.room_taps, fs=args.fs)
+                             angles=args.room_angles, taps=args.room_taps, fs=args.fs, bands=args.room_bands,
+                             band_tilt=args.room_band_tilt, ear_model=args.room_ear_model)
     return dict(speech=speech, noises=noises, brirs=rir.simulate_brirs(rooms, fs=args.fs, device=args.device))
 
 

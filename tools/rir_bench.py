@@ -1,6 +1,7 @@
 """Time of the shoebox image-source simulator (brever_amd/rir.py).
 
     python tools/rir_bench.py [--shapes 100x19x8000 2x3x800] [--fs 16000] [--seed 0] [--repeats 3]
+                              [--bands K] [--ear_model pattern|sphere] [--scratch_bytes N]
 
 One JSON line per shape ROOMSxANGLESxTAPS: `random_rooms(ROOMS, seed, angles=ANGLES equally spaced, taps=TAPS)`,
 two ears per angle. `value` is the median over `--repeats` launches of brv_rir_simulate alone (a host clock around a
@@ -14,7 +15,15 @@ operations (a subtraction, two FMAs, two products, a reciprocal, an addition); `
 that against 39.3 T fp64 vector instructions per second (the 78.6 TFLOP/s of the datasheet), and is therefore a
 floor's share, not a utilisation: the kernel's reciprocal alone is five instructions, and selects, compares and LDS
 reads come on top. `tile_images` gives the median and the largest number of images per tile of the first job,
-which is what makes the last tiles of a long response the expensive ones."""
+which is what makes the last tiles of a long response the expensive ones.
+
+With `--bands K` a second line per shape measures the band entry points on the same rooms with
+`bands=K` and `--ear_model`, in the same run: `tile_ms` is brv_rir_bands_channels alone and `combine_ms`
+brv_rir_bands_combine alone (each the median over `--repeats` launches after a warm-up, summed over the chunks of
+jobs whose channel rows fit `--scratch_bytes`), `end_to_end_ms` one whole `simulate_brirs` call.
+`tile_over_single_band` is `tile_ms` over the `value` of the first line, to be set against `channels`: the point of
+the multi-channel kernel is that C channels cost less than C launches. `combine_share_of_fp64_fma_peak` sets the
+`jobs * taps * C * M_f` fused multiply-adds of the filters against 39.3 T per second."""
 import argparse
 import json
 import os
@@ -66,12 +75,82 @@ def count_job(rows, ix, opts, tiles=False):
     return int(hit.sum()), int(n.sum()), per_tile
 
 
+def timed(fn, repeats):
+    """Median and least seconds of ``repeats`` calls of ``fn`` after one warm-up call, each ending in a synchronise."""
+    times = []
+    for _ in range(repeats + 1):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        times.append(time.perf_counter() - t0)
+    return float(np.median(times[1:])), float(min(times[1:]))
+
+
+def bench_bands(args, rooms, dev, single_band_seconds):
+    """The JSON line of the band entry points for ``rooms`` (all of one group)."""
+    room = rooms[0]
+    sphere = room.ear_model == 'sphere'
+    geom, shape, at = [], [], 0
+    for r in rooms:
+        ears, side = r.ears(), r.side()
+        for angle in r.angles:
+            for e in range(2):
+                geom.append(rir._band_geom_row(r.dims, r.beta, r.source(angle), r.head if sphere else ears[e],
+                                               side if e == 0 else -side, r.ear_pattern))
+                shape.append((r.taps, at + e, 2))
+            at += 2*r.taps
+    geom, shape = np.array(geom), np.array(shape)
+    filters, pad = rir.band_filters(args.fs, args.bands, room.ear_model, room.head_radius)
+    opts = rir.band_opts(args.fs, args.bands, room.ear_model, room.head_radius, pad=pad)
+    channels = rir.channels_of(opts)
+    filters_d = torch.tensor(filters, device=dev)
+    out = torch.zeros(at, dtype=torch.float32, device=dev)
+    chunks = rir.chunk_jobs(shape[:, 0], channels, pad, args.scratch_bytes)
+    tile = combine = tile_min = combine_min = tables_s = 0.0
+    table_rows = 0
+    for first, end in chunks:
+        t0 = time.perf_counter()
+        rows, index = rir.build_band_tables(geom[first:end], shape[first:end], opts)
+        tables_s += time.perf_counter() - t0
+        table_rows += len(rows)
+        tables, index_d = torch.from_numpy(rows).to(dev), torch.from_numpy(index).to(dev)
+        scratch = torch.empty(int(index[-1, 7]) + channels*(int(index[-1, 4]) + pad), dtype=torch.float64, device=dev)
+        max_taps = int(index[:, 4].max())
+        median, least = timed(lambda: rir.bands_call(
+            'brv_rir_bands_channels', tables, index_d, len(index), len(tables), max_taps, opts.ctypes.data, -1,
+            scratch, scratch.numel(), rir.hip.stream()), args.repeats)
+        tile, tile_min = tile + median, tile_min + least
+        median, least = timed(lambda: rir.bands_call(
+            'brv_rir_bands_combine', scratch, scratch.numel(), index_d, len(index), max_taps, opts.ctypes.data,
+            filters_d, filters.shape[1], out, out.numel(), rir.hip.stream()), args.repeats)
+        combine, combine_min = combine + median, combine_min + least
+        del tables, index_d, scratch
+    t0 = time.perf_counter()
+    brirs = rir.simulate_brirs(rooms, fs=args.fs, device=dev, scratch_bytes=args.scratch_bytes)
+    end_to_end_ms = 1e3*(time.perf_counter() - t0)
+    assert np.array_equal(brirs[0][0].reshape(-1), out[:2*room.taps].cpu().numpy())
+    fmas = float(shape[:, 0].sum())*channels*filters.shape[1]
+    return dict(metric='rir_bands_ms', value=1e3*(tile + combine), tile_ms=1e3*tile, tile_min_ms=1e3*tile_min,
+                combine_ms=1e3*combine, combine_min_ms=1e3*combine_min, end_to_end_ms=end_to_end_ms,
+                tables_ms=1e3*tables_s, table_rows=table_rows, repeats=args.repeats, rooms=len(rooms),
+                angles=len(room.angles), taps=room.taps, jobs=len(geom), fs=args.fs, window=float(opts[2]),
+                bands=args.bands, ear_model=room.ear_model, channels=channels, filter_taps=filters.shape[1],
+                pad=pad, chunks=len(chunks), scratch_bytes=args.scratch_bytes,
+                single_band_ms=1e3*single_band_seconds, tile_over_single_band=tile/single_band_seconds,
+                combine_fmas=fmas, combine_share_of_fp64_fma_peak=fmas/combine/FP64_INSTRUCTIONS_PER_SECOND,
+                timing='host clock around one launch ending in a device synchronise, median, summed over chunks')
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--shapes', nargs='+', default=['100x19x8000', '2x3x800'])
     ap.add_argument('--fs', type=int, default=16000)
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--repeats', type=int, default=3)
+    ap.add_argument('--bands', type=int, default=0, help='also measure the band entry points with this many bands')
+    ap.add_argument('--ear_model', choices=['pattern', 'sphere'], default='pattern')
+    ap.add_argument('--scratch_bytes', type=int, default=1 << 30)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('rir_bench needs a ROCm device: a time from anywhere else says nothing')
@@ -115,6 +194,11 @@ def main():
                     timing='host clock around one launch ending in a device synchronise, median',
                     counts='exact for the first job of every room, times the jobs of the room')
         print(json.dumps(line), flush=True)
+        if args.bands:
+            del tables, index_d, out
+            banded = rir.random_rooms(n_rooms, args.seed, angles=angles, taps=taps, fs=args.fs, bands=args.bands,
+                                      ear_model=args.ear_model)
+            print(json.dumps(bench_bands(args, banded, dev, seconds)), flush=True)
 
 
 if __name__ == '__main__':
