@@ -20,7 +20,8 @@
 // Entry positions, the flush points and the slices of the waves are functions of the job's own tables and of the
 // tile, nothing else: no atomics, bitwise repeatable, a job alone equals the job in a batch.
 //
-// rir_bands.cuh, included at the end, adds the band entry points (octave-band walls, a spherical-head ear).
+// rir_bands.cuh, included at the end, adds the band entry points (octave-band walls, a spherical-head ear), and
+// rir_hrir.cuh after it the measured-ear entry points (an HRIR set as the ear).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -371,6 +372,9 @@ int brv_rir_simulate(const double* tables, const int64_t* index, int64_t n_jobs,
 
 // the band entry points (include/rir/brever_rir_bands.h)
 #include "rir_bands.cuh"
+
+// the measured-ear entry points (include/rir/brever_rir_hrir.h)
+#include "rir_hrir.cuh"
 
 // the library's last-error message and its two status exports (../status.h)
 BRV_DEFINE_STATUS(brv_rir_version, brv_rir_last_error)

@@ -7,6 +7,10 @@ image, but the library it wraps is (``libhdf5`` + ``libhdf5_hl`` of the conda tr
 the handful of entry points that layout needs -- files written here are read back by ``h5py`` /
 ``h5dump`` / ``h5ls`` like the reference's (tests/test_scripts.py checks them with ``h5dump``).
 
+The read side (a file opened read-only, a dataset as an array, a string attribute of fixed or variable length) is
+what ``brever_amd.rir.load_sofa`` needs of a SOFA file, which is HDF5 written by netCDF; ``write_attr`` exists so
+that the tests can write one.
+
 Host-side I/O, not on the compute path. ``available()`` is False when the shared libraries cannot be
 loaded; ``scripts/test_model.py`` then falls back to ``scores.npz`` as before.
 """
@@ -28,6 +32,8 @@ H5F_ACC_RDONLY, H5F_ACC_RDWR, H5F_ACC_TRUNC = 0, 1, 2
 H5P_DEFAULT, H5S_ALL = 0, 0
 H5T_VARIABLE = ctypes.c_size_t(-1).value
 H5T_CSET_UTF8 = 1
+H5T_STRING = 3                                   # H5T_class_t
+H5S_SCALAR = 0                                   # H5S_class_t
 
 
 def _find(name):
@@ -77,6 +83,15 @@ def _load():
             'H5Tcopy': (_hid, [_hid]), 'H5Tset_size': (_herr, [_hid, ctypes.c_size_t]),
             'H5Tset_cset': (_herr, [_hid, ctypes.c_int]), 'H5Tclose': (_herr, [_hid]),
             'H5Lexists': (ctypes.c_int, [_hid, ctypes.c_char_p, _hid]),
+            'H5Screate': (_hid, [ctypes.c_int]),
+            'H5Tis_variable_str': (ctypes.c_int, [_hid]), 'H5Tget_size': (ctypes.c_size_t, [_hid]),
+            'H5Tget_class': (ctypes.c_int, [_hid]),
+            'H5Aexists_by_name': (ctypes.c_int, [_hid, ctypes.c_char_p, ctypes.c_char_p, _hid]),
+            'H5Aopen_by_name': (_hid, [_hid, ctypes.c_char_p, ctypes.c_char_p, _hid, _hid]),
+            'H5Acreate_by_name': (_hid, [_hid, ctypes.c_char_p, ctypes.c_char_p, _hid, _hid, _hid, _hid, _hid]),
+            'H5Aget_type': (_hid, [_hid]), 'H5Aclose': (_herr, [_hid]),
+            'H5Aread': (_herr, [_hid, _hid, ctypes.c_void_p]), 'H5Awrite': (_herr, [_hid, _hid, ctypes.c_void_p]),
+            'H5free_memory': (_herr, [ctypes.c_void_p]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(lib, name)
@@ -211,7 +226,55 @@ class File:
         finally:
             _lib.H5Dclose(dset)
 
+    def write_attr(self, key, name, text, variable=False):
+        """Scalar string attribute ``name`` of the object ``key`` (``'/'``: the file): a fixed-length string as
+        netCDF writes them, or a variable-length one as ``h5py`` does."""
+        raw = text.encode()
+        t = self._vlen_str() if variable else _check(_lib.H5Tcopy(_global('H5T_C_S1_g')), 'H5Tcopy')
+        if not variable:
+            _lib.H5Tset_size(t, max(len(raw), 1))
+        space = _check(_lib.H5Screate(H5S_SCALAR), 'H5Screate')
+        attr = _lib.H5Acreate_by_name(self.fid, key.encode(), name.encode(), t, space, H5P_DEFAULT, H5P_DEFAULT,
+                                      H5P_DEFAULT)
+        status = -1
+        if attr >= 0:
+            buf = (ctypes.c_char_p*1)(raw) if variable else ctypes.create_string_buffer(raw, max(len(raw), 1))
+            status = _lib.H5Awrite(attr, t, ctypes.cast(buf, ctypes.c_void_p))
+            _lib.H5Aclose(attr)
+        _lib.H5Sclose(space)
+        _lib.H5Tclose(t)
+        _check(status, f'writing the attribute {name} of {key}')
+
     # -- reading ---------------------------------------------------------------------------------
+    def read_attr(self, key, name):
+        """The string attribute ``name`` of the object ``key`` (``'/'``: the file), fixed or variable length, without
+        its padding; ``None`` if the object has no such attribute. ``ValueError`` if it is not a string."""
+        if key != '/' and key not in self:
+            return None
+        if _lib.H5Aexists_by_name(self.fid, key.encode(), name.encode(), H5P_DEFAULT) <= 0:
+            return None
+        attr = _check(_lib.H5Aopen_by_name(self.fid, key.encode(), name.encode(), H5P_DEFAULT, H5P_DEFAULT),
+                      f'opening the attribute {name} of {key}')
+        t = _lib.H5Aget_type(attr)                       # read in the file's own type: no conversion to fail
+        try:
+            if t < 0 or _lib.H5Tget_class(t) != H5T_STRING:
+                raise ValueError(f'the attribute {name} of {key} is not a string')
+            if _lib.H5Tis_variable_str(t) > 0:
+                buf = (ctypes.c_void_p*1)()
+                _check(_lib.H5Aread(attr, t, ctypes.cast(buf, ctypes.c_void_p)), f'reading the attribute {name}')
+                raw = ctypes.string_at(buf[0]) if buf[0] else b''
+                if buf[0]:
+                    _lib.H5free_memory(buf[0])
+            else:
+                buf = ctypes.create_string_buffer(int(_lib.H5Tget_size(t)) + 1)
+                _check(_lib.H5Aread(attr, t, ctypes.cast(buf, ctypes.c_void_p)), f'reading the attribute {name}')
+                raw = buf.raw[:-1].split(b'\0')[0]
+        finally:
+            if t >= 0:
+                _lib.H5Tclose(t)
+            _lib.H5Aclose(attr)
+        return raw.decode(errors='replace').rstrip(' ')
+
     def _shape(self, dset):
         space = _lib.H5Dget_space(dset)
         n = _lib.H5Sget_simple_extent_ndims(space)

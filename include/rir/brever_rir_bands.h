@@ -53,8 +53,8 @@
  *                               in channel order and stored as fp32 to out[out_offset + t out_stride].
  *
  * Every sum has a fixed order that depends on the job alone: no atomics, bitwise repeatable, a job gives the same
- * bits alone as in a batch. Out of scope: air absorption, measured HRTFs and pinna cues, source directivity, torso
- * effects, other room shapes.
+ * bits alone as in a batch. Out of scope: air absorption, source directivity, torso effects, other room shapes; a
+ * measured ear (HRTFs, pinna cues) is brever_rir_hrir.h.
  *
  * Conventions: those of brever_rir.h. geom, shape, opts, rows and index of the host steps are HOST pointers; tables,
  * index, scratch, filters and out of the two launches are device pointers borrowed from the caller (opts stays a host

@@ -71,9 +71,16 @@ def parse(argv=None):
                    help='octave bands of the wall coefficients from 125 Hz upwards; 0: one coefficient per wall')
     p.add_argument('--room_band_tilt', type=float, nargs=2, default=[0.0, 0.25], metavar=('LO', 'HI'),
                    help='with --room_bands: rt60 falls by 2^-u per octave, u uniform in this range per room')
-    p.add_argument('--room_ear_model', choices=['pattern', 'sphere'], default='pattern',
-                   help='an ear is a first-order receiver, or a point on a rigid sphere (head shadow, Woodworth delay)')
-    return p.parse_args(argv)
+    p.add_argument('--room_ear_model', choices=['pattern', 'sphere', 'hrir'], default='pattern',
+                   help='an ear is a first-order receiver, a point on a rigid sphere (head shadow, Woodworth delay), '
+                        'or the measured pair of --room_hrirs')
+    p.add_argument('--room_hrirs', default=None, metavar='FILE',
+                   help='with --room_ear_model hrir: the measured HRIR set, a SimpleFreeFieldHRIR .sofa file or the '
+                        '.npz of brever_amd.rir.HrirSet.save')
+    args = p.parse_args(argv)
+    if (args.room_ear_model == 'hrir') != (args.room_hrirs is not None):
+        p.error('--room_ear_model hrir and --room_hrirs FILE go together')
+    return args
 
 
 def simulated_pools(args):
@@ -85,7 +92,8 @@ def simulated_pools(args):
     speech, noises, _ = PoolMixtureMaker._load(args.pool)
     rooms = rir.random_rooms(args.simulate_rooms, args.room_seed, rt60=args.room_rt60, distance=args.room_distance,
                              angles=args.room_angles, taps=args.room_taps, fs=args.fs, bands=args.room_bands,
-                             band_tilt=args.room_band_tilt, ear_model=args.room_ear_model)
+                             band_tilt=args.room_band_tilt, ear_model=args.room_ear_model,
+                             hrirs=rir.load_hrirs(args.room_hrirs) if args.room_hrirs else None)
     return dict(speech=speech, noises=noises, brirs=rir.simulate_brirs(rooms, fs=args.fs, device=args.device))
 
 

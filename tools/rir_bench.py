@@ -1,7 +1,7 @@
 """Time of the shoebox image-source simulator (brever_amd/rir.py).
 
     python tools/rir_bench.py [--shapes 100x19x8000 2x3x800] [--fs 16000] [--seed 0] [--repeats 3]
-                              [--bands K] [--ear_model pattern|sphere] [--scratch_bytes N]
+                              [--bands K] [--ear_model pattern|sphere] [--scratch_bytes N] [--hrir D T_H]
 
 One JSON line per shape ROOMSxANGLESxTAPS: `random_rooms(ROOMS, seed, angles=ANGLES equally spaced, taps=TAPS)`,
 two ears per angle. `value` is the median over `--repeats` launches of brv_rir_simulate alone (a host clock around a
@@ -23,7 +23,15 @@ brv_rir_bands_combine alone (each the median over `--repeats` launches after a w
 jobs whose channel rows fit `--scratch_bytes`), `end_to_end_ms` one whole `simulate_brirs` call.
 `tile_over_single_band` is `tile_ms` over the `value` of the first line, to be set against `channels`: the point of
 the multi-channel kernel is that C channels cost less than C launches. `combine_share_of_fp64_fma_peak` sets the
-`jobs * taps * C * M_f` fused multiply-adds of the filters against 39.3 T per second."""
+`jobs * taps * C * M_f` fused multiply-adds of the filters against 39.3 T per second.
+
+With `--hrir D T_H` two more lines per shape measure the measured-ear entry points on the same rooms
+with one coefficient per wall (K = 1) and with `bands=K`, in the same run, for a synthetic set of `D` directions (a
+Fibonacci sphere) and `T_H` taps: `channels_ms` is brv_rir_hrir_channels alone (its clearing of the direction scratch
+included), `fold_ms` brv_rir_hrir_fold alone and `combine_ms` brv_rir_bands_combine alone, each the median over
+`--repeats` launches after a warm-up, summed over the chunks. One job is one (room, angle) and gives both ears.
+`fold_fmas` counts `jobs * K * (taps + pad) * D * 2 * n_filter`, what the fold would do if it passed over nothing;
+`*_over_bands_*` set a launch against the band line of the same run (`--bands` is required)."""
 import argparse
 import json
 import os
@@ -142,6 +150,95 @@ def bench_bands(args, rooms, dev, single_band_seconds):
                 timing='host clock around one launch ending in a device synchronise, median, summed over chunks')
 
 
+def synthetic_set(D, taps_h, fs, seed):
+    """``D`` directions on a Fibonacci sphere turned by a seeded angle, seeded normal responses under a decaying
+    envelope: the cost of the kernels depends on ``D`` and ``taps_h`` only."""
+    rng = np.random.default_rng([seed, D, taps_h])
+    i = np.arange(D) + 0.5
+    z = 1.0 - 2.0*i/D
+    phi = i*np.pi*(3.0 - np.sqrt(5.0)) + rng.uniform(0.0, 2.0*np.pi)
+    rho = np.sqrt(1.0 - z*z)
+    hrirs = rng.standard_normal((D, 2, taps_h))*np.exp(-np.arange(taps_h)/(taps_h/4.0))
+    return rir.HrirSet(np.stack([rho*np.cos(phi), rho*np.sin(phi), z], axis=1), hrirs, fs)
+
+
+def bench_hrir(args, rooms, dev, bands_line):
+    """The JSON line of the measured-ear entry points for ``rooms`` (all of one group)."""
+    room = rooms[0]
+    hrirs, K = room.hrirs, max(room.bands(), 1)
+    geom, shape, at = [], [], 0
+    for r in rooms:
+        for angle in r.angles:
+            geom.append(rir._hrir_geom_row(r.dims, r.beta, r.source(angle), r.head, r.front(), r.side()))
+            shape.append((r.taps, at, 2, 1))
+            at += 2*r.taps
+    geom, shape = np.array(geom), np.array(shape)
+    filters, pad = rir.band_filters(args.fs, K)
+    opts = rir.hrir_opts(args.fs, K, hrirs, pad=pad)
+    combine_opts = rir.band_opts(args.fs, K, 'pattern', 0.0, pad=pad)
+    D = len(hrirs)
+    filters_d = torch.tensor(filters, device=dev)
+    directions_d = torch.tensor(hrirs.directions, device=dev)
+    responses_d = torch.from_numpy(rir.padded_hrirs(hrirs)).to(dev)
+    out = torch.zeros(at, dtype=torch.float32, device=dev)
+    chunks = rir.chunk_jobs(shape[:, 0], K*(D + 2), pad, args.scratch_bytes)
+    sums = dict(channels=[0.0, 0.0], fold=[0.0, 0.0], combine=[0.0, 0.0])
+    tables_s, table_rows = 0.0, 0
+    for first, end in chunks:
+        t0 = time.perf_counter()
+        rows, index, ear_index = rir.build_hrir_tables(geom[first:end], shape[first:end], opts, hrirs.directions)
+        tables_s += time.perf_counter() - t0
+        table_rows += len(rows)
+        tables, index_d, ear_d = (torch.from_numpy(v).to(dev) for v in (rows, index, ear_index))
+        last = int(index[-1, 4]) + pad
+        dirs = torch.empty(int(index[-1, 5]) + K*D*last, dtype=torch.float64, device=dev)
+        fold = torch.empty(int(index[-1, 7]) + 2*K*last, dtype=torch.float64, device=dev)
+        max_taps = int(index[:, 4].max())
+        launches = dict(
+            channels=lambda: rir.hrir_call(
+                'brv_rir_hrir_channels', tables, index_d, len(index), len(tables), max_taps, opts.ctypes.data, -1,
+                directions_d, dirs, dirs.numel(), rir.hip.stream()),
+            fold=lambda: rir.hrir_call(
+                'brv_rir_hrir_fold', dirs, dirs.numel(), index_d, len(index), max_taps, opts.ctypes.data, responses_d,
+                responses_d.shape[2], fold, fold.numel(), rir.hip.stream()),
+            combine=lambda: rir.bands_call(
+                'brv_rir_bands_combine', fold, fold.numel(), ear_d, len(ear_d), max_taps, combine_opts.ctypes.data,
+                filters_d, filters.shape[1], out, out.numel(), rir.hip.stream()))
+        for name, fn in launches.items():
+            median, least = timed(fn, args.repeats)
+            sums[name][0] += median
+            sums[name][1] += least
+        del tables, index_d, ear_d, dirs, fold
+    t0 = time.perf_counter()
+    brirs = rir.simulate_brirs(rooms, fs=args.fs, device=dev, scratch_bytes=args.scratch_bytes)
+    end_to_end_ms = 1e3*(time.perf_counter() - t0)
+    assert np.array_equal(brirs[0][0].reshape(-1), out[:2*room.taps].cpu().numpy())
+    rows_taps = float((shape[:, 0] + pad).sum())
+    fold_fmas = rows_taps*K*D*2*responses_d.shape[2]
+    combine_fmas = 2.0*float(shape[:, 0].sum())*K*filters.shape[1]
+    line = dict(metric='rir_hrir_ms', value=1e3*sum(v[0] for v in sums.values()),
+                channels_ms=1e3*sums['channels'][0], channels_min_ms=1e3*sums['channels'][1],
+                fold_ms=1e3*sums['fold'][0], fold_min_ms=1e3*sums['fold'][1],
+                combine_ms=1e3*sums['combine'][0], combine_min_ms=1e3*sums['combine'][1],
+                dominant=max(sums, key=lambda k: sums[k][0]), end_to_end_ms=end_to_end_ms, tables_ms=1e3*tables_s,
+                table_rows=table_rows, repeats=args.repeats, rooms=len(rooms), angles=len(room.angles),
+                taps=room.taps, jobs=len(geom), fs=args.fs, window=float(opts[2]), bands=K, directions=D,
+                hrir_taps=hrirs.taps, hrir_filter_taps=int(responses_d.shape[2]), filter_taps=filters.shape[1],
+                pad=pad, chunks=len(chunks), scratch_bytes=args.scratch_bytes,
+                direction_scratch_bytes_per_job=8*K*D*(room.taps + pad), fold_fmas=fold_fmas,
+                fold_share_of_fp64_fma_peak=fold_fmas/sums['fold'][0]/FP64_INSTRUCTIONS_PER_SECOND,
+                combine_fmas=combine_fmas,
+                timing='host clock around one launch ending in a device synchronise, median, summed over chunks')
+    if bands_line is not None:
+        line.update(bands_tile_ms=bands_line['tile_ms'], bands_combine_ms=bands_line['combine_ms'],
+                    bands_pair_ms=bands_line['value'],
+                    channels_over_bands_tile=line['channels_ms']/bands_line['tile_ms'],
+                    fold_over_bands_pair=line['fold_ms']/bands_line['value'],
+                    combine_over_bands_combine=line['combine_ms']/bands_line['combine_ms'],
+                    value_over_bands_pair=line['value']/bands_line['value'])
+    return line
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--shapes', nargs='+', default=['100x19x8000', '2x3x800'])
@@ -151,7 +248,11 @@ def main():
     ap.add_argument('--bands', type=int, default=0, help='also measure the band entry points with this many bands')
     ap.add_argument('--ear_model', choices=['pattern', 'sphere'], default='pattern')
     ap.add_argument('--scratch_bytes', type=int, default=1 << 30)
+    ap.add_argument('--hrir', type=int, nargs=2, default=None, metavar=('D', 'T_H'),
+                    help='also measure the measured-ear entry points with a synthetic set of D directions and T_H taps')
     args = ap.parse_args()
+    if args.hrir and not args.bands:
+        ap.error('--hrir is measured against the band entry points of the same run: give --bands K as well')
     if not torch.cuda.is_available():
         raise SystemExit('rir_bench needs a ROCm device: a time from anywhere else says nothing')
     dev = torch.device('cuda:0')
@@ -198,7 +299,15 @@ def main():
             del tables, index_d, out
             banded = rir.random_rooms(n_rooms, args.seed, angles=angles, taps=taps, fs=args.fs, bands=args.bands,
                                       ear_model=args.ear_model)
-            print(json.dumps(bench_bands(args, banded, dev, seconds)), flush=True)
+            bands_line = bench_bands(args, banded, dev, seconds)
+            print(json.dumps(bands_line), flush=True)
+            if args.hrir:
+                del banded
+                hrirs = synthetic_set(args.hrir[0], args.hrir[1], args.fs, args.seed)
+                for bands in (0, args.bands):
+                    measured = rir.random_rooms(n_rooms, args.seed, angles=angles, taps=taps, fs=args.fs, bands=bands,
+                                                ear_model='hrir', hrirs=hrirs)
+                    print(json.dumps(bench_hrir(args, measured, dev, bands_line)), flush=True)
 
 
 if __name__ == '__main__':
