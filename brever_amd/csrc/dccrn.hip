@@ -560,9 +560,17 @@ __global__ __launch_bounds__(512) void lstm_fwd_quad_kernel(const float* gates_i
 #pragma unroll
     for (int i = 0; i < 32; i += 4) {
       const float4 hv = *reinterpret_cast<const float4*>(hb + i);
+      // fused multiply-adds spelled out: left to the compiler, the HAS_ACT instantiation got some of these products
+      // as packed multiplies and packed adds (unfused) and the other one did not, so that training and inference
+      // forward passes differed in the last bit of a few hidden states
 #pragma unroll
-      for (int g = 0; g < 4; ++g)
-        p[g] += w[g][i]*hv.x + w[g][i + 1]*hv.y + w[g][i + 2]*hv.z + w[g][i + 3]*hv.w;
+      for (int g = 0; g < 4; ++g) {
+        float s = w[g][i]*hv.x;
+        s = __builtin_fmaf(w[g][i + 1], hv.y, s);
+        s = __builtin_fmaf(w[g][i + 2], hv.z, s);
+        s = __builtin_fmaf(w[g][i + 3], hv.w, s);
+        p[g] += s;
+      }
     }
 #pragma unroll
     for (int g = 0; g < 4; ++g) p[g] = quad_sum(p[g] + (q == g ? gin : 0.f));

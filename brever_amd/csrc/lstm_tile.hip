@@ -669,6 +669,12 @@ extern "C" {
 
 int brv_lstm_tile_supported(int64_t H) { return H == LH ? 1 : 0; }
 
+// the ONE copy of the rule: brv_lstm_tile_forward / _backward launch what this returns
+int brv_lstm_tile_variant(int64_t B, int64_t groups, int lowp) {
+  if (!lowp) return 0;
+  return q4_pays(B, groups < 1 ? 1 : groups) ? 2 : 1;
+}
+
 int brv_lstm_tile_forward(const float* gates_in, const float* w_hh, const float* bias, float* y,
                           float* act, float* cs, int64_t B, int64_t T, int64_t H, int64_t groups,
                           int64_t reverse_mask, int64_t y_ld, int64_t y_group_offset, int lowp,
@@ -677,7 +683,8 @@ int brv_lstm_tile_forward(const float* gates_in, const float* w_hh, const float*
              "requires H == 128, B >= 1, T >= 1, groups >= 1, groups <= 30, B a multiple of groups");
   const int per_group = (int)(B/groups);
   const unsigned grid = (unsigned)(groups*((per_group + LC - 1)/LC));
-  if (q4_pays(B, groups) && lowp) {
+  const int variant = brv_lstm_tile_variant(B, groups, lowp);
+  if (variant == 2) {
     const unsigned g4 = (unsigned)(groups*((per_group + QC - 1)/QC));
     if (lowp == 2)
       hipLaunchKernelGGL(lstm_q4_fwd_kernel<true>, dim3(g4), dim3(512), 0, (hipStream_t)stream, gates_in, w_hh, bias,
@@ -688,11 +695,11 @@ int brv_lstm_tile_forward(const float* gates_in, const float* w_hh, const float*
     BRV_HIP_OK(hipGetLastError());
     return 0;
   }
-  if (lowp == 2)
+  if (variant == 1 && lowp == 2)
     hipLaunchKernelGGL(lstm_tile_fwd_bf16_kernel<true>, dim3(grid), dim3(512), 0, (hipStream_t)stream,
                        gates_in, w_hh, bias, y, act, cs, per_group, (int)T, (int)reverse_mask,
                        (long long)y_ld, (long long)y_group_offset);
-  else if (lowp)
+  else if (variant == 1)
     hipLaunchKernelGGL(lstm_tile_fwd_bf16_kernel<false>, dim3(grid), dim3(512), 0, (hipStream_t)stream,
                        gates_in, w_hh, bias, y, act, cs, per_group, (int)T, (int)reverse_mask,
                        (long long)y_ld, (long long)y_group_offset);
@@ -712,7 +719,8 @@ int brv_lstm_tile_backward(const float* act, const float* cs, const float* w_hh,
              "requires H == 128, B >= 1, T >= 1, groups >= 1, groups <= 30, B a multiple of groups");
   const int per_group = (int)(B/groups);
   const unsigned grid = (unsigned)(groups*((per_group + LC - 1)/LC));
-  if (q4_pays(B, groups) && lowp) {
+  const int variant = brv_lstm_tile_variant(B, groups, lowp);
+  if (variant == 2) {
     const unsigned g4 = (unsigned)(groups*((per_group + QC - 1)/QC));
     if (lowp == 2)
       hipLaunchKernelGGL(lstm_q4_bwd_kernel<true>, dim3(g4), dim3(512), 0, (hipStream_t)stream, act, cs, w_hh, dy,
@@ -723,11 +731,11 @@ int brv_lstm_tile_backward(const float* act, const float* cs, const float* w_hh,
     BRV_HIP_OK(hipGetLastError());
     return 0;
   }
-  if (lowp == 2)
+  if (variant == 1 && lowp == 2)
     hipLaunchKernelGGL(lstm_tile_bwd_bf16_kernel<true>, dim3(grid), dim3(512), 0, (hipStream_t)stream,
                        act, cs, w_hh, dy, dgates, per_group, (int)T, (int)reverse_mask,
                        (long long)dy_ld, (long long)dy_group_offset);
-  else if (lowp)
+  else if (variant == 1)
     hipLaunchKernelGGL(lstm_tile_bwd_bf16_kernel<false>, dim3(grid), dim3(512), 0, (hipStream_t)stream,
                        act, cs, w_hh, dy, dgates, per_group, (int)T, (int)reverse_mask,
                        (long long)dy_ld, (long long)dy_group_offset);

@@ -720,9 +720,14 @@ int brv_causal_groupnorm_backward(const float* x, const float* dy, const float* 
                                   void* scratch, float* uv_scratch, int64_t B, int64_t C,
                                   int64_t inner, int64_t T, int64_t groups, brv_stream_t stream);
 
-/* ---- LSTM recurrence for many short chains (nn.LSTM as used by tfgridnet.py:200-216): 16
- * chains per workgroup, one exact-fp32 MFMA product per step, hidden size 128 only
- * (brv_lstm_tile_supported). Same arguments as brv_lstm_recurrent_forward / _backward EXCEPT the
+/* ---- LSTM recurrence for many short chains (nn.LSTM as used by tfgridnet.py:200-216), hidden
+ * size 128 only (brv_lstm_tile_supported). Three kernel pairs; brv_lstm_tile_variant(B, groups, lowp)
+ * names the one a launch of B chains in `groups` groups takes: 0 = 16 chains per workgroup, one
+ * exact-fp32 MFMA product per step (lowp == 0); 1 = 16 chains per workgroup on the bf16 MFMA;
+ * 2 = 4 chains per workgroup on the bf16 MFMA. Between 1 and 2 (lowp != 0) the library chooses by
+ * the number of rounds of workgroups either takes on the device's compute units; forward and
+ * backward of the same (B, groups, lowp) always take the same variant. Same arguments as
+ * brv_lstm_recurrent_forward / _backward EXCEPT the
  * gate layout of gates_in, act and dgates, which is interleaved (column = 4*unit + gate) instead
  * of torch's gate-major order; w_hh and bias stay in torch's layout. Bit g of reverse_mask makes
  * group g run over the frames backwards (the second direction of a bidirectional nn.LSTM, no
@@ -735,6 +740,7 @@ int brv_causal_groupnorm_backward(const float* x, const float* dy, const float* 
  * (the two largest streams of the then HBM-bound kernel; the input projection writes bf16 through
  * brv_gemm_bf16_mixed). */
 int brv_lstm_tile_supported(int64_t H);
+int brv_lstm_tile_variant(int64_t B, int64_t groups, int lowp);
 int brv_lstm_tile_forward(const float* gates_in, const float* w_hh, const float* bias, float* y,
                           float* act, float* cs, int64_t B, int64_t T, int64_t H, int64_t groups,
                           int64_t reverse_mask, int64_t y_ld, int64_t y_group_offset, int lowp,

@@ -119,6 +119,7 @@ NO_REFUSAL = {
     'brv_cconv_packed_bytes': 'size arithmetic only',
     'brv_lstm_recurrent_bf16_supported': 'flag query',
     'brv_lstm_tile_supported': 'flag query',
+    'brv_lstm_tile_variant': 'flag query',
     'brv_head_permute_supported': 'flag query',
     'brv_linear_small_supported': 'flag query',
     'brv_linear_small_wgrad_supported': 'flag query',
