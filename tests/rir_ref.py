@@ -78,3 +78,16 @@ def bound(h_ref):
     """The parity bound of the GPU tests: one fp32 output rounding with a factor two of slack, relative to the
     response's peak."""
     return 2.0**-23*float(np.abs(h_ref).max())
+
+
+def last_tile_images(rows, index, job, taps, fs, window, less=0.0, more=0.0, c=343.0, tile=128):
+    """Images of a job's band tables (rows of ``3 + K`` doubles, the squared offset in column 2) that the tile kernels
+    list for the last tile of a row of ``taps`` taps: those at a distance that can land inside a window of a tap of
+    that tile, an image at distance ``d`` arriving at ``(d + delta) fs / c`` with ``-less <= delta <= more``."""
+    hdr, nx, ny, nz = (int(v) for v in index[job, :4])
+    x, y, z = (rows[first:first + n, 2] for first, n in ((hdr + 1, nx), (hdr + 1 + nx, ny), (hdr + 1 + nx + ny, nz)))
+    t0 = (taps - 1)//tile*tile
+    lo = max((t0 - window/2 - 1e-6)*c/fs - less, 0.0)
+    hi = (taps - 1 + window/2 + 1e-6)*c/fs + more
+    d2 = x[:, None, None] + y[None, :, None] + z[None, None, :]
+    return int(((d2 >= lo*lo) & (d2 <= hi*hi)).sum())

@@ -1,5 +1,5 @@
-"""The shoebox image-source simulator on the GPU (brever_amd/rir.py, csrc/rir/) against the fp64 restatement of
-tests/rir_ref.py, its bitwise repeatability, and the simulated BRIRs as the pool of the mixture engine.
+"""The shoebox image-source simulator on the GPU (brever_amd/rir.py; csrc/rir/rir.hip on rir_shell.cuh and rir_host.h) against
+the fp64 restatement of tests/rir_ref.py, its bitwise repeatability, and the simulated BRIRs as the pool of the mixture engine.
 
 Parity is held on the fp32 output: ``|h - float32(h_ref)| <= 2^-23 max|h_ref|`` per tap, one output rounding with a
 factor two of slack; the fp64 evaluation error of either side is orders of magnitude below it."""

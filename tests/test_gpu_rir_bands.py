@@ -1,6 +1,6 @@
-"""Octave-band walls and the spherical-head ear on the GPU (brever_amd/rir.py, csrc/rir/rir_bands.cuh)
-against the fp64 restatement of tests/rir_bands_ref.py, bitwise repeatability, and the plumbing up to the dataset
-script.
+"""Octave-band walls and the spherical-head ear on the GPU (brever_amd/rir.py; csrc/rir/rir_bands.cuh on the walk of
+rir_shell.cuh, the FIR tile of rir_fir.cuh and the host side of rir_host.h) against the fp64
+restatement of tests/rir_bands_ref.py, bitwise repeatability, and the plumbing up to the dataset script.
 
 Parity is the bound of tests/test_gpu_rir.py, ``rir_ref.bound``: ``|h - float32(h_ref)| <= 2^-23 max|h_ref|`` per tap.
 It carries over because every sum, those of the filters included, is fp64 and the only fp32 rounding is the store."""
@@ -95,6 +95,31 @@ def test_six_walls_different_in_every_band(K, fs, near):
     assert np.abs(ref[0] - _ref_room(_room_b(beta=[_beta(K)[0]]*K, angles=(90.0,), distance=near + RAD, taps=333),
                                      fs, window=33)[0]).max() > 1e-4       # the bands matter
     _hold_room(f'K = {K}', rir.simulate_brirs([room], fs=fs, window=33, device=DEV)[0], ref)
+
+
+@pytest.mark.parametrize('model', ['pattern', 'sphere'])
+@pytest.mark.parametrize('K', range(1, 9))
+def test_every_tile_kernel_the_dispatch_can_return(K, model):
+    """All sixteen instantiations of ``rir_bands_tile_kernel``, which share one walk, one list entry and one tap weight
+    (csrc/rir/rir_shell.cuh). The last band's centre has to lie below fs/2, so K = 7 and 8 run at 48 kHz. The taps are
+    chosen so that the last tile of a channel row, which is not a whole tile, lists more than 256 images: a list of
+    512 entries (C <= 4) is then flushed in the middle of the tile and a list of 256 many times. The count is taken
+    from the job's own tables, so that the input cannot silently stop reaching the flush."""
+    fs, taps = (FS, 600) if K <= 6 else (48000, 2900)
+    room = _room_b(beta=_beta(K), taps=taps, ear_model=model)
+    _, pad = rir.band_filters(fs, K, model)
+    ears, side = room.ears(), room.side()
+    geom = [rir._band_geom_row(room.dims, room.beta, room.source(40.0), room.head if model == 'sphere' else ears[e],
+                               side if e == 0 else -side, room.ear_pattern) for e in range(2)]
+    rows, index = rir.build_band_tables(geom, [[taps, e, 2] for e in range(2)],
+                                        rir.band_opts(fs, K, model, window=33, pad=pad))
+    widen = (0.5*math.pi*RAD, RAD) if model == 'sphere' else (0.0, 0.0)     # the range of the head's delay
+    images = [R.last_tile_images(rows, index, e, taps + pad, fs, 33, *widen) for e in range(2)]
+    print(f'K = {K} {model}: rows of {taps + pad} taps, {(taps + pad - 1)%rir.TILE + 1} in the last tile, which lists '
+          f'{images} images')
+    assert (taps + pad)%rir.TILE != 0 and min(images) > 256
+    _hold_room(f'K = {K} {model}', rir.simulate_brirs([room], fs=fs, window=33, device=DEV)[0],
+               _ref_room(room, fs, window=33))
 
 
 def _envelope_peak(h):

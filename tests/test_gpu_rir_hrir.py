@@ -1,6 +1,6 @@
-"""The measured ear on the GPU (brever_amd/rir.py, csrc/rir/rir_hrir.cuh) against the fp64 restatement of
-tests/rir_hrir_ref.py, against closed forms and the merged kernels, bitwise repeatability, and the plumbing up to the
-dataset script.
+"""The measured ear on the GPU (brever_amd/rir.py; csrc/rir/rir_hrir.cuh on the walk of rir_shell.cuh, the FIR tile of
+rir_fir.cuh and the host side of rir_host.h) against the fp64 restatement of tests/rir_hrir_ref.py,
+against closed forms and the merged kernels, bitwise repeatability, and the plumbing up to the dataset script.
 
 Parity is the bound of tests/test_gpu_rir.py, ``rir_ref.bound``: ``|h - float32(h_ref)| <= 2^-23 max|h_ref|`` per tap.
 It carries over because every sum -- direction rows, fold and band filters -- is fp64 and the only fp32 rounding is the
@@ -55,15 +55,15 @@ def _room(name, beta, hrirs, **over):
     return rir.ShoeboxRoom(**kw)
 
 
-def _ref(room, angle=None, **kw):
+def _ref(room, angle=None, fs=FS, **kw):
     """``(response, margins, directions in use)`` of the restatement for one angle of a room, computed once per
     argument set and left unchanged."""
     angle = room.angles[0] if angle is None else angle
     key = (room.dims, room.beta, room.head, room.yaw, angle, room.distance, room.taps, room.hrirs.directions.tobytes(),
-           room.hrirs.hrirs.tobytes(), tuple(sorted(kw.items())))
+           room.hrirs.hrirs.tobytes(), fs, tuple(sorted(kw.items())))
     if key not in _REF:
         used = set()
-        h, margins = H.brir(room.dims, room.beta, room.head, room.yaw, angle, room.distance, room.taps, FS,
+        h, margins = H.brir(room.dims, room.beta, room.head, room.yaw, angle, room.distance, room.taps, fs,
                             room.hrirs.directions, room.hrirs.hrirs, used=used, **kw)
         h.setflags(write=False)
         _REF[key] = (h, margins, len(used))
@@ -100,6 +100,32 @@ def test_parity_with_the_restatement(name, bands, taps_h):
     """257 + 128 and 700 + 128 taps of a direction row are not whole tiles, the 700-tap room fills the list of a far
     tile more than once, and neither 24 nor 40 HRIR taps are a multiple of the fold's 16."""
     _parity(f'{name} K = {bands} T_h = {taps_h}', _room(name, _beta(bands) if bands else BETA6, _grid_set(taps_h)))
+
+
+@pytest.mark.parametrize('K', range(1, 9))
+def test_every_tile_kernel_the_dispatch_can_return(K):
+    """All eight instantiations of ``rir_hrir_tile_kernel``, which share the walk, the list entry and the tap weight of
+    the band kernels (csrc/rir/rir_shell.cuh), on the room of the same test of tests/test_gpu_rir_bands.py. The last
+    band's centre has to lie below fs/2, so K = 7 and 8 run at 48 kHz, with a set of that rate. The last tile of a
+    direction row is not a whole tile and lists more than 256 images, counted from the job's own tables: a list of 512
+    entries (K <= 6) is sorted and flushed in the middle of the tile, a list of 256 many times."""
+    fs, taps = (FS, 600) if K <= 6 else (48000, 2900)
+    az, el = H.fixture_grid()
+    hrirs = _grid_set(24) if fs == FS else rir.HrirSet.from_angles(az, el, H.fixture_hrirs(38, 24, 1), fs)
+    room = rir.ShoeboxRoom((3.2, 2.6, 2.4), _beta(K), (1.4, 1.2, 1.3), math.radians(20.0), 1.0, (40.0,), taps,
+                           ear_model='hrir', hrirs=hrirs)
+    _, pad = rir.band_filters(fs, K)
+    rows, index, _ = rir.build_hrir_tables(rir._hrir_geom_row(room.dims, room.beta, room.source(40.0), room.head,
+                                                              room.front(), room.side()), [[taps, 0, 2, 1]],
+                                           rir.hrir_opts(fs, K, hrirs, 33, pad=pad), hrirs.directions)
+    images = R.last_tile_images(rows, index, 0, taps + pad, fs, 33)
+    print(f'K = {K}: rows of {taps + pad} taps, {(taps + pad - 1)%rir.TILE + 1} in the last tile, which lists {images} '
+          f'images')
+    assert (taps + pad)%rir.TILE != 0 and images > 256
+    ref, margins, used = _ref(room, fs=fs, window=33)
+    print(f'K = {K}: {len(margins)} images, {used} of {len(hrirs)} directions in use, least margin {margins.min():.2e}')
+    assert margins.min() >= MARGIN
+    _hold_ears(f'K = {K}', rir.simulate_brirs([room], fs=fs, window=33, device=DEV)[0][0], ref)
 
 
 @pytest.mark.parametrize('angle,azimuth', [(90.0, 90), (-90.0, 270), (0.0, 0)])
