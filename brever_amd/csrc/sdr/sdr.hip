@@ -336,5 +336,8 @@ int brv_sdr_backward(const float* x, const float* y, const int64_t* lengths, con
 
 }
 
+// SIR and SAR: the joint projection on several references (include/sdr/brever_bsseval.h), on the kernels above
+#include "bsseval.cuh"
+
 // the library's last-error message and its two status exports (../status.h)
 BRV_DEFINE_STATUS(brv_sdr_version, brv_sdr_last_error)

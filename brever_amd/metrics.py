@@ -6,6 +6,11 @@ clean target, batched ``(B, L)`` or single ``(L,)``.
 * ``sdr`` (not in the reference): the BSS-eval signal-to-distortion ratio with a 512-tap allowed distortion filter,
   in fp64 on the HIP path (``sdr.py``, ``csrc/sdr/sdr.hip``); the call shape of ``snr`` plus ``filter_length`` and
   ``load_diag``;
+* ``sir`` / ``sar`` (not in the reference): the other two of the BSS-eval triple, the signal-to-interference and the
+  signal-to-artifacts ratio (``bsseval.py``, ``csrc/sdr/bsseval.cuh``). They need a second reference, ``noise``: for
+  a mixture ``foreground + background`` it is ``mixture - target``, which ``score`` below passes. The *input* column
+  of ``sar`` sits at or near its floor of ``10 log10(2^52)`` dB by construction: the mixture lies in the span of its
+  own two components;
 * ``stoi`` / ``estoi``: the reference calls the ``pystoi`` / ``batch_pystoi`` wheels (absent from
   this image, not under the reference tree). Here the published algorithm runs as HIP kernels
   (``csrc/stoi.hip``: polyphase resampling to 10 kHz, silent-frame removal, one-third octave band
@@ -16,9 +21,12 @@ clean target, batched ``(B, L)`` or single ``(L,)``.
   that reference configs resolve; calling it uses the wheel when it is importable and raises a
   clear ``ImportError`` otherwise (``metric_available('pesq')`` tells which).
 """
+import inspect
+
 import numpy as np
 import torch
 
+from . import bsseval as bss_hip
 from . import hip
 from . import sdr as sdr_hip
 from . import stoi as stoi_hip
@@ -175,3 +183,63 @@ def sdr(x, y, lengths=None, filter_length=512, load_diag=0.0):
     value, _ = sdr_hip.forward(x.detach().reshape(B, W).float().contiguous(),
                                y.detach().reshape(B, W).float().contiguous(), lengths, filter_length, load_diag)
     return value.item() if unbatched else value
+
+
+def _bss(which, x, y, lengths, noise, filter_length, load_diag):
+    """``sir`` / ``sar`` of the estimate ``x`` against the references ``(y, noise ...)`` (``bsseval.bss_eval`` with
+    one estimate, whose target is ``y``)."""
+    filter_length, load_diag = sdr_hip.check_options(filter_length, load_diag)
+    if noise is None:
+        raise ValueError(f"the '{which}' metric needs a second reference: pass noise= (for a mixture of a target "
+                         f'and a background, mixture - target; metrics.score does that), one (B, L) signal or up to '
+                         f'{bss_hip.MAX_REFERENCES - 1} as (B, K, L)')
+    x, y, noise = torch.as_tensor(x), torch.as_tensor(y), torch.as_tensor(noise)
+    hip.require_device(x, y, noise)
+    x, y, lengths, unbatched = _check_input(x, y, lengths)
+    B, W = x.shape[0], x.shape[-1]
+    if unbatched and noise.ndim == 1:
+        noise = noise[None]
+    if noise.ndim == 2:
+        noise = noise[:, None]
+    if noise.ndim != 3 or (noise.shape[0], noise.shape[-1]) != (B, W) or \
+            not 1 <= noise.shape[1] <= bss_hip.MAX_REFERENCES - 1:
+        raise ValueError(f'noise must be (B, L) or (B, K, L) with K <= {bss_hip.MAX_REFERENCES - 1} and match the '
+                         f'inputs {tuple(x.shape)}, got {tuple(noise.shape)}')
+    out = bss_hip.bss_eval(x.reshape(B, 1, W), torch.cat([y.reshape(B, 1, W).to(noise.dtype), noise], dim=1), lengths,
+                           filter_length, load_diag, permute=False)
+    value = getattr(out, which)[:, 0]
+    return value.item() if unbatched else value
+
+
+@MetricRegistry.register('sir')
+def sir(x, y, lengths=None, noise=None, filter_length=512, load_diag=0.0):
+    """BSS-eval signal-to-interference ratio in dB: of the part of ``x`` that lies in the span of the references
+    ``(y, noise)``, each through ``filter_length`` taps, how much is ``y``'s. ``noise``: the other references,
+    ``(B, L)`` or ``(B, K, L)`` with ``K <= 3`` (``(L,)`` for a single row). A ``(B,)`` fp64 tensor on the inputs'
+    device, or a float for a single row; NaN for a degenerate one."""
+    return _bss('sir', x, y, lengths, noise, filter_length, load_diag)
+
+
+@MetricRegistry.register('sar')
+def sar(x, y, lengths=None, noise=None, filter_length=512, load_diag=0.0):
+    """BSS-eval signal-to-artifacts ratio in dB: the part of ``x`` in the span of the references ``(y, noise)``
+    against the part outside it. Arguments and result as ``sir``. Scoring a mixture against its own components gives
+    the floor, ``10 log10(2^52)`` dB or close to it."""
+    return _bss('sar', x, y, lengths, noise, filter_length, load_diag)
+
+
+def takes_noise(name):
+    """True for a registered metric whose signature has a ``noise`` parameter (``sir``, ``sar``)."""
+    return 'noise' in inspect.signature(MetricRegistry.get(name)).parameters
+
+
+def score(name, x, target, lengths, mixture=None):
+    """The registered metric ``name`` of ``x`` against ``target``. A metric whose signature has a ``noise`` parameter
+    (``sir``, ``sar``) gets ``noise = mixture - target``, the second component of a mixture
+    ``foreground + background``; every other metric is called as ``metric(x, target, lengths=lengths)``."""
+    fn = MetricRegistry.get(name)
+    if not takes_noise(name):
+        return fn(x, target, lengths=lengths)
+    if mixture is None:
+        raise ValueError(f"the '{name}' metric needs the mixture: its second reference is mixture - target")
+    return fn(x, target, lengths=lengths, noise=torch.as_tensor(mixture) - torch.as_tensor(target))

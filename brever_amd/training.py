@@ -28,7 +28,7 @@ import torch.distributed as dist
 from .batching import BatchSamplerRegistry, DistributedBatchSamplerWrapper
 from .data import BreverDataLoader, DevicePrefetcher
 from .inspect import NoParse, Parse
-from .metrics import MetricRegistry
+from .metrics import MetricRegistry, score, takes_noise
 from .models import count_params
 from .models.base import BreverBaseModel
 from .parallel import GradSynchronizer, broadcast_parameters
@@ -423,9 +423,11 @@ class BreverTrainer:
         if output.ndim == 3:
             output = output[:, 0]
         target = target[:, 0].mean(-2)
+        # the mono mixture, for the metrics that take a second reference (sir, sar)
+        mixture = input_.mean(-2) if any(takes_noise(name) for name in self.val_metrics) else None
         metrics = {}
         for name in self.val_metrics:
-            values = MetricRegistry.get(name)(output, target, lengths=lengths)
+            values = score(name, output, target, lengths, mixture=mixture)
             # (stoi / estoi hand back NumPy arrays: every logged value is a device tensor, as
             # `reduce` and the loss logger expect)
             metrics[name] = torch.as_tensor(values, dtype=torch.float32, device=self.device).mean()
